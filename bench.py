@@ -13,6 +13,12 @@ only collective of the path).
 Run as ``python bench.py`` (N=1) or under ``torch.distributed.run`` with one
 rank per GPU; shots are sharded by global shot index (weak scaling: every rank
 decodes ``--shots`` shots per step).  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times ``--steps`` steps and prints the line.
+``--full`` adds what takes runs of its own: the rocprofv3 PMC traffic passes,
+the fp32 line, the CPU baseline, the per-kernel roofline launches of the other
+workloads and the C-ABI all-reduce cross-check.  ``--dump-outputs DIR`` writes
+the counters the timed steps returned as ``DIR/<name>.npy``.
 """
 from __future__ import annotations
 
@@ -119,13 +125,14 @@ def parse():
     ap.add_argument("--precision", type=int, default=64, choices=(32, 64),
                     help="64 = ldpc's float64 arithmetic (the reference; headline), 32 = fast mode (not the reference)")
     ap.add_argument("--fp32-line", type=int, default=1,
-                    help="also time the fp32 fast mode on the same workload (reported beside the headline, N=1)")
+                    help="with --full: also time the fp32 fast mode on the same workload (reported beside the headline, N=1)")
     ap.add_argument("--pmc-traffic", type=int, default=1,
-                    help="measure HBM bytes per launch with rocprofv3 PMC passes of this build (N=1, before GPU init)")
+                    help="with --full: measure HBM bytes per launch with rocprofv3 PMC passes of this build (N=1, before "
+                         "GPU init)")
     ap.add_argument("--max-iter-ratio", type=float, default=10)
     ap.add_argument("--logical", default="Total", choices=("X", "Z", "Total"))
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="budget of the CPU baseline sample")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="with --full: budget of the CPU baseline sample")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--comm", default="torch", choices=("torch", "native"),
                     help="torch: one rank per GPU (torchrun), counters all-reduced by torch.distributed; native: ONE "
                          "process drives --gpus GPUs through the C ABI (qldpc_mc_run_sharded + qldpc_comm_init_all)")
@@ -141,6 +148,14 @@ def parse():
     ap.add_argument("--dec2", default="bp", choices=("bp", "bposd"),
                     help="phenl final-round decoder: BP, or BP+OSD-E(10) as the notebooks use")
     ap.add_argument("--num-cycles", type=int, default=13)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the rocprofv3 PMC traffic passes (--pmc-traffic), "
+                         "the fp32 line (--fp32-line), the CPU baseline (--no-cpu-baseline / --cpu-seconds), the "
+                         "per-kernel roofline launches of the phenl / bposd / circuit workloads and the N > 1 "
+                         "C-ABI all-reduce cross-check; without it only the warm-up and the timed steps run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned to its caller as DIR/<name>.npy "
+                         "(float64; rank 0)")
     return ap.parse_args()
 
 
@@ -459,7 +474,10 @@ def phenl_main(a, torch, dist, world, rank, dev, st_pmc=None):
         dist.barrier()
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
+    before_last = None
     for i in range(a.steps):
+        if a.dump_outputs and i == a.steps - 1:
+            before_last = cnt.clone()  # --dump-outputs: the counters as the last step found them
         ph.launch(p / 2, p / 2, p / 2, p, SEED + 3, ((a.warmup + i) * world + rank) * S, S, R, a.logical, cnt)
     if world > 1:
         dist.all_reduce(cnt)
@@ -472,6 +490,10 @@ def phenl_main(a, torch, dist, world, rank, dev, st_pmc=None):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     w = cnt.cpu().numpy()
+    if before_last is not None:
+        if world > 1:
+            dist.all_reduce(before_last)
+        dump_outputs(a, rank, {"counters": w, "counters_last_step": w - before_last.cpu().numpy()})
     shots, decodes, iters = int(w[0]), int(w[2] + w[3]), int(w[4] + w[5])
     # ST graph edges dominate: (num_rounds-1) ST decodes + 1 final decode per sector per sample
     E_st = int(codes.space_time_csr(code.hz, rep).nnz)
@@ -486,8 +508,9 @@ def phenl_main(a, torch, dist, world, rank, dev, st_pmc=None):
     peak_src = None
     if fam is not None:
         peak, peak_src = lds_ceiling(fam)
+    # --full: the space-time decoder kernel alone, in launches of its own
     stk = st_kernel_roofline(torch, ph.decoders[0], codes.space_time_csr(code.hz, rep), p, min(S, 65536), bpe, bound, peak,
-                             dev, lds_pmc=st_pmc, peak_src=peak_src)
+                             dev, lds_pmc=st_pmc, peak_src=peak_src) if a.full else None
     out = {
         "metric": "phenomenological space-time samples/sec (BASELINE config 5; not the headline)",
         "value": shots / elapsed, "unit": "samples/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
@@ -619,6 +642,8 @@ def bposd_main(a, torch, dist, world, rank, dev):
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    # the last step's (failures, shots, osd_decodes) as bposd_counts returned them
+    dump_outputs(a, rank, {"bposd_counts_last_step": [f, c, o]})
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -636,7 +661,7 @@ def bposd_main(a, torch, dist, world, rank, dev):
                    "shots_per_gpu_step": S, "parallelism": f"shot-sharded x{world}"},
         "osd_decodes": osd_n, "osd_frac_of_decodes": osd_n / max(1, 2 * shots),
         "logical_error_rate": fails / max(shots, 1),
-        "roofline": osd_kernel_roofline(torch, code, p, None, dev) if world == 1 else None,
+        "roofline": osd_kernel_roofline(torch, code, p, None, dev) if a.full and world == 1 else None,
         "note": "wall clock of the device-resident BP+OSD loop: fused engine-3 MC capturing the decodes that reach "
                 "max_iter (posteriors, syndrome, error), GPU OSD (osd_gpu_kernel) on those, device re-check of their "
                 "residuals (qldpc_mc_set_osd)",
@@ -724,6 +749,7 @@ def native_comm_main(a, torch):
     elapsed = time.perf_counter() - t0
     if res.shots != S * n * a.steps:
         raise RuntimeError(f"counter mismatch: {res.shots} != {S} x {n} x {a.steps}")
+    dump_outputs(a, 0, {"counters": result_words(res), "counters_last_step": result_words(r)})
     dec = sum(res.sector_decodes)
     emit({"metric": "BP-decoded shots/sec (node) on hgp_34_n1600 + % of HBM/LDS roofline", "value": res.shots / elapsed,
           "unit": "shots/s", "n_gpus": n, "steps": a.steps, "warmup": a.warmup, "ms_per_step": elapsed / a.steps * 1e3,
@@ -841,7 +867,8 @@ def circuit_main(a, torch, dist, world, rank, dev):
            "wer_per_cycle": word_error_rate_per_cycle(fails, shots, code.K, a.num_cycles),
            "printed_reference_wer": 0.00019299501269032238 if (p == 1e-3 and a.num_cycles == 13 and a.num_rep == 3
                                                                and d == 3 and a.circuit_noise == "cx") else None,
-           "roofline": circuit_kernel_roofline(torch, sim, g, dev, min(S, 65536))}
+           "roofline": circuit_kernel_roofline(torch, sim, g, dev, min(S, 65536)) if a.full else None}
+    dump_outputs(a, rank, {"counters_last_step": result_words(r)})  # the last fused_counts' MCResult
     if rank == 0:
         emit(out)
     if world > 1:
@@ -860,6 +887,24 @@ def emit(out):
         os.write(_JSON_FD, line)
 
 
+def result_words(r):
+    """An MCResult's counters in the order of the device counter words (MCResult.from_words)."""
+    return np.concatenate([[r.shots, r.failures], r.sector_decodes, r.sector_iters, r.sector_nonconv, r.sector_fail,
+                           np.ravel(r.iter_hist)])
+
+
+def dump_outputs(a, rank, arrays):
+    """--dump-outputs DIR: the arrays the timed path handed its caller, as DIR/<name>.npy (float64: the
+    int64 counters are exact below 2^53; 16 KiB per array).  The inputs are a function of the
+    arguments alone (fixed SEED, shot blocks indexed by step and rank), so two builds run with the same
+    arguments can be compared array for array."""
+    if not a.dump_outputs or rank != 0:
+        return
+    os.makedirs(a.dump_outputs, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(a.dump_outputs, name + ".npy"), np.asarray(arr, dtype=np.float64))
+
+
 def main():
     global _JSON_FD
     a = parse()
@@ -873,9 +918,9 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     traffic = None
     st_pmc = None
-    if a.workload == "data" and world == 1 and a.pmc_traffic and a.comm == "torch":
+    if a.full and a.workload == "data" and world == 1 and a.pmc_traffic and a.comm == "torch":
         traffic = pmc_traffic(a)  # child processes, before this process initialises the GPU
-    if a.workload == "phenl" and world == 1 and a.pmc_traffic and a.comm == "torch":
+    if a.full and a.workload == "phenl" and world == 1 and a.pmc_traffic and a.comm == "torch":
         # the space-time decoder kernel alone, on the same syndromes st_kernel_roofline decodes
         name = a.code if a.code != "hgp_34_n1600" else "hgp_34_n1225_q3"
         st_pmc = pmc_lds([os.path.join(ROOT, "tools", "prof_st.py"), str(a.p), str(min(int(a.shots), 65536)),
@@ -910,6 +955,7 @@ def main():
 
     code = codes.get_code(a.code)
     r = time_data(a, a.precision, torch, dist, world, rank, dev)
+    dump_outputs(a, rank, r["outputs"])
     n = code.N
     max_iter = int(n / a.max_iter_ratio)
     p = a.p
@@ -977,7 +1023,7 @@ def main():
                      "hbm": {"achieved": (tb / (r["kern_ms"] * 1e-3) / 1e9) if tb else None,
                              "peak": HBM_PEAK_GBS, "unit": "GB/s", "pmc": traffic}},
     }
-    if world == 1 and a.precision == 64 and a.fp32_line:
+    if a.full and world == 1 and a.precision == 64 and a.fp32_line:
         # fp32 fast mode on the same workload: reported beside the headline, never as `value`
         r32 = time_data(a, 32, torch, dist, world, rank, dev)
         # on the headline's basis: the same algorithmic bytes (16 B per edge-iteration in fp32) over the
@@ -995,7 +1041,7 @@ def main():
             "logical_error_rate": r32["failures"] / max(r32["shots"], 1),
             "note": "float32 messages: NOT ldpc's float64 arithmetic (decoded-vector agreement with fp64 is "
                     "measured in tests/test_gpu_agreement.py)"}
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(code, p, max_iter, a.logical, a.cpu_seconds)
     if rank == 0:
         emit(out)
@@ -1042,8 +1088,12 @@ def time_data(a, precision, torch, dist, world, rank, dev):
     torch.cuda.synchronize(dev)
 
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.steps)]
+    dump = bool(a.dump_outputs) and precision == a.precision
+    before_last = None
     t0 = time.perf_counter()
     for i in range(a.steps):
+        if dump and i == a.steps - 1:
+            before_last = cnt.clone()  # --dump-outputs: the counters as the last step found them (one small async copy)
         ev[i][0].record(stream)
         step(a.warmup + i)
         ev[i][1].record(stream)
@@ -1060,13 +1110,21 @@ def time_data(a, precision, torch, dist, world, rank, dev):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     kern_ms = float(np.mean([s.elapsed_time(e) for s, e in ev]))
-    comm_check = native_comm_check(torch, dist, world, rank, dev, local, cnt) if world > 1 and precision == a.precision \
-        else None
+    comm_check = native_comm_check(torch, dist, world, rank, dev, local, cnt) \
+        if a.full and world > 1 and precision == a.precision else None
     w = cnt.cpu().numpy()
     shots = int(w[0])
     if shots != S * a.steps * world:
         raise RuntimeError(f"counter mismatch: {shots} shots != {S} x {a.steps} x {world}")
+    outputs = {}
+    if dump:
+        if world > 1:
+            dist.all_reduce(before_last)
+        # the caller's counter words (shots, failures, per-sector decodes / iterations / non-converged /
+        # failures, iteration histograms) after the last timed launch, and that launch's own contribution
+        outputs = {"counters": w, "counters_last_step": w - before_last.cpu().numpy()}
     return {"value": shots / elapsed, "elapsed": elapsed, "kern_ms": kern_ms, "shots": shots, "failures": int(w[1]),
+            "outputs": outputs,
             "decodes": int(w[2] + w[3]), "iters": int(w[4] + w[5]), "nonconv": int(w[6] + w[7]),
             "kernel": kernel_name(dx or dz), "engine": (dx or dz).geometry()["engine"],
             "kernel_id": (dx or dz).geometry().get("kernel_id"), "comm_check": comm_check}

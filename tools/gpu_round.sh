@@ -16,7 +16,7 @@ timeout -k 10 600 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout
 rc=$?; tail -3 "$O/pytest_gpu.log"; [ $rc -eq 0 ] || exit $rc
 
 step bench
-timeout -k 10 300 python -u bench.py > "$O/bench.json" 2> "$O/bench.err" || { tail "$O/bench.err"; exit 1; }
+timeout -k 10 300 python -u bench.py --full > "$O/bench.json" 2> "$O/bench.err" || { tail "$O/bench.err"; exit 1; }
 cat "$O/bench.json"
 
 step kernel-trace
@@ -30,7 +30,7 @@ for c in FETCH_SIZE WRITE_SIZE; do
     python3 "$R/bench.py" --steps 1 --warmup 0 --no-cpu-baseline > "$O/pmc_$c.json" 2> "$O/pmc_$c.err" || exit 1
 done
 step phenl
-timeout -k 10 300 python3 "$R/bench.py" --workload phenl --p 0.005 --shots 65536 --steps 3 --warmup 1 > "$O/bench_phenl.json" 2> "$O/bench_phenl.err" || { tail "$O/bench_phenl.err"; exit 1; }
+timeout -k 10 300 python3 "$R/bench.py" --workload phenl --p 0.005 --shots 65536 --steps 3 --warmup 1 --full > "$O/bench_phenl.json" 2> "$O/bench_phenl.err" || { tail "$O/bench_phenl.err"; exit 1; }
 cat "$O/bench_phenl.json"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/trace_phenl" -o run -- \
   python3 "$R/bench.py" --workload phenl --p 0.005 --shots 65536 --steps 1 --warmup 1 > "$O/bench_phenl_trace.json" 2> "$O/bench_phenl_trace.err" || exit 1
