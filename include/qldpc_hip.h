@@ -288,6 +288,14 @@ int qldpc_bp_engine(const qldpc_bp *bp, int32_t *engine);
  * row_chunks = 16-byte chunks per check row (engines 2-4). */
 int qldpc_bp_kernel_id(const qldpc_bp *bp, int32_t *kernel_id, int32_t *row_chunks);
 
+/* The route qldpc_bp_create would take for this graph, priors and the QLDPC_* switches, decided
+ * on the host alone (no device call: runs on a machine without a GPU).  out[0..7] = engine,
+ * kernel_id, row_chunks, threads, vars_per_thread, lds_bytes, degree3_slots, degree2_slots as the
+ * decoder's qldpc_bp_engine / _kernel_id / _geometry / _degree3_slots report them; out_len >= 8.
+ * The errors of qldpc_bp_create that do not involve the device; ENOTSUP for product-sum. */
+int qldpc_bp_plan(const qldpc_graph *g, const double *channel_probs, int32_t bp_method, int32_t precision,
+                  int32_t vars_per_thread, int32_t min_col_slots, int32_t *out, int32_t out_len);
+
 /* Engine 3: leading variable slots per thread that hold only variables of
  * column degree <= 3 (variables are host-sorted by degree; those slots skip the
  * 4th edge slot at compile time).  0 for the other engines and for the fp64

@@ -29,7 +29,7 @@ EXPORTED = [
     "qldpc_comm_allreduce_counters_group", "qldpc_comm_destroy", "qldpc_mc_run_sharded", "qldpc_sample_errors",
     "qldpc_stream_sync", "qldpc_bp_kernel_id", "qldpc_build_flags", "qldpc_circ_create", "qldpc_circ_set_final_osd", "qldpc_circ_set_sampler",
     "qldpc_circ_info", "qldpc_circ_launch", "qldpc_circ_sample", "qldpc_circ_destroy",
-    "qldpc_shard_range", "qldpc_bp_lds_model", "qldpc_m2s_place_model",
+    "qldpc_shard_range", "qldpc_bp_lds_model", "qldpc_m2s_place_model", "qldpc_bp_plan",
 ]
 BUILD_EXPERIMENTAL = 1  # qldpc_build_flags(): the measured-and-not-kept kernel families are compiled in
 COMM_ID_BYTES = 128
@@ -178,6 +178,8 @@ def _declare(L):
     L.qldpc_sample_errors.argtypes = [_dbl, _dbl, _dbl, _u64, _u64, _i64, _i32, _vp, _vp, _vp]
     L.qldpc_bp_kernel_id.restype = ctypes.c_int
     L.qldpc_bp_kernel_id.argtypes = [_vp, ctypes.POINTER(_i32), ctypes.POINTER(_i32)]
+    L.qldpc_bp_plan.restype = ctypes.c_int
+    L.qldpc_bp_plan.argtypes = [_vp, _vp, _i32, _i32, _i32, _i32, ctypes.POINTER(_i32), _i32]
     L.qldpc_stream_sync.restype = ctypes.c_int
     L.qldpc_stream_sync.argtypes = [_vp]
     L.qldpc_build_flags.restype = ctypes.c_int

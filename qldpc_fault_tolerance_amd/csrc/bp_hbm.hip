@@ -47,7 +47,7 @@ using namespace qldpc;
 
 constexpr int kHRow = 12;  // max row degree (compile-time register block)
 constexpr int kHCol = 12;  // max column degree
-constexpr int kHThreads = 256;
+constexpr int kHThreads = qldpc_rt::kHbmThreads;
 
 struct HArgs {
   const int32_t* rp;     // [m+1] CSR row pointers (row-major edge ids)
@@ -354,9 +354,6 @@ int hbm_prepare(qldpc_bp* bp) {
       hipMemcpy(bp->h_cp.p, cp.data(), cp.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
       (!crpos.empty() && hipMemcpy(bp->h_crpos.p, crpos.data(), crpos.size() * 4, hipMemcpyHostToDevice) != hipSuccess))
     return set_err(QLDPC_EHIP, "upload HBM-engine tables");
-  bp->TB = kHThreads;
-  bp->VPL = 1;
-  bp->lds_bytes = 0;
   return 0;
 }
 
@@ -367,7 +364,7 @@ bool hbm_xlds(const qldpc_bp* bp) {
 }
 
 size_t hbm_wave_bytes(const qldpc_bp* bp) {
-  const size_t tsize = bp->precision == 32 ? 4 : 8;
+  const size_t tsize = bp->route.precision == 32 ? 4 : 8;
   const size_t b = (size_t)2 * bp->g->nnz * 64 * tsize + (hbm_xlds(bp) ? 0 : (size_t)bp->g->n * 64);
   return (b + 255) & ~(size_t)255;
 }
@@ -423,7 +420,7 @@ int hbm_decode_launch(qldpc_bp* bp, const uint8_t* synd, uint8_t* corr, int32_t*
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kHThreads), shm, stream, a, a.rp, a.rcol, a.rcpos, a.cp,
                        a.crpos, a.llr);
   };
-  if (bp->precision == 32)
+  if (bp->route.precision == 32)
     xl ? launch(hdec_kernel<float, true>) : launch(hdec_kernel<float, false>);
   else
     xl ? launch(hdec_kernel<double, true>) : launch(hdec_kernel<double, false>);

@@ -172,10 +172,10 @@ int ps_decode_launch(const qldpc_bp* bp, const uint8_t* synd, uint8_t* corr, int
   a.max_iter = bp->max_iter;
   const long long cap = bp->ps_grid;
   const int grid = (int)std::max<long long>(1, std::min<long long>(B, cap));
-  if (bp->precision == 32)
-    hipLaunchKernelGGL(ps_decode_kernel<float>, dim3(grid), dim3(kPsThreads), bp->lds_bytes, stream, a);
+  if (bp->route.precision == 32)
+    hipLaunchKernelGGL(ps_decode_kernel<float>, dim3(grid), dim3(kPsThreads), bp->route.lds_bytes, stream, a);
   else
-    hipLaunchKernelGGL(ps_decode_kernel<double>, dim3(grid), dim3(kPsThreads), bp->lds_bytes, stream, a);
+    hipLaunchKernelGGL(ps_decode_kernel<double>, dim3(grid), dim3(kPsThreads), bp->route.lds_bytes, stream, a);
   QLDPC_HIP(hipGetLastError());
   return 0;
 }

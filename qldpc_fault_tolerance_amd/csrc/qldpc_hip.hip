@@ -70,19 +70,19 @@ SVariant get_rvariant(int engine, int precision, int vpl, int d3k, int dmax) {
 
 // fp64 engine-3 kernels built for <= 256-thread workgroups (engine id 103:
 // 256-VGPR budget, own v2c in VGPRs, compile-time D3K); QLDPC_F64W=0 disables.
-bool use_f64w(int engine, int precision, int dmax, int tb, int vpl, int ea_shift, int nch) {
+bool use_f64w(const Route& r) {
   // column degree 5 (kern_r_f64_d5.hip): VPL 4-5 only
   // (column degree 5 also with rows of 9-10 = 5 chunks: the lifted-product [h | I] graphs, round 6)
-  return engine == 3 && precision == 64 && (dmax == 4 || (dmax == 5 && (vpl <= 5 || (vpl == 6 && nch == 5)))) &&
-         ea_shift == 0 && tb <= 256 && vpl >= 4 && vpl <= 8 && (nch == 3 || nch == 4 || (dmax == 5 && nch == 5)) &&
+  return r.engine == 3 && r.precision == 64 &&
+         (r.DMAX == 4 || (r.DMAX == 5 && (r.VPL <= 5 || (r.VPL == 6 && r.nch == 5)))) && r.ea_shift == 0 && r.TB <= 256 &&
+         r.VPL >= 4 && r.VPL <= 8 && (r.nch == 3 || r.nch == 4 || (r.DMAX == 5 && r.nch == 5)) &&
          env_int("QLDPC_F64W", 1) != 0;
 }
 
 // fp32 engine-3 kernels with the compile-time 2-chunk check phase (rows of <= 8 edges);
 // QLDPC_F32W=0 falls back to the runtime-width check loop.
-bool use_f32w(int engine, int precision, int dmax, int tb, int vpl, int ea_shift, int nch) {
-  (void)tb;
-  return engine == 3 && precision == 32 && dmax == 4 && ea_shift == 0 && vpl >= 5 && vpl <= 8 && nch == 2 &&
+bool use_f32w(const Route& r) {
+  return r.engine == 3 && r.precision == 32 && r.DMAX == 4 && r.ea_shift == 0 && r.VPL >= 5 && r.VPL <= 8 && r.nch == 2 &&
          env_int("QLDPC_F32W", 1) != 0;
 }
 
@@ -96,50 +96,59 @@ unsigned long long* debug_stamps_buffer() {
 #endif
 
 // fp64 engine-3 kernels for 257-512-thread workgroups (engine id 303, VPL 3-4); opt-in QLDPC_F64X=1
-bool use_f64x(int engine, int precision, int dmax, int tb, int vpl, int ea_shift) {
-  return engine == 3 && precision == 64 && dmax == 4 && ea_shift == 0 && tb > 256 && tb <= 512 && vpl >= 3 &&
-         vpl <= 4 && QLDPC_EXPERIMENTAL && env_int("QLDPC_F64X", 0) != 0;
+bool use_f64x(const Route& r) {
+  return r.engine == 3 && r.precision == 64 && r.DMAX == 4 && r.ea_shift == 0 && r.TB > 256 && r.TB <= 512 && r.VPL >= 3 &&
+         r.VPL <= 4 && QLDPC_EXPERIMENTAL && env_int("QLDPC_F64X", 0) != 0;
 }
 
 // Slot-family kernels of an engine (2, 3 or 4).
-SVariant slot_variant(int engine, int precision, int dmax, int ns, int vpl, int d3k, int ea_shift = 0, int tb = 1024,
-                      int nch = 0, int tail = 0, int m2s = 0, int fb = 0, int d2k = 0, int pk = 0) {
+SVariant slot_variant(const Route& r) {
+  const SVariant none{nullptr, nullptr, nullptr, nullptr};
+  const bool e3 = r.engine == 3, f64 = r.precision == 64;
   // fp32 space-time family with byte F words (rows of 2 chunks + a tail slot, 512 threads, 2 per CU)
-  if (fb) {
-    const bool ok = engine == 3 && precision == 32 && dmax == 4 && ea_shift == 2 && nch == 2 && tail && tb == 512;
-    return ok ? get_rvariant_f32_stfb(vpl, d3k, d2k) : SVariant{nullptr, nullptr, nullptr, nullptr};
+  if (r.fb) {
+    const bool ok = e3 && !f64 && r.DMAX == 4 && r.ea_shift == 2 && r.nch == 2 && r.tail && r.TB == 512;
+    return ok ? get_rvariant_f32_stfb(r.VPL, r.d3k, r.d2k) : none;
   }
   // fp64 m2-in-slot family (rows of 3 chunks + a tail slot, <= 256 threads, 3 workgroups per CU)
-  if (m2s) {
+  if (r.m2s) {
     // the fp64 space-time graphs: rows of 4 chunks + a tail slot, dword-scaled addresses, 1024
     // threads (engine id 111313, round 6)
-    if (m2s == 1 && engine == 3 && precision == 64 && dmax == 4 && ea_shift == 2 && nch == 4 && tail && tb >= 512)
-      return get_rvariant_f64_m2st(vpl, d3k, d2k);
+    if (r.m2s == 1 && e3 && f64 && r.DMAX == 4 && r.ea_shift == 2 && r.nch == 4 && r.tail && r.TB >= 512)
+      return get_rvariant_f64_m2st(r.VPL, r.d3k, r.d2k);
     // rows of 8 (4 chunks, no tail array), column degree 5, 256 threads (128 / 192 for small graphs): engine id 10103
-    if (m2s == 1 && engine == 3 && precision == 64 && dmax == 5 && ea_shift == 0 && nch == 4 && !tail && tb <= 256)
-      return pk ? get_rvariant_f64_m2s8pk(vpl, d3k) : get_rvariant_f64_m2s8(vpl, d3k);
-    const bool ok = engine == 3 && precision == 64 && dmax == 4 && ea_shift == 0 && nch == 3 && tail && tb <= 256;
-    if (m2s == 3)  // variable-major V slots: no tail array, 256 threads
-      return (engine == 3 && precision == 64 && dmax == 4 && ea_shift == 0 && tb == 256) ? get_rvariant_f64_m2v(vpl, d3k)
-                                                                                          : SVariant{nullptr, nullptr, nullptr, nullptr};
-    if (!ok) return SVariant{nullptr, nullptr, nullptr, nullptr};
-    return m2s == 2 ? get_rvariant_f64_c2s(vpl, d3k) : get_rvariant_f64_m2s(vpl, d3k);
+    if (r.m2s == 1 && e3 && f64 && r.DMAX == 5 && r.ea_shift == 0 && r.nch == 4 && !r.tail && r.TB <= 256)
+      return r.m2s_pk ? get_rvariant_f64_m2s8pk(r.VPL, r.d3k) : get_rvariant_f64_m2s8(r.VPL, r.d3k);
+    const bool ok = e3 && f64 && r.DMAX == 4 && r.ea_shift == 0 && r.nch == 3 && r.tail && r.TB <= 256;
+    if (r.m2s == 3)  // variable-major V slots: no tail array, 256 threads
+      return (e3 && f64 && r.DMAX == 4 && r.ea_shift == 0 && r.TB == 256) ? get_rvariant_f64_m2v(r.VPL, r.d3k) : none;
+    if (!ok) return none;
+    return r.m2s == 2 ? get_rvariant_f64_c2s(r.VPL, r.d3k) : get_rvariant_f64_m2s(r.VPL, r.d3k);
   }
   // fp64 tail layout (rows of 4 chunks + a tail slot, dword-scaled addresses, 1024 threads)
-  if (tail) {
-    const bool ok = engine == 3 && dmax == 4 && ea_shift == 2 && nch == (precision == 64 ? 4 : 2) &&
-                    (tb > 512 || (precision == 64 && tb == 512));
-    if (!ok) return SVariant{nullptr, nullptr, nullptr, nullptr};
-    return precision == 64 ? get_rvariant_f64_st(vpl, d3k, d2k) : get_rvariant_f32_st(vpl, d3k);
+  if (r.tail) {
+    const bool ok = e3 && r.DMAX == 4 && r.ea_shift == 2 && r.nch == (f64 ? 4 : 2) && (r.TB > 512 || (f64 && r.TB == 512));
+    if (!ok) return none;
+    return f64 ? get_rvariant_f64_st(r.VPL, r.d3k, r.d2k) : get_rvariant_f32_st(r.VPL, r.d3k);
   }
-  if (use_f64w(engine, precision, dmax, tb, vpl, ea_shift, nch))
-    return dmax == 5 ? get_rvariant_f64_w_d5(vpl, d3k, nch) : get_rvariant_f64_w(vpl, d3k, nch);
-  if (use_f64x(engine, precision, dmax, tb, vpl, ea_shift)) return get_rvariant_f64_x(vpl, d3k);
-  if (use_f32w(engine, precision, dmax, tb, vpl, ea_shift, nch)) return get_rvariant_f32_w(vpl, d3k);
-  if (engine == 4 && precision == 64 && tb <= 256 && vpl >= 4) return get_r4variant_f64_w(vpl);
-  if (engine == 3 && ea_shift == 2)
-    return (precision == 32 && dmax == 4) ? get_rvariant_f32_big(vpl, d3k) : SVariant{nullptr, nullptr, nullptr, nullptr};
-  return engine >= 3 ? get_rvariant(engine, precision, vpl, d3k, dmax) : get_svariant(precision, dmax, ns);
+  if (use_f64w(r)) return r.DMAX == 5 ? get_rvariant_f64_w_d5(r.VPL, r.d3k, r.nch) : get_rvariant_f64_w(r.VPL, r.d3k, r.nch);
+  if (use_f64x(r)) return get_rvariant_f64_x(r.VPL, r.d3k);
+  if (use_f32w(r)) return get_rvariant_f32_w(r.VPL, r.d3k);
+  if (r.engine == 4 && f64 && r.TB <= 256 && r.VPL >= 4) return get_r4variant_f64_w(r.VPL);
+  if (e3 && r.ea_shift == 2) return (!f64 && r.DMAX == 4) ? get_rvariant_f32_big(r.VPL, r.d3k) : none;
+  return r.engine >= 3 ? get_rvariant(r.engine, r.precision, r.VPL, r.d3k, r.DMAX) : get_svariant(r.precision, r.DMAX, r.NS);
+}
+
+// The id the handles report for that kernel (qldpc_bp_kernel_id): the engine, or the engine-3 family
+// in slot_variant's order.
+int route_kernel_id(const Route& r) {
+  if (r.engine != 3) return r.engine;
+  if (r.m2s)
+    return r.m2s == 2 ? 31103 : r.m2s == 3 ? 40103 : (r.tail && r.nch == 4) ? 11313 + 100000 * std::min(r.d2k, 1)
+           : r.tail ? 11103 : r.m2s_pk ? 10203 : 10103;
+  if (r.fb) return 21013 + ((r.d3k >= 8 && r.d2k > 0) ? 100000 * std::min(r.d2k, 4) : 0);  // + D2K digit
+  if (r.tail) return 1013 + ((r.precision == 64 && r.VPL == 6 && r.d2k >= 1 && r.d3k >= 1) ? 100000 : 0);
+  return use_f64w(r) ? 103 : use_f64x(r) ? 303 : r.ea_shift == 2 ? 13 : 3;
 }
 
 int round_up(int x, int a) { return (x + a - 1) / a * a; }
@@ -237,12 +246,19 @@ int choose_rgeometry(int n, int m, int requested_vpl, int& TB, int& VPL, int pre
   return 0;
 }
 
-// Engines 3 and 4 address their image with 16-bit byte offsets.
+// The engine-3/4 LDS image of a route over `vslots` V slots and `mmax` checks (the graph's own, or
+// the larger of two sectors'), and a workgroup's LDS bytes with it.
+RLayout route_layout(const Route& r, int vslots, int mmax) {
+  return r_layout(r.engine, vslots, mmax, r.precision == 32 ? 4 : 8, r.tail, r.m2s, r.fb);
+}
+size_t route_lds(const Route& r, int vslots, int mmax) {
+  return r_lds_bytes((int)route_layout(r, vslots, mmax).total, kChunkMax);
+}
+
 // Engines 3 and 4 address their image with 16-bit byte offsets; engine 3 with
 // dword-scaled offsets (kernel id 13, ea_shift 2) reaches 256 KiB.
-bool r_fits(int eng, int vslots, int mmax, int tsize, int ea_shift = 0, int tail = 0, int m2s = 0, int fb = 0) {
-  const RLayout L = r_layout(eng, vslots, mmax, tsize, tail, m2s, fb);
-  return L.lred <= (65536u << ea_shift) && r_lds_bytes((int)L.total, kChunkMax) <= (size_t)kLdsMax;
+bool route_fits(const Route& r, int vslots, int mmax) {
+  return route_layout(r, vslots, mmax).lred <= (65536u << r.ea_shift) && route_lds(r, vslots, mmax) <= (size_t)kLdsMax;
 }
 
 // Slots per workgroup: QLDPC_NS, else 1 (independent workgroups interleave
@@ -343,11 +359,11 @@ int qldpc_graph_info(const qldpc_graph* g, int32_t* m, int32_t* n, int32_t* nnz,
 }
 
 static int upload_llr(qldpc_bp* bp) {
-  const int TB = bp->TB, VPL = bp->VPL, n = bp->g->n;
-  if (bp->engine == 6) {  // HBM engine: log((1-p)/p) per variable, variable order
+  const int TB = bp->route.TB, VPL = bp->route.VPL, n = bp->g->n;
+  if (bp->route.engine == 6) {  // HBM engine: log((1-p)/p) per variable, variable order
     std::vector<double> l64(n);
     for (int j = 0; j < n; ++j) l64[j] = std::log((1.0 - bp->probs[j]) / bp->probs[j]);  // glibc log, as Cython
-    if (bp->precision == 32) {
+    if (bp->route.precision == 32) {
       std::vector<float> l32(l64.begin(), l64.end());
       QLDPC_HIP(hipMemcpy(bp->llr.p, l32.data(), (size_t)n * 4, hipMemcpyHostToDevice));
     } else {
@@ -355,10 +371,10 @@ static int upload_llr(qldpc_bp* bp) {
     }
     return 0;
   }
-  if (bp->engine == 5) {  // product-sum priors: ratio p / (1 - p), computed in double (oracle ws_priors)
+  if (bp->route.engine == 5) {  // product-sum priors: ratio p / (1 - p), computed in double (oracle ws_priors)
     std::vector<double> r64(n);
     for (int j = 0; j < n; ++j) r64[j] = bp->probs[j] / (1.0 - bp->probs[j]);
-    if (bp->precision == 32) {
+    if (bp->route.precision == 32) {
       std::vector<float> r32(r64.begin(), r64.end());
       QLDPC_HIP(hipMemcpy(bp->llr.p, r32.data(), (size_t)n * 4, hipMemcpyHostToDevice));
     } else {
@@ -373,7 +389,7 @@ static int upload_llr(qldpc_bp* bp) {
       const int j = bp->slot_var.empty() ? (k * TB + t < n ? k * TB + t : -1) : bp->slot_var[(size_t)k * TB + t];
       if (j >= 0) l64[(size_t)k * TB + t] = std::log((1.0 - bp->probs[j]) / bp->probs[j]);  // glibc log, as Cython
     }
-  if (bp->precision == 32) {
+  if (bp->route.precision == 32) {
     std::vector<float> l32(cnt);
     for (size_t i = 0; i < cnt; ++i) l32[i] = (float)l64[i];
     QLDPC_HIP(hipMemcpy(bp->llr.p, l32.data(), cnt * sizeof(float), hipMemcpyHostToDevice));
@@ -381,6 +397,31 @@ static int upload_llr(qldpc_bp* bp) {
     QLDPC_HIP(hipMemcpy(bp->llr.p, l64.data(), cnt * sizeof(double), hipMemcpyHostToDevice));
   }
   return 0;
+}
+
+// Variables in column order, stably sorted by degree class: a variable's class is the number of
+// `bounds` its degree exceeds ({}: the identity, {3}: degree <= 3 first, {2, 3}: <= 2, then 3, then more).
+static std::vector<int32_t> degree_sorted(const qldpc_graph* g, std::initializer_list<int> bounds) {
+  std::vector<int32_t> order;
+  order.reserve(g->n);
+  for (size_t c = 0; c <= bounds.size(); ++c)
+    for (int j = 0; j < g->n; ++j) {
+      size_t cj = 0;
+      for (int b : bounds) cj += (int)g->col_rows[j].size() > b;
+      if (cj == c) order.push_back(j);
+    }
+  return order;
+}
+
+// Leading whole variable slots whose variables (padding aside) all have degree <= d: a kernel's
+// compile-time D3K (d = 3) / D2K (d = 2).
+static int leading_slots(const qldpc_graph* g, const std::vector<int32_t>& slot_var, int TB, int VPL, int d) {
+  for (int k = 0; k < VPL; ++k)
+    for (int t = 0; t < TB; ++t) {
+      const int j = slot_var[(size_t)k * TB + t];
+      if (j >= 0 && (int)g->col_rows[j].size() > d) return k;
+    }
+  return VPL;
 }
 
 // Engine-2/3 edge table: for slot (k, t) holding variable j = slot_var[k*TB+t]
@@ -421,25 +462,15 @@ struct StPlan {
 };
 static StPlan st_plan(const qldpc_graph* g, int tb, int vpl, int DM, bool narrow, bool balance) {
   StPlan P;
-  auto cls = [&](int d) { return narrow ? std::min(std::max(d, 1), 4) - 1 : (d <= 2 ? 0 : d <= 3 ? 1 : 2); };
-  std::vector<int32_t> order;
-  order.reserve(g->n);
-  for (int c = 0; c < (narrow ? 4 : 3); ++c)
-    for (int j = 0; j < g->n; ++j)
-      if (cls((int)g->col_rows[j].size()) == c) order.push_back(j);
+  const std::vector<int32_t> order = narrow ? degree_sorted(g, {1, 2, 3}) : degree_sorted(g, {2, 3});
+  std::vector<int32_t> logical((size_t)vpl * tb, -1);  // variable of every logical position
   std::vector<int> deg((size_t)vpl * tb, -1);
-  for (int p = 0; p < g->n && p < vpl * tb; ++p) deg[p] = (int)g->col_rows[order[p]].size();
-  auto whole = [&](int lim) {  // leading variable slots whose variables all have degree <= lim
-    int kk = 0;
-    for (; kk < vpl; ++kk) {
-      bool ok = true;
-      for (int t = 0; t < tb && ok; ++t) ok = deg[(size_t)kk * tb + t] <= lim;
-      if (!ok) break;
-    }
-    return kk;
-  };
-  P.d2 = whole(2);
-  P.d3 = whole(3);
+  for (int p = 0; p < g->n && p < vpl * tb; ++p) {
+    logical[p] = order[p];
+    deg[p] = (int)g->col_rows[order[p]].size();
+  }
+  P.d2 = leading_slots(g, logical, tb, vpl, 2);
+  P.d3 = leading_slots(g, logical, tb, vpl, 3);
   const int nwv = (tb + 63) / 64;
   std::vector<int> W(vpl, 0), units(nwv, 0);
   for (int k = 0; k < vpl; ++k) {
@@ -491,11 +522,13 @@ static StPlan st_plan(const qldpc_graph* g, int tb, int vpl, int DM, bool narrow
   return P;
 }
 
-static void build_slot_edges(const qldpc_graph* g, int TB, int VPL, int DM, int tsize, int nch,
-                             const std::vector<int32_t>& slot_var, std::vector<uint32_t>& out, int vbase_dw = -1,
-                             const std::vector<int>& lab = {}, int tail = 0, int m2s = 0, int d3k = 0,
-                             int dummy0 = -1, int* ndummy = nullptr, int anneal = 0, int anneal_iters = -1,
-                             int tail_base = -1, int d2k = 0, uint32_t nw = 0) {
+// `m2s`: place for the families whose variable phase also reads each edge's V slot (r.m2s == 1).
+static void build_slot_edges(const qldpc_graph* g, const Route& r, const std::vector<int32_t>& slot_var,
+                             std::vector<uint32_t>& out, int vbase_dw, const std::vector<int>& lab, int m2s, int dummy0,
+                             int* ndummy, int anneal, int anneal_iters = -1, int tail_base = -1) {
+  const int TB = r.TB, VPL = r.VPL, DM = r.DMAX, tsize = r.precision == 32 ? 4 : 8, nch = r.nch, tail = r.tail;
+  const int d3k = r.d3k, d2k = r.d2k;
+  const uint32_t nw = r.nw;
   const int nv = 16 / tsize;  // messages per 16-byte chunk
   const int rw = nch * nv;
   const int rwt = rw + (tail ? 1 : 0);  // tail layouts: logical slot rw = the row's tail slot
@@ -739,8 +772,9 @@ static void build_slot_edges(const qldpc_graph* g, int TB, int VPL, int DM, int 
 // lanes, bank pair (a / 8) mod 16.  Identical addresses broadcast.  A group costs max over its
 // banks of the distinct addresses there (1 = conflict-free).  Compared against SQ_LDS_BANK_CONFLICT
 // / SQ_LDS_IDX_ACTIVE (tools/lds_model.py).
-static void lds_model_var_phase(const std::vector<uint32_t>& edges, int TB, int VPL, int DM, int d3k, uint32_t vbase,
-                                bool m2s, int64_t* out) {
+static void lds_model_var_phase(const std::vector<uint32_t>& edges, const Route& r, uint32_t vbase, int64_t* out) {
+  const int TB = r.TB, VPL = r.VPL, DM = r.DMAX, d3k = r.d3k;
+  const bool m2s = r.m2s == 1;
   static const int kB128[4][16] = {{0, 1, 2, 3, 12, 13, 14, 15, 20, 21, 22, 23, 24, 25, 26, 27},
                                    {4, 5, 6, 7, 8, 9, 10, 11, 16, 17, 18, 19, 28, 29, 30, 31},
                                    {32, 33, 34, 35, 44, 45, 46, 47, 52, 53, 54, 55, 56, 57, 58, 59},
@@ -830,9 +864,9 @@ static void lds_model_var_phase(const std::vector<uint32_t>& edges, int TB, int 
 // a row of 8 slots covers half of the 16 bank pairs), so build_slot_edges's
 // in-row placement can make the stores conflict free too.  Pure host work, done
 // once per decoder; the arithmetic is untouched (labels only move storage).
-static std::vector<int> label_checks(const qldpc_graph* g, const std::vector<int32_t>& slot_var, int TB, int VPL,
-                                     int DM, int tsize, int* cost_before = nullptr, int* cost_after = nullptr,
-                                     int m2s = 0) {
+static std::vector<int> label_checks(const qldpc_graph* g, const Route& r, const std::vector<int32_t>& slot_var,
+                                     int* cost_before, int* cost_after) {
+  const int TB = r.TB, VPL = r.VPL, DM = r.DMAX, tsize = r.precision == 32 ? 4 : 8, m2s = r.m2s;
   const int m = g->m;
   std::vector<int> lab(m);
   for (int i = 0; i < m; ++i) lab[i] = i;
@@ -967,13 +1001,13 @@ static int create_ps(qldpc_graph* g, const double* channel_probs, int32_t max_it
                      qldpc_bp** out) {
   auto* bp = new qldpc_bp();
   bp->g = g;
-  bp->engine = 5;
+  bp->route.engine = 5;
   bp->method = QLDPC_PRODUCT_SUM;
-  bp->precision = precision;
+  bp->route.precision = precision;
   bp->max_iter = max_iter > 0 ? max_iter : g->n;
   bp->alpha = 0;
-  bp->TB = 256;
-  bp->VPL = (g->n + 255) / 256;
+  bp->route.TB = 256;
+  bp->route.VPL = (g->n + 255) / 256;
   bp->probs.assign(channel_probs, channel_probs + g->n);
   auto fail = [&](int code) {
     for (DevBuf* d : {&bp->llr, &bp->ps_rp, &bp->ps_ci, &bp->ps_cp, &bp->ps_ce, &bp->ps_ws}) d->release();
@@ -1004,10 +1038,10 @@ static int create_ps(qldpc_graph* g, const double* channel_probs, int32_t max_it
   if ((rc = upload_llr(bp))) return fail(rc);
   // messages in LDS when 2E values fit in 96 KiB (>= 1 workgroup per CU with room), else in HBM
   const bool lds_msgs = ps_lds_bytes(precision, g->m, g->n, E, true) <= 96 * 1024;
-  bp->lds_bytes = (int)ps_lds_bytes(precision, g->m, g->n, E, lds_msgs);
-  if (bp->lds_bytes > kLdsMax) return fail(set_err(QLDPC_ENOTSUP, "graph too large for the product-sum engine"));
+  bp->route.lds_bytes = (int)ps_lds_bytes(precision, g->m, g->n, E, lds_msgs);
+  if (bp->route.lds_bytes > kLdsMax) return fail(set_err(QLDPC_ENOTSUP, "graph too large for the product-sum engine"));
   int nb = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, ps_kernel(precision), bp->TB, bp->lds_bytes) != hipSuccess)
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, ps_kernel(precision), bp->route.TB, bp->route.lds_bytes) != hipSuccess)
     nb = 1;
   bp->blocks_per_cu = std::max(1, nb);
   if ((rc = device_cus(g->device, bp->cus))) return fail(rc);
@@ -1033,7 +1067,7 @@ static void bp1_prepare(qldpc_bp* bp) {
   bp->bp1_off = !(bp->max_iter == 1 && bp->method == 1) || env_int("QLDPC_BP1", 1) == 0;
   if (bp->bp1_off) return;
   const std::string keep = qldpc_rt::g_err;  // an ENOTSUP here is not the caller's error
-  if (qldpc_firstmin_create(bp->g, bp->probs.data(), 0, bp->alpha, bp->precision, &bp->bp1) != 0) {
+  if (qldpc_firstmin_create(bp->g, bp->probs.data(), 0, bp->alpha, bp->route.precision, &bp->bp1) != 0) {
     bp->bp1 = nullptr;
     bp->bp1_off = true;
     qldpc_rt::g_err = keep;
@@ -1060,77 +1094,478 @@ int qldpc_bp_create_soft(qldpc_graph* g, const double* channel_probs, int32_t ma
   return create_min_sum(g, channel_probs, max_iter, QLDPC_MIN_SUM, ms_scaling_factor, precision, 0, 0, 1, out);
 }
 
-static int create_min_sum(qldpc_graph* g, const double* channel_probs, int32_t max_iter, int32_t bp_method,
-                          double ms_scaling_factor, int32_t precision, int32_t vars_per_thread,
-                          int32_t min_col_slots, int forced_engine, qldpc_bp** out) {
-  if (!g || !channel_probs || !out) return set_err(QLDPC_EINVAL, "NULL argument");
+// ------------------------------------------------------------- route plan
+// Host only: no hip* call, no device buffer (qldpc_bp_plan runs it on a machine without a GPU).
+
+static bool uniform_priors(const double* probs, int n) {
+  for (int j = 1; j < n; ++j)
+    if (probs[j] != probs[0]) return false;
+  return true;
+}
+
+static int validate_create(const qldpc_graph* g, const double* channel_probs, int precision, int bp_method) {
+  if (!g || !channel_probs) return set_err(QLDPC_EINVAL, "NULL argument");
   if (precision != 32 && precision != 64) return set_err(QLDPC_EINVAL, "precision must be 32 or 64");
   if (bp_method != QLDPC_MIN_SUM && bp_method != QLDPC_PRODUCT_SUM)
     return set_err(QLDPC_EINVAL, "bp_method must be 0 (product_sum) or 1 (minimum_sum)");
-  QLDPC_HIP(hipSetDevice(g->device));
-  if (bp_method == QLDPC_PRODUCT_SUM) return create_ps(g, channel_probs, max_iter, precision, out);
+  return 0;
+}
+
+static bool fits(const Route& c, const qldpc_graph* g) { return route_fits(c, route_vslots(c, g->m), g->m); }
+
+// engine 6: messages in HBM, one decode per lane (bp_hbm.hip) -- requested, or when no LDS engine
+// serves the graph (`why`; QLDPC_HBM_FALLBACK=0 makes that an error instead)
+static int to_hbm(Route& r, std::vector<int32_t>& slot_var, const char* why = nullptr) {
+  if (why && env_int("QLDPC_HBM_FALLBACK", 1) == 0) return set_err(QLDPC_ENOTSUP, why);
+  r.engine = 6;
+  r.TB = kHbmThreads;
+  r.VPL = 1;
+  r.lds_bytes = 0;
+  r.ea_shift = r.tail = r.m2s = r.fb = r.m2s_pk = r.vslots_dummy = r.d3k = r.d2k = 0;
+  r.nw = r.live_last = 0;
+  slot_var.clear();
+  return 0;
+}
+
+// rows one message wider than whole chunks (space-time graphs: rows of 9 = 4 fp64 / 2 fp32
+// chunks + 1): chunk rows + a tail slot per row, dword-scaled addresses, 1024-thread
+// workgroups.  fp64: the image fits LDS at all (162.7 KB instead of 176 KB); fp32: the check
+// phase reads 36 instead of 48 bytes per row through the compile-time-width loop.  fp64 images
+// past the 16-bit layout's 64 KiB take it too (round 6: e.g. hgp_34_n1600 over two rounds, 1536 x
+// 4736, 117 KB, which ran on engine 2 before: fp64 engine 3 has no dword-scaled plain layout), and
+// so do fp64 rows of 8 (the tail slot stays empty: GenBicycleA3 / A4 over 2-5 rounds) and graphs
+// whose geometry is 512 threads (hgp_34_n625 over three rounds, 900 x 2775: two decodes per CU)
+static void admit_tail(const qldpc_graph* g, int vars_per_thread, Route& r) {
+  const bool f64t = r.precision == 64 && env_int("QLDPC_E3_TAIL64", 1) != 0;
+  Route plain = r;
+  plain.ea_shift = f64t ? 0 : 2;
+  if (!(r.engine == 3 && r.DMAX == 4 && (g->max_row == 9 || (f64t && g->max_row == 8)) && env_int("QLDPC_E3_TAIL", 1) != 0 &&
+        (r.precision == 32 || !fits(plain, g))))
+    return;
+  Route c = r;
+  c.tail = 1;
+  c.nch = r.precision == 32 ? 2 : 4;  // 8 messages
+  c.ea_shift = 2;
+  // fp32: byte F words shrink the image below half a CU (config 5: 85.1 -> 79.6 KB), so two
+  // 512-thread decodes share a CU (bp_reg.h eng_fb; QLDPC_E3_FB=0 keeps one 1024-thread decode)
+  Route fb = c;
+  fb.fb = 1;
+  fb.TB = 512;
+  fb.VPL = (g->n + 511) / 512;
+  int tb = 0, vpl = 0;
+  if (r.precision == 32 && vars_per_thread <= 0 && env_int("QLDPC_TB", 0) <= 0 && env_int("QLDPC_E3_FB", 1) != 0 &&
+      fb.VPL >= 9 && fb.VPL <= 12 && (g->m + 511) / 512 <= 32 && fits(fb, g) &&
+      2 * route_lds(fb, route_vslots(fb, g->m), g->m) <= (size_t)kLdsMax)
+    r = fb;
+  else if (fits(c, g) && !choose_rgeometry(g->n, g->m, vars_per_thread, tb, vpl) && (tb > 512 || (f64t && tb == 512)) &&
+           vpl >= 4 && vpl <= 8)
+    r = c;
+}
+
+// fp64 "m2 in slot" family (bp_reg.h eng_m2s, kern_r_f64_m2s.hip): one-word check state, m2 in
+// the argmin edge's V slot, rows of up to 7 edges as 3 chunks + a tail slot, <= 256 threads.
+// The headline hgp_34_n1600 image drops from 65.0 KB to 52.3 KB: 3 workgroups per CU instead
+// of 2.  The kernel keeps no dummy edges for real variables, so every column degree must be
+// 3 or 4 with the degree-3 variables filling whole variable slots (host degree sort).
+// (`uniform`: QLDPC_M2S_UNIL kernels hold one prior for every variable)
+static void admit_m2s(const qldpc_graph* g, bool uniform, int vars_per_thread, Route& r) {
+  if (!(r.engine == 3 && r.precision == 64 && r.DMAX == 4 && !r.tail && g->max_row >= 1 && g->max_row <= 7 &&
+        env_int("QLDPC_M2S", 1) != 0 && env_int("QLDPC_DEGSORT", 1) != 0))
+    return;
+  int tb = 0, vpl = 0, n3 = 0, nother = 0;
+  for (int j = 0; j < g->n; ++j) {
+    const int d = (int)g->col_rows[j].size();
+    n3 += d == 3;
+    nother += d != 3 && d != 4;
+  }
+  Route c = r;
+  c.tail = 1;
+  c.m2s = 1;
+  c.nch = 3;
+  c.ea_shift = 0;
+  if (nother || !uniform || choose_rgeometry(g->n, g->m, vars_per_thread, tb, vpl) || tb > 256 || vpl < 4 || vpl > 8 ||
+      !(n3 % tb == 0 || n3 == g->n) || !fits(c, g))
+    return;
+  r = c;
+  // "c2v in slot" (bp_reg.h eng_c2s, kern_r_f64_c2s.hip, opt-in QLDPC_C2S=1): the check phase
+  // writes the c2v of every edge into the row's slots, so no row may have a padding slot:
+  // every row exactly 7 edges (the headline HGP graphs).  No CS array (n1600 52.3 -> 46.2 KB)
+  // and 25 % fewer VALU, but its check phase stores 7 words per row where m2s stores 2, and
+  // LDS stores cost 3x the cycles of reads per byte: 1.141 M vs 1.189 M shots/s
+  // (profiles/r03/c2s/), so m2s stays the default
+  bool full = true;
+  for (int i = 0; i < g->m && full; ++i) full = g->row_ptr[i + 1] - g->row_ptr[i] == 7;
+  c.m2s = 2;
+  if (full && QLDPC_EXPERIMENTAL && env_int("QLDPC_C2S", 0) != 0 && fits(c, g)) r.m2s = 2;
+  // variable-major V slots (bp_reg.h eng_m2v, kern_r_f64_m2v.hip): edge (k, d) of lane t at
+  // slot (ecnt(k) + d) * 256 + t, the last variable slot at ecnt * 256 + d * NL + t, then one
+  // sentinel slot; the check phase's rows come from a register table (m <= 4 * 256)
+  const int d3 = n3 == g->n ? vpl : n3 / 256;
+  const int nlast = g->n - (vpl - 1) * 256, NL = (nlast + 63) & ~63;
+  const int ecl = 3 * std::min(vpl - 1, d3) + 4 * std::max(0, vpl - 1 - d3);
+  Route v = r;
+  v.m2s = 3;
+  v.tail = 0;
+  v.vslots_m2v = ecl * 256 + (vpl - 1 < d3 ? 3 : 4) * NL + 1;
+  v.m2v_vlast = ecl * 256;
+  v.m2v_nl = NL;
+  if (r.m2s == 1 && tb == 256 && g->m <= 4 * 256 && v.vslots_m2v * 8 < 65536 && QLDPC_EXPERIMENTAL &&
+      env_int("QLDPC_M2V", 0) != 0 && fits(v, g))
+    r = v;
+}
+
+// fp64 space-time graphs on the tail layout (rows of 8 / 9 as 4 chunks + a tail slot, 1024 threads,
+// one decode per CU): the one-word check state too (round 6, kern_r_f64_m2st.hip, engine id
+// 111313).  The two-word tail family re-reads each edge's own previous v2c from LDS (its 128-VGPR
+// budget had no room for it) and gathers 16-byte check states: 24 B of variable-phase reads per
+// edge.  Here the own v2c lives in VGPRs (118 with the uniform prior in SGPRs, no scratch) and an
+// edge reads the 8-byte CS and its own slot: 16 B.  Real variables never touch a shared dummy:
+// the measurement variables in 3-edge slots and the degree-3 ones in 4-edge slots get private
+// dummy V slots (config 5: 1,348, 10.8 KB), placed before the tail array.  Uniform priors only.
+// Known, out of scope here: admitted for d2 >= 1 against a kernel compiled for D2K = 1.
+static void admit_m2st(const qldpc_graph* g, bool uniform, int vars_per_thread, Route& r) {
+  if (!(r.engine == 3 && r.precision == 64 && r.DMAX == 4 && r.tail && !r.fb && !r.m2s && r.nch == 4 &&
+        env_int("QLDPC_M2ST", 1) != 0 && env_int("QLDPC_DEGSORT", 1) != 0 && env_int("QLDPC_D2K", 1) != 0))
+    return;
+  int tb = 0, vpl = 0;
+  if (!uniform || choose_rgeometry(g->n, g->m, vars_per_thread, tb, vpl) || tb < 512) return;
+  // the slot map plan_route makes below (st_plan), its D2K / D3K and the private dummies of
+  // build_slot_edges
+  const StPlan P = st_plan(g, tb, vpl, r.DMAX, env_int("QLDPC_NW", 1) != 0, env_int("QLDPC_NW_BAL", 1) != 0);
+  Route c = r;
+  c.m2s = 1;
+  c.vslots_dummy = P.nd;
+  c.nw = P.nw;
+  c.live_last = P.live_last;
+#if QLDPC_DIAG_NOLAST
+  // diagnostic builds only (results invalid): no wave runs the last variable slot, to time the
+  // cost of the waves that hold it
+  c.live_last = 0;
+#endif
+  if (g->max_col <= r.DMAX && P.d2 >= 1 && route_vslots(c, g->m) < 0x3FFFF && get_rvariant_f64_m2st(vpl, P.d3, P.d2).dec_k &&
+      fits(c, g))
+    r = c;
+}
+
+// fp64 column degree 5 graphs that come out at 512 threads x <= 3 variables (LP_Matg8_L21 / L30's
+// [h | I], 315 x 1029 / 450 x 1470): the two-word degree-5 family at 256 threads x 5 / 6 variables
+// instead of engine 2 (round 6; QLDPC_D5_256=0 keeps the old geometry).  Admits by choosing
+// vars_per_thread for the geometry call of plan_route.
+static void admit_d5_256(const qldpc_graph* g, const Route& r, int pref, int& vars_per_thread, int& vmax) {
+  if (!(r.engine == 3 && r.precision == 64 && r.DMAX == 5 && vars_per_thread <= 0 && env_int("QLDPC_TB", 0) <= 0 &&
+        env_int("QLDPC_D5_256", 1) != 0 && g->max_row > 8 && g->max_row <= 10))
+    return;
+  int tb = 0, vpl = 0;
+  if (choose_rgeometry(g->n, g->m, 0, tb, vpl, pref, vmax) || tb <= 256) return;
+  for (int v = 5; v <= 6 && vars_per_thread <= 0; ++v) {
+    int tb5 = 0, vpl5 = 0;
+    if (!choose_rgeometry(g->n, g->m, v, tb5, vpl5, pref, 6) && tb5 <= 256) {
+      vars_per_thread = v;
+      vmax = std::max(vmax, v);
+    }
+  }
+}
+
+// the m2s family for rows of 8 and column degree 5 (kern_r_f64_m2s8.hip, engine id 10103): the
+// lifted-product codes (LP_Matg8_L30: 750 degree-3 and 270 degree-5 columns, rows of 8).  Rows of
+// 4 chunks, no tail array.  Slots k >= D3K hold 5 edge slots; a real variable with fewer edges
+// there (a degree-3 variable in the slot shared with the degree-5 class) gets a PRIVATE dummy V
+// slot per missing edge, past the rows, and the dummy CS entry 0 (+0, parity 0): no other lane
+// writes that slot, so the variable phase always reads its own previous v2c back and takes
+// c2v = +-0, which leaves every sum bit-exact (w-domain sums are never -0).  The two-word family
+// runs these graphs at 2 workgroups per CU (256 VGPRs); the one-word state fits 3.
+static void admit_m2s8(const qldpc_graph* g, bool uniform, int pref, int vmax, int& vars_per_thread, Route& r) {
+  if (!(r.engine == 3 && r.precision == 64 && r.DMAX == 5 && !r.tail && !r.m2s && g->max_row >= 1 && g->max_row <= 8 &&
+        env_int("QLDPC_M2S", 1) != 0 && env_int("QLDPC_M2S8", 1) != 0 && env_int("QLDPC_DEGSORT", 1) != 0))
+    return;
+  int tb = 0, vpl = 0, n3 = 0, small_vpt = 0;
+  for (int j = 0; j < g->n; ++j) n3 += g->col_rows[j].size() <= 3;
+  if (!uniform || choose_rgeometry(g->n, g->m, vars_per_thread, tb, vpl, pref, vmax)) return;
+  // smaller graphs (LP_Matg8_L16 / L21, the Threshold notebook's codes: 544 / 714 columns) come out
+  // at 256 threads x 3 variables, below the family's 4-6: run them at the most variables per thread
+  // (<= 5 for degree 5) whose workgroup is smaller, 128 x 5 / 192 x 5 (round 6; they ran on engine 2
+  // before).  The geometry call of plan_route then takes this VPL.
+  if (tb == 256 && vpl < 4 && vars_per_thread <= 0 && env_int("QLDPC_TB", 0) <= 0 && env_int("QLDPC_M2S8_SMALL", 1) != 0)
+    for (int v = std::min(6, vmax); v >= 4 && !small_vpt; --v) {
+      int tb2 = 0, vpl2 = 0;
+      if (!choose_rgeometry(g->n, g->m, v, tb2, vpl2, pref, vmax) && tb2 < 256 && vpl2 == v) {
+        tb = tb2;
+        vpl = vpl2;
+        small_vpt = v;
+      }
+    }
+  if (!((tb == 256 || (tb < 256 && small_vpt > 0)) && vpl >= 4 && vpl <= 6)) return;
+  // the slot map of plan_route: degree <= 3 first, so slots k < n3 / tb (whole) hold degree <= 3 only
+  const int d3 = n3 == g->n ? vpl : n3 / tb;
+  const std::vector<int32_t> order = degree_sorted(g, {3});
+  Route c = r;
+  c.m2s = 1;
+  c.nch = 4;
+  c.ea_shift = 0;
+  for (int p = 0; p < g->n; ++p) c.vslots_dummy += ((p / tb) < d3 ? 3 : r.DMAX) - (int)g->col_rows[order[p]].size();
+  if (route_vslots(c, g->m) >= 0xFFFF || !fits(c, g)) return;
+  r = c;
+  if (small_vpt > 0) vars_per_thread = small_vpt;
+  // packed absolute addresses, 4 workgroups per CU: LP L30 fp64 4.08 M vs 3.67 M shots/s
+  // (0.622 vs 0.561 of the LDS roofline, profiles/r04/passd/); QLDPC_M2S8_PK=0 keeps 10103
+  r.m2s_pk = env_int("QLDPC_M2S8_PK", 1) != 0 && vpl <= 5 && 4 * route_lds(c, route_vslots(c, g->m), g->m) <= (size_t)kLdsMax;
+}
+
+// The route of a min-sum decoder and its slot map (engines 2-4: the variable of every (k, t) slot,
+// -1 = padding), from the graph, whether the priors are uniform, and the QLDPC_* switches.
+static int plan_route(const qldpc_graph* g, bool uniform, int precision, int vars_per_thread, int min_col_slots,
+                      int forced_engine, Route& r, std::vector<int32_t>& slot_var) {
   const int want_engine = forced_engine ? forced_engine : env_int("QLDPC_ENGINE", 3);
   if (want_engine == 4 && !QLDPC_EXPERIMENTAL)
     return set_err(QLDPC_ENOTSUP, "engine 4 is built only with -DQLDPC_EXPERIMENTAL=1 (tools/build_variant.py)");
-  auto* bp = new qldpc_bp();
-  bp->g = g;
-  bp->engine = ((want_engine >= 1 && want_engine <= 4) || want_engine == 6) ? want_engine : 3;
+  r = Route();
+  slot_var.clear();
+  r.precision = precision;
+  r.engine = ((want_engine >= 1 && want_engine <= 4) || want_engine == 6) ? want_engine : 3;
   // column degree > 8: beyond the LDS engines' edge slots -> engine 6 (row and column degree <= 12); soft BP stays engine 1
-  if ((g->max_col > 8 || min_col_slots > 8) && bp->engine != 6) {
-    if (bp->engine == 1) {
-      delete bp;
-      return set_err(QLDPC_ENOTSUP, "column degree > 8");
-    }
-    bp->engine = 6;
+  if ((g->max_col > 8 || min_col_slots > 8) && r.engine != 6) {
+    if (r.engine == 1) return set_err(QLDPC_ENOTSUP, "column degree > 8");
+    r.engine = 6;
   }
-  bp->max_iter = max_iter > 0 ? max_iter : g->n;
-  bp->method = bp_method;
-  bp->alpha = ms_scaling_factor;
-  bp->precision = precision;
-  const int colmax = std::max(g->max_col, (int)min_col_slots);
-  bp->DMAX = colmax <= 4 ? 4 : 8;
+  const int colmax = std::max(g->max_col, min_col_slots);
+  r.DMAX = colmax <= 4 ? 4 : 8;
   // engine 3 also takes fp32 graphs with column degree 5-6 (lifted-product codes), exact slot count
-  if (bp->engine == 3 && precision == 32 && colmax > 4 && colmax <= 6 && env_int("QLDPC_E3_D56", 1) != 0)
-    bp->DMAX = colmax;
+  if (r.engine == 3 && precision == 32 && colmax > 4 && colmax <= 6 && env_int("QLDPC_E3_D56", 1) != 0) r.DMAX = colmax;
   // fp64: column degree 5 on the <= 256-thread family (checked with the geometry below)
-  if (bp->engine == 3 && precision == 64 && colmax == 5 && env_int("QLDPC_E3_D56", 1) != 0) bp->DMAX = 5;
-  bp->probs.assign(channel_probs, channel_probs + g->n);
-  auto fail = [&](int code) {
-    for (DevBuf* d : {&bp->vchk, &bp->llr, &bp->rdeg, &bp->rowtab, &bp->perm, &bp->rperm, &bp->work, &bp->h_rp, &bp->h_rcol,
-                      &bp->h_rcpos, &bp->h_cp, &bp->h_crpos, &bp->h_ws})
-      d->release();
-    delete bp;
-    return code;
-  };
-  // engine 6: messages in HBM, one decode per lane (bp_hbm.hip) -- requested, or below when the
-  // per-decode LDS image of every LDS engine exceeds the 160 KiB of a CU
-  auto setup_hbm = [&]() {
-    bp->engine = 6;
-    bp->ea_shift = 0;
-    bp->slot_var.clear();
-    int rc6 = hbm_prepare(bp);
-    if (rc6) return fail(rc6);
-    bp->llr.release();
-    if ((rc6 = bp->llr.alloc((size_t)g->n * (precision == 32 ? 4 : 8))) || (rc6 = upload_llr(bp))) return fail(rc6);
-    int nb6 = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb6, hbm_kernel(precision), bp->TB, 0) != hipSuccess) nb6 = 1;
-    bp->blocks_per_cu = std::max(1, nb6);
-    if ((rc6 = device_cus(g->device, bp->cus))) return fail(rc6);
-    bp1_prepare(bp);
-    *out = bp;
-    return 0;
-  };
-  if (bp->engine == 6) return setup_hbm();
+  if (r.engine == 3 && precision == 64 && colmax == 5 && env_int("QLDPC_E3_D56", 1) != 0) r.DMAX = 5;
+  if (r.engine == 6) return to_hbm(r, slot_var);
   const int tsize = precision == 32 ? 4 : 8;
-  int DM = bp->DMAX;
-  std::vector<uint32_t> vchk;
-  const void* kern = nullptr;
-  int rc;
-  if (bp->engine == 1) {
-    rc = choose_geometry(g->n, g->m, vars_per_thread, max_spill_free_vpl(precision, DM), bp->TB, bp->VPL);
-    if (rc) return fail(rc);
-    const int TB = bp->TB, VPL = bp->VPL, D2 = DM / 2;
-    vchk.assign((size_t)VPL * D2 * TB, 0xFFFFFFFFu);
+  if (r.engine == 1) {
+    const int rc = choose_geometry(g->n, g->m, vars_per_thread, max_spill_free_vpl(precision, r.DMAX), r.TB, r.VPL);
+    if (rc) return rc;
+    r.lds_bytes = (int)lds_for(precision, g->m);
+    return get_variant(precision, r.VPL, r.DMAX).dec_k ? 0 : set_err(QLDPC_ENOTSUP, "no kernel variant");
+  }
+  if (r.engine == 4 && g->max_row > 8) r.engine = 3;  // engine 4 rows are 8 slots wide
+  r.nch = r.engine == 4 ? 8 * tsize / 16 : (std::max(1, g->max_row) * tsize + 15) / 16;
+  // no LDS image addresses this many slots: HBM-resident messages (engine 6)
+  if (route_vslots(r, g->m) >= 0xFFFF)
+    return to_hbm(r, slot_var, "V image exceeds 65535 message slots (QLDPC_HBM_FALLBACK=0)");
+  // degree-5/6 variables hold 2.5x the registers of degree-4 ones: fewer per thread
+  const int pref = r.DMAX == 4 ? kPrefVplR : 4;
+  int vmax = r.DMAX == 4 ? kMaxVplR : 5;
+  // images of 64-256 KiB (space-time graphs): engine 3 with dword-scaled addresses (fp32, 4 slots)
+  Route big = r;
+  big.ea_shift = 2;
+  if (r.engine == 3 && precision == 32 && r.DMAX == 4 && !fits(r, g) && fits(big, g) && env_int("QLDPC_E3_BIG", 1) != 0) r = big;
+  admit_tail(g, vars_per_thread, r);
+  admit_m2s(g, uniform, vars_per_thread, r);
+  admit_m2st(g, uniform, vars_per_thread, r);
+  admit_d5_256(g, r, pref, vars_per_thread, vmax);
+  admit_m2s8(g, uniform, pref, vmax, vars_per_thread, r);
+  if (r.engine >= 3 && ((r.DMAX != 4 && !(r.engine == 3 && (r.DMAX == 5 || r.DMAX == 6))) ||
+                        (!r.fb && choose_rgeometry(g->n, g->m, vars_per_thread, r.TB, r.VPL, pref, vmax)) || !fits(r, g) ||
+                        (precision == 64 && r.DMAX == 5 && !r.m2s && !use_f64w(r)))) {
+    r.ea_shift = r.tail = r.m2s = r.vslots_dummy = r.m2s_pk = r.fb = 0;
+    r.engine = 2;  // graph outside the register engines' envelope
+    r.nch = (std::max(1, g->max_row) * tsize + 15) / 16;
+    if (r.DMAX == 5 || r.DMAX == 6) r.DMAX = 8;  // engine 2 kernels come in 4 and 8 slots
+  }
+  const int vslots = route_vslots(r, g->m);
+  if (r.engine >= 3) {
+    r.NS = 1;
+    r.lds_bytes = (int)route_lds(r, vslots, g->m);
+  } else {
+    const int rc = choose_sgeometry(g->n, g->m, vars_per_thread, r.TB, r.VPL);
+    if (rc) return rc;
+    const int img = (int)slot_img_bytes(vslots, g->m, tsize);
+    r.NS = choose_ns(img);
+    r.lds_bytes = (int)slot_lds_bytes(r.NS, img, kChunkMax);
+    // big images leave room for few workgroups per CU: widen the workgroup so
+    // the CU still holds >= 16 waves (ST n1225 fp32: 1 x 1024 threads, 2x the
+    // samples/s of 1 x 256, bench.py --workload phenl)
+    const int bpc = std::max(1, kLdsMax / std::max(1, r.lds_bytes));
+    if (vars_per_thread <= 0 && env_int("QLDPC_TB", 0) <= 0 && bpc * r.TB / 64 < 16) {
+      const int tb = std::min(kMaxThreadsS, round_up((16 + bpc - 1) / bpc * 64, 64));
+      if (tb > r.TB) {
+        r.TB = tb;
+        r.VPL = (g->n + tb - 1) / tb;
+      }
+    }
+  }
+  // no LDS engine holds this decode: HBM-resident messages
+  if (r.lds_bytes > kLdsMax) return to_hbm(r, slot_var, "per-shot LDS image exceeds 160 KiB (QLDPC_HBM_FALLBACK=0)");
+  // slot -> variable map: identity, or (engine 3) degree <= 3 variables first
+  const bool sort3 = r.engine == 3 && r.DMAX >= 4 && env_int("QLDPC_DEGSORT", 1) != 0;
+  // byte-F kernels also keep degree <= 2 variables (the space-time measurement columns) in
+  // compile-time 2-edge slots: those go first
+  const bool sort2 = sort3 && (r.fb || (r.tail && precision == 64 && (!r.m2s || r.nch == 4))) && env_int("QLDPC_D2K", 1) != 0;
+  if (r.engine == 3 && precision == 64 && r.tail && r.m2s == 1 && r.nch == 4) {
+    // (the fp64 space-time m2s family: st_plan's order, degree classes 1 / 2 / 3 / 4 with narrow waves)
+    slot_var = st_plan(g, r.TB, r.VPL, r.DMAX, env_int("QLDPC_NW", 1) != 0, env_int("QLDPC_NW_BAL", 1) != 0).slots;
+  } else {
+    slot_var = sort2 ? degree_sorted(g, {2, 3}) : sort3 ? degree_sorted(g, {3}) : degree_sorted(g, {});
+    slot_var.resize((size_t)r.VPL * r.TB, -1);
+  }
+  r.d3k = sort3 ? leading_slots(g, slot_var, r.TB, r.VPL, 3) : 0;
+  r.d2k = sort2 ? leading_slots(g, slot_var, r.TB, r.VPL, 2) : 0;
+  // fp64 engine-3 kernels are built with D3K = 0 only, except the <= 256-thread family
+  if (precision != 32 && !use_f64w(r) && !use_f64x(r) && !r.tail && !r.m2s) r.d3k = 0;
+  if (slot_variant(r).dec_k) return 0;
+  // no kernel compiled for this engine-3/4 geometry (e.g. fp32 images past 64 KiB at 8 variables per
+  // thread, GenBicycleA4 over five rounds): the HBM-resident engine serves any graph
+  return (r.engine == 3 || r.engine == 4) ? to_hbm(r, slot_var, "no kernel variant") : set_err(QLDPC_ENOTSUP, "no kernel variant");
+}
+
+// ------------------------------------------------------------ host tables
+struct HostTables {
+  std::vector<uint32_t> edges;   // engine 1: packed u16 check ids; engines 2-4: edge words
+  std::vector<int> lab;          // engine 3: label of each check (empty = identity)
+  std::vector<uint8_t> rdeg;     // engines 3/4: row degrees by check label
+  std::vector<uint32_t> rowtab;  // m2v: the check phase's row table
+};
+
+// m2v lane search (opt-in QLDPC_M2V_PERM=1: measured 1.6 % slower): a variable's V slots sit in its
+// lane's bank pair (slot mod 32 = lane mod 32), so which lane a variable occupies inside its slot k
+// sets the banks of the check phase's gathers.  A seeded local search swaps two variables of one
+// slot k (same degree class) whenever that does not raise Σ_{row group of 32, bank} load² (the
+// check gathers; a group whose bank loads are all <= 7 admits conflict-free gather orders) +
+// Σ_{32-lane group, edge, bank} count² of the variable phase's CS gathers (bank pair = (check + 1)
+// mod 32).  Storage only.
+static void m2v_lane_search(const qldpc_graph* g, const Route& r, std::vector<int32_t>& slot_var) {
+  const int TBm = r.TB, VPLm = r.VPL, DM = r.DMAX, M = g->m;
+  const int ng = (M + 31) / 32;
+  std::vector<int> L((size_t)ng * 32, 0);                       // check groups x banks
+  std::vector<int> C((size_t)VPLm * DM * (TBm / 32) * 32, 0);   // CS gather groups x banks
+  auto cidx = [&](int k, int d, int h, int b) { return (((size_t)k * DM + d) * (TBm / 32) + h) * 32 + b; };
+  auto add = [&](int j, int pos, int sg) {
+    const int k = pos / TBm, t = pos % TBm, b = t % 32, h = t / 32;
+    const auto& rows = g->col_rows[j];
+    for (int d = 0; d < (int)rows.size(); ++d) {
+      L[(size_t)(rows[d] / 32) * 32 + b] += sg;
+      C[cidx(k, d, h, (rows[d] + 1) % 32)] += sg;
+    }
+  };
+  auto sq = [&](int j, int pos) {  // Σ of the counts this variable's entries see (for the delta)
+    const int k = pos / TBm, t = pos % TBm, b = t % 32, h = t / 32;
+    long long v = 0;
+    const auto& rows = g->col_rows[j];
+    for (int d = 0; d < (int)rows.size(); ++d) v += 2 * L[(size_t)(rows[d] / 32) * 32 + b] + C[cidx(k, d, h, (rows[d] + 1) % 32)];
+    return v;
+  };
+  for (int pos = 0; pos < VPLm * TBm; ++pos)
+    if (slot_var[pos] >= 0) add(slot_var[pos], pos, +1);
+  uint64_t rs = 0xD1B54A32D192ED03ull;
+  auto rnd = [&]() { rs ^= rs << 13; rs ^= rs >> 7; rs ^= rs << 17; return rs; };
+  const int iters = env_int("QLDPC_M2V_PERM_IT", 400000);
+  for (int it = 0; it < iters; ++it) {
+    const int k = (int)(rnd() % (uint64_t)VPLm);
+    const int pa = k * TBm + (int)(rnd() % (uint64_t)TBm), pb = k * TBm + (int)(rnd() % (uint64_t)TBm);
+    const int ja = slot_var[pa], jb = slot_var[pb];
+    if (ja < 0 || jb < 0 || pa == pb || (pa % 32) == (pb % 32) && (pa / 32) == (pb / 32)) continue;
+    if (g->col_rows[ja].size() != g->col_rows[jb].size()) continue;
+    // cost change: remove both, measure, add swapped, measure (counts are small integers)
+    add(ja, pa, -1);
+    add(jb, pb, -1);
+    const long long before = sq(ja, pa) + sq(jb, pb);
+    const long long after = sq(ja, pb) + sq(jb, pa);
+    if (after <= before) {
+      slot_var[pa] = jb;
+      slot_var[pb] = ja;
+      add(jb, pa, +1);
+      add(ja, pb, +1);
+    } else {
+      add(ja, pa, +1);
+      add(jb, pb, +1);
+    }
+  }
+}
+
+// m2v row table (bp_reg.h M2vRows): row i = q * TB + t -> uint4 (q * TB + t): the byte offsets
+// from the V base of its edges' variable-major slots, two 16-bit offsets per word, the unused
+// entries at the sentinel slot
+static int m2v_row_table(const qldpc_graph* g, const Route& r, const std::vector<int32_t>& slot_var,
+                         std::vector<uint32_t>& tab) {
+  const int TBm = r.TB, VPLm = r.VPL, d3 = std::min(r.d3k, VPLm);
+  auto ecnt = [&](int k) { return 3 * std::min(k, d3) + 4 * std::max(0, k - d3); };
+  if (ecnt(VPLm - 1) * TBm != r.m2v_vlast) return set_err(QLDPC_ENOTSUP, "m2v layout mismatch");
+  const uint32_t sent = (uint32_t)(r.vslots_m2v - 1) * 8u;
+  std::vector<std::vector<uint32_t>> roff(g->m);
+  for (int k = 0; k < VPLm; ++k)
+    for (int t = 0; t < TBm; ++t) {
+      const int j = slot_var[(size_t)k * TBm + t];
+      if (j < 0) continue;
+      const auto& rows = g->col_rows[j];
+      for (int d = 0; d < (int)rows.size(); ++d) {
+        const int vs = k < VPLm - 1 ? (ecnt(k) + d) * TBm + t : r.m2v_vlast + d * r.m2v_nl + t;
+        roff[rows[d]].push_back((uint32_t)vs * 8u);
+      }
+    }
+  for (int i = 0; i < g->m; ++i) {
+    if (roff[i].size() > 7) return set_err(QLDPC_ENOTSUP, "m2v row wider than 7");
+    while (roff[i].size() < 8) roff[i].push_back(sent);
+  }
+  // The check phase gathers entry e of its rows with one ds_read_b64 per e: 32-lane groups,
+  // bank pair = slot mod 32 (MI355X_MICROARCH.md §LDS).  The order of a row's entries is
+  // free: per group of 32 rows, a seeded local search swaps two entries of a row whenever that
+  // does not raise Σ_e Σ_bank count² (the sentinel broadcasts: not counted).  Host work only.
+  if (env_int("QLDPC_M2V_ORDER", 1) != 0) {
+    uint64_t rs = 0x9E3779B97F4A7C15ull;
+    auto rnd = [&]() { rs ^= rs << 13; rs ^= rs >> 7; rs ^= rs << 17; return rs; };
+    for (int q = 0; q < 4; ++q)
+      for (int g0 = 0; g0 < TBm; g0 += 32) {
+        std::vector<int> rr;
+        for (int l = 0; l < 32; ++l)
+          if (q * TBm + g0 + l < g->m) rr.push_back(q * TBm + g0 + l);
+        if (rr.size() < 2) continue;
+        int cnt[7][32] = {{0}};
+        auto bk = [&](uint32_t o) { return (int)((o / 8u) % 32u); };
+        for (int i : rr)
+          for (int e = 0; e < 7; ++e)
+            if (roff[i][e] != sent) cnt[e][bk(roff[i][e])]++;
+        for (int it = 0; it < 4000; ++it) {
+          const int i = rr[rnd() % rr.size()], a = (int)(rnd() % 7), b = (int)(rnd() % 7);
+          const uint32_t oa = roff[i][a], ob = roff[i][b];
+          if (a == b || oa == ob) continue;
+          auto term = [&](int e, uint32_t o, int dlt) {  // change of count^2 when o enters (+1) / leaves (-1) e
+            if (o == sent) return 0;
+            const int c = cnt[e][bk(o)];
+            return dlt > 0 ? 2 * c + 1 : -(2 * c - 1);
+          };
+          int d = term(a, oa, -1);
+          if (oa != sent) cnt[a][bk(oa)]--;
+          d += term(b, ob, -1);
+          if (ob != sent) cnt[b][bk(ob)]--;
+          d += term(a, ob, +1);
+          if (ob != sent) cnt[a][bk(ob)]++;
+          d += term(b, oa, +1);
+          if (oa != sent) cnt[b][bk(oa)]++;
+          if (d <= 0) {
+            roff[i][a] = ob;
+            roff[i][b] = oa;
+          } else {  // undo
+            if (ob != sent) cnt[a][bk(ob)]--;
+            if (oa != sent) cnt[b][bk(oa)]--;
+            if (oa != sent) cnt[a][bk(oa)]++;
+            if (ob != sent) cnt[b][bk(ob)]++;
+          }
+        }
+      }
+  }
+  tab.assign((size_t)4 * TBm * 4, 0);
+  for (int q = 0; q < 4; ++q)
+    for (int t = 0; t < TBm; ++t) {
+      const int i = q * TBm + t;
+      uint32_t o[8];
+      for (int e = 0; e < 8; ++e) o[e] = i < g->m ? roff[i][e] : sent;
+      for (int w = 0; w < 4; ++w) tab[((size_t)q * TBm + t) * 4 + w] = o[2 * w] | (o[2 * w + 1] << 16);
+    }
+  return 0;
+}
+
+// The host tables of a planned decoder (bp->route, bp->slot_var; the m2v lane search may permute
+// the latter), plus its label / LDS-model statistics.
+static int build_tables(qldpc_bp* bp, HostTables& T) {
+  const qldpc_graph* g = bp->g;
+  const Route& r = bp->route;
+  if (r.engine == 1) {
+    const int TB = r.TB, VPL = r.VPL, DM = r.DMAX, D2 = DM / 2;
+    T.edges.assign((size_t)VPL * D2 * TB, 0xFFFFFFFFu);
     for (int k = 0; k < VPL; ++k)
       for (int t = 0; t < TB; ++t) {
         const int j = k * TB + t;
@@ -1138,512 +1573,115 @@ static int create_min_sum(qldpc_graph* g, const double* channel_probs, int32_t m
         const auto& rows = g->col_rows[j];
         for (int d = 0; d < DM; ++d) {
           const uint32_t v = d < (int)rows.size() ? (uint32_t)rows[d] : 0xFFFFu;
-          uint32_t& w = vchk[((size_t)k * D2 + d / 2) * TB + t];
+          uint32_t& w = T.edges[((size_t)k * D2 + d / 2) * TB + t];
           w = (d & 1) ? ((w & 0xFFFFu) | (v << 16)) : ((w & 0xFFFF0000u) | v);
         }
       }
-    bp->lds_bytes = (int)lds_for(precision, g->m);
-    kern = get_variant(precision, bp->VPL, DM).dec_k;
+    return 0;
+  }
+  const int tsize = r.precision == 32 ? 4 : 8;
+  const RLayout L = route_layout(r, route_vslots(r, g->m), g->m);
+  if (r.m2s == 3 && env_int("QLDPC_M2V_PERM", 0) != 0) m2v_lane_search(g, r, bp->slot_var);
+  // fp64 two-word families (measured +3 % with the bank-aware fp64 v2c placement); fp32 gathers of
+  // the structured codes are already near conflict-free, and the m2s family runs 2.5 % faster on
+  // the identity labels (1.188 M vs 1.159 M shots/s, profiles/r03/m2s_ab/ab_label.txt): off there
+  // (QLDPC_LABEL=1 forces it on)
+  if (r.engine == 3 && env_int("QLDPC_LABEL", r.precision == 64 && !r.m2s ? 1 : 0) != 0)
+    T.lab = label_checks(g, r, bp->slot_var, &bp->gather_conf[0], &bp->gather_conf[1]);
+  const bool f64e3 = r.engine == 3 && r.precision == 64 && r.m2s != 3;
+  int ndummy = 0;
+  build_slot_edges(g, r, bp->slot_var, T.edges, (r.engine == 3 && env_int("QLDPC_BANKOPT", 1) != 0) ? (int)(L.v / 4) : -1,
+                   T.lab, r.m2s == 1 && env_int("QLDPC_M2S_PLACE", 1) != 0,
+                   r.vslots_dummy ? (1 + g->m * r.nch) * (16 / tsize) : -1, &ndummy,
+                   !f64e3 ? 0 : (r.m2s || r.tail) ? 1 : env_int("QLDPC_ANNEAL_2W", 1) != 0 ? 2 : 0, -1,
+                   (r.tail && r.vslots_dummy) ? (int)(L.t - L.v) / tsize : -1);
+  if (ndummy != r.vslots_dummy) return set_err(QLDPC_EINVAL, "m2s private dummy slot count mismatch");
+  if (f64e3 && r.ea_shift == 0) lds_model_var_phase(T.edges, r, L.v, bp->lds_model);
+  if (r.m2s == 3)
+    if (const int rc = m2v_row_table(g, r, bp->slot_var, T.rowtab)) return rc;
+  if (r.engine >= 3) {
+    // row degrees by check label: engine 4 keeps them in F, engine 3 their parity (bp_reg.h, w domain)
+    T.rdeg.resize(std::max(1, g->m));
+    for (int i = 0; i < g->m; ++i) T.rdeg[T.lab.empty() ? i : T.lab[i]] = (uint8_t)(g->row_ptr[i + 1] - g->row_ptr[i]);
+  }
+  return 0;
+}
+
+static int upload(DevBuf& buf, const void* src, size_t bytes, const char* what) {
+  if (const int rc = buf.alloc(std::max<size_t>(bytes, 1))) return rc;
+  if (bytes && hipMemcpy(buf.p, src, bytes, hipMemcpyHostToDevice) != hipSuccess) return set_err(QLDPC_EHIP, what);
+  return 0;
+}
+
+// validate -> plan the route -> build the host tables -> upload -> occupancy -> first-min step
+static int create_min_sum(qldpc_graph* g, const double* channel_probs, int32_t max_iter, int32_t bp_method,
+                          double ms_scaling_factor, int32_t precision, int32_t vars_per_thread,
+                          int32_t min_col_slots, int forced_engine, qldpc_bp** out) {
+  if (!out) return set_err(QLDPC_EINVAL, "NULL argument");
+  int rc = validate_create(g, channel_probs, precision, bp_method);
+  if (rc) return rc;
+  QLDPC_HIP(hipSetDevice(g->device));
+  if (bp_method == QLDPC_PRODUCT_SUM) return create_ps(g, channel_probs, max_iter, precision, out);
+  auto* bp = new qldpc_bp();
+  auto fail = [&](int code) {
+    qldpc_bp_destroy(bp);
+    return code;
+  };
+  bp->g = g;
+  bp->max_iter = max_iter > 0 ? max_iter : g->n;
+  bp->method = bp_method;
+  bp->alpha = ms_scaling_factor;
+  bp->probs.assign(channel_probs, channel_probs + g->n);
+  if ((rc = plan_route(g, !QLDPC_M2S_UNIL || uniform_priors(channel_probs, g->n), precision, vars_per_thread,
+                       min_col_slots, forced_engine, bp->route, bp->slot_var)))
+    return fail(rc);
+  const Route& r = bp->route;
+  const int tsize = precision == 32 ? 4 : 8;
+  const void* kern;
+  if (r.engine == 6) {
+    if ((rc = hbm_prepare(bp)) || (rc = bp->llr.alloc((size_t)g->n * tsize))) return fail(rc);
+    kern = hbm_kernel(precision);
   } else {
-    if (bp->engine == 4 && g->max_row > 8) bp->engine = 3;  // engine 4 rows are 8 slots wide
-    bp->nch = bp->engine == 4 ? 8 * tsize / 16 : (std::max(1, g->max_row) * tsize + 15) / 16;
-    const int vslots = (1 + g->m * bp->nch) * (16 / tsize);
-    if (vslots >= 0xFFFF) {  // no LDS image addresses this many slots: HBM-resident messages (engine 6)
-      if (env_int("QLDPC_HBM_FALLBACK", 1) == 0)
-        return fail(set_err(QLDPC_ENOTSUP, "V image exceeds 65535 message slots (QLDPC_HBM_FALLBACK=0)"));
-      return setup_hbm();
-    }
-    // degree-5/6 variables hold 2.5x the registers of degree-4 ones: fewer per thread
-    const int pref = DM == 4 ? kPrefVplR : 4;
-    int vmax = DM == 4 ? kMaxVplR : 5;
-    // images of 64-256 KiB (space-time graphs): engine 3 with dword-scaled addresses (fp32, 4 slots)
-    if (bp->engine == 3 && precision == 32 && DM == 4 && !r_fits(3, vslots, g->m, tsize) &&
-        r_fits(3, vslots, g->m, tsize, 2) && env_int("QLDPC_E3_BIG", 1) != 0)
-      bp->ea_shift = 2;
-    // rows one message wider than whole chunks (space-time graphs: rows of 9 = 4 fp64 / 2 fp32
-    // chunks + 1): chunk rows + a tail slot per row, dword-scaled addresses, 1024-thread
-    // workgroups.  fp64: the image fits LDS at all (162.7 KB instead of 176 KB); fp32: the check
-    // phase reads 36 instead of 48 bytes per row through the compile-time-width loop.  fp64 images
-    // past the 16-bit layout's 64 KiB take it too (round 6: e.g. hgp_34_n1600 over two rounds, 1536 x
-    // 4736, 117 KB, which ran on engine 2 before: fp64 engine 3 has no dword-scaled plain layout), and
-    // so do fp64 rows of 8 (the tail slot stays empty: GenBicycleA3 / A4 over 2-5 rounds) and graphs
-    // whose geometry is 512 threads (hgp_34_n625 over three rounds, 900 x 2775: two decodes per CU)
-    const bool f64t = precision == 64 && env_int("QLDPC_E3_TAIL64", 1) != 0;
-    if (bp->engine == 3 && DM == 4 && (g->max_row == 9 || (f64t && g->max_row == 8)) && env_int("QLDPC_E3_TAIL", 1) != 0 &&
-        (precision == 32 || !r_fits(3, vslots, g->m, tsize, f64t ? 0 : 2))) {
-      const int nch_t = 8 * tsize / 16;
-      const int vst = (1 + g->m * nch_t) * (16 / tsize);
-      int tb = 0, vpl = 0;
-      // fp32: byte F words shrink the image below half a CU (config 5: 85.1 -> 79.6 KB), so two
-      // 512-thread decodes share a CU (bp_reg.h eng_fb; QLDPC_E3_FB=0 keeps one 1024-thread decode)
-      const int vpl_fb = (g->n + 511) / 512;
-      if (precision == 32 && vars_per_thread <= 0 && env_int("QLDPC_TB", 0) <= 0 && env_int("QLDPC_E3_FB", 1) != 0 &&
-          vpl_fb >= 9 && vpl_fb <= 12 && (g->m + 511) / 512 <= 32 && r_fits(3, vst, g->m, tsize, 2, 1, 0, 1) &&
-          2 * r_lds_bytes((int)r_layout(3, vst, g->m, tsize, 1, 0, 1).total, kChunkMax) <= (size_t)kLdsMax) {
-        bp->tail = 1;
-        bp->fb = 1;
-        bp->nch = nch_t;
-        bp->ea_shift = 2;
-        bp->TB = 512;
-        bp->VPL = vpl_fb;
-      } else if (r_fits(3, vst, g->m, tsize, 2, 1) && !choose_rgeometry(g->n, g->m, vars_per_thread, tb, vpl) &&
-                 (tb > 512 || (f64t && tb == 512)) && vpl >= 4 && vpl <= 8) {
-        bp->tail = 1;
-        bp->nch = nch_t;
-        bp->ea_shift = 2;
-      }
-    }
-    // fp64 "m2 in slot" family (bp_reg.h eng_m2s, kern_r_f64_m2s.hip): one-word check state, m2 in
-    // the argmin edge's V slot, rows of up to 7 edges as 3 chunks + a tail slot, <= 256 threads.
-    // The headline hgp_34_n1600 image drops from 65.0 KB to 52.3 KB: 3 workgroups per CU instead
-    // of 2.  The kernel keeps no dummy edges for real variables, so every column degree must be
-    // 3 or 4 with the degree-3 variables filling whole variable slots (host degree sort).
-    if (bp->engine == 3 && precision == 64 && DM == 4 && !bp->tail && g->max_row >= 1 && g->max_row <= 7 &&
-        env_int("QLDPC_M2S", 1) != 0 && env_int("QLDPC_DEGSORT", 1) != 0) {
-      int tb = 0, vpl = 0, n3 = 0, nother = 0;
-      for (int j = 0; j < g->n; ++j) {
-        const int d = (int)g->col_rows[j].size();
-        n3 += d == 3;
-        nother += d != 3 && d != 4;
-      }
-      bool uni = true;  // QLDPC_M2S_UNIL kernels hold one prior for every variable
-      for (int j = 1; j < g->n && QLDPC_M2S_UNIL; ++j) uni = uni && channel_probs[j] == channel_probs[0];
-      if (!nother && uni && !choose_rgeometry(g->n, g->m, vars_per_thread, tb, vpl) && tb <= 256 && vpl >= 4 &&
-          vpl <= 8 && (n3 % tb == 0 || n3 == g->n) && r_fits(3, (1 + g->m * 3) * 2, g->m, 8, 0, 1, 1)) {
-        bp->tail = 1;
-        bp->m2s = 1;
-        bp->nch = 3;
-        bp->ea_shift = 0;
-        // "c2v in slot" (bp_reg.h eng_c2s, kern_r_f64_c2s.hip, opt-in QLDPC_C2S=1): the check phase
-        // writes the c2v of every edge into the row's slots, so no row may have a padding slot:
-        // every row exactly 7 edges (the headline HGP graphs).  No CS array (n1600 52.3 -> 46.2 KB)
-        // and 25 % fewer VALU, but its check phase stores 7 words per row where m2s stores 2, and
-        // LDS stores cost 3x the cycles of reads per byte: 1.141 M vs 1.189 M shots/s
-        // (profiles/r03/c2s/), so m2s stays the default
-        bool full = true;
-        for (int i = 0; i < g->m && full; ++i) full = g->row_ptr[i + 1] - g->row_ptr[i] == 7;
-        if (full && QLDPC_EXPERIMENTAL && env_int("QLDPC_C2S", 0) != 0 && r_fits(3, (1 + g->m * 3) * 2, g->m, 8, 0, 1, 2)) bp->m2s = 2;
-        // variable-major V slots (bp_reg.h eng_m2v, kern_r_f64_m2v.hip): edge (k, d) of lane t at
-        // slot (ecnt(k) + d) * 256 + t, the last variable slot at ecnt * 256 + d * NL + t, then one
-        // sentinel slot; the check phase's rows come from a register table (m <= 4 * 256)
-        const int d3 = n3 == g->n ? vpl : n3 / 256;
-        const int nlast = g->n - (vpl - 1) * 256, NL = (nlast + 63) & ~63;
-        const int ecl = 3 * std::min(vpl - 1, d3) + 4 * std::max(0, vpl - 1 - d3);
-        const int vm = ecl * 256 + (vpl - 1 < d3 ? 3 : 4) * NL + 1;
-        if (bp->m2s == 1 && tb == 256 && g->m <= 4 * 256 && vm * 8 < 65536 && QLDPC_EXPERIMENTAL && env_int("QLDPC_M2V", 0) != 0 &&
-            r_fits(3, vm, g->m, 8, 0, 0, 1)) {
-          bp->m2s = 3;
-          bp->tail = 0;
-          bp->vslots_m2v = vm;
-          bp->m2v_vlast = ecl * 256;
-          bp->m2v_nl = NL;
-        }
-      }
-    }
-    // fp64 space-time graphs on the tail layout (rows of 8 / 9 as 4 chunks + a tail slot, 1024 threads,
-    // one decode per CU): the one-word check state too (round 6, kern_r_f64_m2st.hip, engine id
-    // 111313).  The two-word tail family re-reads each edge's own previous v2c from LDS (its 128-VGPR
-    // budget had no room for it) and gathers 16-byte check states: 24 B of variable-phase reads per
-    // edge.  Here the own v2c lives in VGPRs (118 with the uniform prior in SGPRs, no scratch) and an
-    // edge reads the 8-byte CS and its own slot: 16 B.  Real variables never touch a shared dummy:
-    // the measurement variables in 3-edge slots and the degree-3 ones in 4-edge slots get private
-    // dummy V slots (config 5: 1,348, 10.8 KB), placed before the tail array.  Uniform priors only.
-    if (bp->engine == 3 && precision == 64 && DM == 4 && bp->tail && !bp->fb && !bp->m2s && bp->nch == 4 &&
-        env_int("QLDPC_M2ST", 1) != 0 && env_int("QLDPC_DEGSORT", 1) != 0 && env_int("QLDPC_D2K", 1) != 0) {
-      int tb = 0, vpl = 0;
-      bool uni = true;
-      for (int j = 1; j < g->n && QLDPC_M2S_UNIL; ++j) uni = uni && channel_probs[j] == channel_probs[0];
-      if (uni && !choose_rgeometry(g->n, g->m, vars_per_thread, tb, vpl) && tb >= 512) {
-        // the slot map the build below makes (st_plan), its D2K / D3K and the private dummies of
-        // build_slot_edges
-        const StPlan P = st_plan(g, tb, vpl, DM, env_int("QLDPC_NW", 1) != 0, env_int("QLDPC_NW_BAL", 1) != 0);
-        const int d2 = P.d2, d3 = P.d3, nd = P.nd;
-        int dmax = 0;
-        for (int j = 0; j < g->n; ++j) dmax = std::max(dmax, (int)g->col_rows[j].size());
-        const int vs = (1 + g->m * 4) * 2 + nd;
-        if (dmax <= DM && d2 >= 1 && vs < 0x3FFFF && get_rvariant_f64_m2st(vpl, d3, d2).dec_k &&
-            r_fits(3, vs, g->m, 8, 2, 1, 1)) {
-          bp->m2s = 1;
-          bp->vslots_dummy = nd;
-          bp->nw = P.nw;
-          bp->live_last = P.live_last;
-#if QLDPC_DIAG_NOLAST
-          // diagnostic builds only (results invalid): no wave runs the last variable slot, to time the
-          // cost of the waves that hold it
-          bp->live_last = 0;
-#endif
-        }
-      }
-    }
-    int m2s8_vpt = 0;  // (the rows-of-8 family's 128-thread geometry for small graphs, below)
-    // fp64 column degree 5 graphs that come out at 512 threads x <= 3 variables (LP_Matg8_L21 / L30's
-    // [h | I], 315 x 1029 / 450 x 1470): the two-word degree-5 family at 256 threads x 5 / 6 variables
-    // instead of engine 2 (round 6; QLDPC_D5_256=0 keeps the old geometry)
-    if (bp->engine == 3 && precision == 64 && DM == 5 && vars_per_thread <= 0 && env_int("QLDPC_TB", 0) <= 0 &&
-        env_int("QLDPC_D5_256", 1) != 0 && g->max_row > 8 && g->max_row <= 10) {
-      int tb = 0, vpl = 0;
-      if (!choose_rgeometry(g->n, g->m, 0, tb, vpl, pref, vmax) && tb > 256)
-        for (int v = 5; v <= 6 && vars_per_thread <= 0; ++v) {
-          int tb5 = 0, vpl5 = 0;
-          if (!choose_rgeometry(g->n, g->m, v, tb5, vpl5, pref, 6) && tb5 <= 256) {
-            vars_per_thread = v;
-            vmax = std::max(vmax, v);
-          }
-        }
-    }
-    // the same family for rows of 8 and column degree 5 (kern_r_f64_m2s8.hip, engine id 10103): the
-    // lifted-product codes (LP_Matg8_L30: 750 degree-3 and 270 degree-5 columns, rows of 8).  Rows of
-    // 4 chunks, no tail array.  Slots k >= D3K hold 5 edge slots; a real variable with fewer edges
-    // there (a degree-3 variable in the slot shared with the degree-5 class) gets a PRIVATE dummy V
-    // slot per missing edge, past the rows, and the dummy CS entry 0 (+0, parity 0): no other lane
-    // writes that slot, so the variable phase always reads its own previous v2c back and takes
-    // c2v = +-0, which leaves every sum bit-exact (w-domain sums are never -0).  The two-word family
-    // runs these graphs at 2 workgroups per CU (256 VGPRs); the one-word state fits 3.
-    if (bp->engine == 3 && precision == 64 && DM == 5 && !bp->tail && !bp->m2s && g->max_row >= 1 && g->max_row <= 8 &&
-        env_int("QLDPC_M2S", 1) != 0 && env_int("QLDPC_M2S8", 1) != 0 && env_int("QLDPC_DEGSORT", 1) != 0) {
-      int tb = 0, vpl = 0, n3 = 0;
-      for (int j = 0; j < g->n; ++j) n3 += g->col_rows[j].size() <= 3;
-      bool uni = true;
-      for (int j = 1; j < g->n && QLDPC_M2S_UNIL; ++j) uni = uni && channel_probs[j] == channel_probs[0];
-      bool ok = uni && !choose_rgeometry(g->n, g->m, vars_per_thread, tb, vpl, pref, vmax);
-      // smaller graphs (LP_Matg8_L16 / L21, the Threshold notebook's codes: 544 / 714 columns) come out
-      // at 256 threads x 3 variables, below the family's 4-6: run them at the most variables per thread
-      // (<= 5 for degree 5) whose workgroup is smaller, 128 x 5 / 192 x 5 (round 6; they ran on engine 2
-      // before).  The geometry call below then takes this VPL.
-      if (ok && tb == 256 && vpl < 4 && vars_per_thread <= 0 && env_int("QLDPC_TB", 0) <= 0 &&
-          env_int("QLDPC_M2S8_SMALL", 1) != 0)
-        for (int v = std::min(6, vmax); v >= 4 && !m2s8_vpt; --v) {
-          int tb2 = 0, vpl2 = 0;
-          if (!choose_rgeometry(g->n, g->m, v, tb2, vpl2, pref, vmax) && tb2 < 256 && vpl2 == v) {
-            tb = tb2;
-            vpl = vpl2;
-            m2s8_vpt = v;
-          }
-        }
-      if (ok && (tb == 256 || (tb < 256 && m2s8_vpt > 0)) && vpl >= 4 && vpl <= 6) {
-        // the slot map below: degree <= 3 first, so slots k < n3 / tb (whole) hold degree <= 3 only
-        const int d3 = n3 == g->n ? vpl : n3 / tb;
-        int nd = 0;
-        for (int p = 0, c = 0; c < 2; ++c)
-          for (int j = 0; j < g->n; ++j) {
-            const int d = (int)g->col_rows[j].size();
-            if ((d <= 3 ? 0 : 1) != c) continue;
-            nd += ((p / tb) < d3 ? 3 : DM) - d;
-            ++p;
-          }
-        const int vs = (1 + g->m * 4) * 2 + nd;
-        if (vs < 0xFFFF && r_fits(3, vs, g->m, 8, 0, 0, 1)) {
-          bp->m2s = 1;
-          bp->nch = 4;
-          bp->ea_shift = 0;
-          bp->vslots_dummy = nd;
-          if (m2s8_vpt > 0) vars_per_thread = m2s8_vpt;
-          // packed absolute addresses, 4 workgroups per CU: LP L30 fp64 4.08 M vs 3.67 M shots/s
-          // (0.622 vs 0.561 of the LDS roofline, profiles/r04/passd/); QLDPC_M2S8_PK=0 keeps 10103
-          bp->m2s_pk = env_int("QLDPC_M2S8_PK", 1) != 0 && vpl <= 5 &&
-                       4 * r_lds_bytes((int)r_layout(3, vs, g->m, 8, 0, 1).total, kChunkMax) <= (size_t)kLdsMax;
-        }
-      }
-    }
-    const int vslots_e3 = bp->vslots_m2v ? bp->vslots_m2v : (1 + g->m * bp->nch) * (16 / tsize) + bp->vslots_dummy;
-    if (bp->engine >= 3 && ((DM != 4 && !(bp->engine == 3 && (DM == 5 || DM == 6))) ||
-                            (!bp->fb && choose_rgeometry(g->n, g->m, vars_per_thread, bp->TB, bp->VPL, pref, vmax)) ||
-                            !r_fits(bp->engine, vslots_e3, g->m, tsize, bp->ea_shift, bp->tail, bp->m2s, bp->fb) ||
-                            (precision == 64 && DM == 5 && !bp->m2s &&
-                             !use_f64w(bp->engine, precision, DM, bp->TB, bp->VPL, bp->ea_shift, bp->nch)))) {
-      bp->ea_shift = 0;
-      bp->tail = 0;
-      bp->m2s = 0;
-      bp->vslots_dummy = 0;
-      bp->m2s_pk = 0;
-      bp->fb = 0;
-      bp->engine = 2;  // graph outside the register engines' envelope
-      bp->nch = (std::max(1, g->max_row) * tsize + 15) / 16;
-      if (DM == 5 || DM == 6) bp->DMAX = DM = 8;  // engine 2 kernels come in 4 and 8 slots
-    }
-    const int vslots2 = bp->vslots_m2v ? bp->vslots_m2v : (1 + g->m * bp->nch) * (16 / tsize) + bp->vslots_dummy;
-    if (bp->engine >= 3) {
-      bp->NS = 1;
-      bp->lds_bytes =
-          (int)r_lds_bytes((int)r_layout(bp->engine, vslots2, g->m, tsize, bp->tail, bp->m2s, bp->fb).total, kChunkMax);
-    } else {
-      rc = choose_sgeometry(g->n, g->m, vars_per_thread, bp->TB, bp->VPL);
-      if (rc) return fail(rc);
-      const int img = (int)slot_img_bytes(vslots2, g->m, tsize);
-      bp->NS = choose_ns(img);
-      bp->lds_bytes = (int)slot_lds_bytes(bp->NS, img, kChunkMax);
-      // big images leave room for few workgroups per CU: widen the workgroup so
-      // the CU still holds >= 16 waves (ST n1225 fp32: 1 x 1024 threads, 2x the
-      // samples/s of 1 x 256, bench.py --workload phenl)
-      const int bpc = std::max(1, kLdsMax / std::max(1, bp->lds_bytes));
-      if (vars_per_thread <= 0 && env_int("QLDPC_TB", 0) <= 0 && bpc * bp->TB / 64 < 16) {
-        const int tb = std::min(kMaxThreadsS, round_up((16 + bpc - 1) / bpc * 64, 64));
-        if (tb > bp->TB) {
-          bp->TB = tb;
-          bp->VPL = (g->n + tb - 1) / tb;
-        }
-      }
-    }
-    if (bp->lds_bytes > kLdsMax) {  // no LDS engine holds this decode: HBM-resident messages
-      if (env_int("QLDPC_HBM_FALLBACK", 1) == 0)
-        return fail(set_err(QLDPC_ENOTSUP, "per-shot LDS image exceeds 160 KiB (QLDPC_HBM_FALLBACK=0)"));
-      return setup_hbm();
-    }
-    // slot -> variable map: identity, or (engine 3) degree <= 3 variables first
-    const int TB = bp->TB, VPL = bp->VPL;
-    std::vector<int32_t> order;
-    order.reserve(g->n);
-    const bool sort3 = bp->engine == 3 && DM >= 4 && env_int("QLDPC_DEGSORT", 1) != 0;
-    // byte-F kernels also keep degree <= 2 variables (the space-time measurement columns) in
-    // compile-time 2-edge slots: those go first
-    const bool sort2 = sort3 && (bp->fb || (bp->tail && precision == 64 && (!bp->m2s || bp->nch == 4))) &&
-                       env_int("QLDPC_D2K", 1) != 0;
-    auto cls = [&](int j) {
-      const int d = (int)g->col_rows[j].size();
-      return sort2 ? (d <= 2 ? 0 : d <= 3 ? 1 : 2) : (d <= 3 ? 0 : 1);
-    };
-    // (the fp64 space-time m2s family: st_plan's order, degree classes 1 / 2 / 3 / 4 with narrow waves)
-    const bool stm2s = bp->engine == 3 && precision == 64 && bp->tail && bp->m2s == 1 && bp->nch == 4;
-    if (stm2s) {
-      bp->slot_var = st_plan(g, bp->TB, bp->VPL, DM, env_int("QLDPC_NW", 1) != 0, env_int("QLDPC_NW_BAL", 1) != 0).slots;
-    } else {
-      for (int pass = 0; pass < (sort2 ? 3 : sort3 ? 2 : 1); ++pass)
-        for (int j = 0; j < g->n; ++j)
-          if (!sort3 || cls(j) == pass) order.push_back(j);
-      bp->slot_var.assign((size_t)VPL * TB, -1);
-      for (int j = 0; j < g->n; ++j) bp->slot_var[j] = order[j];
-    }
+    HostTables T;
+    if ((rc = build_tables(bp, T))) return fail(rc);
     bp->npos = g->n;
-    bp->d3k = 0;
-    if (sort3)
-      for (int k = 0; k < VPL; ++k) {
-        bool ok = true;
-        for (int t = 0; t < TB && ok; ++t) {
-          const int j = bp->slot_var[(size_t)k * TB + t];
-          ok = j < 0 || (int)g->col_rows[j].size() <= 3;
-        }
-        if (!ok) break;
-        bp->d3k = k + 1;
-      }
-    bp->d2k = 0;
-    if (sort2)
-      for (int k = 0; k < VPL; ++k) {
-        bool ok = true;
-        for (int t = 0; t < TB && ok; ++t) {
-          const int j = bp->slot_var[(size_t)k * TB + t];
-          ok = j < 0 || (int)g->col_rows[j].size() <= 2;
-        }
-        if (!ok) break;
-        bp->d2k = k + 1;
-      }
-    const int vbase_dw = (bp->engine == 3 && env_int("QLDPC_BANKOPT", 1) != 0)
-                             ? (int)(r_layout(3, vslots2, g->m, tsize, bp->tail, bp->m2s).v / 4)
-                             : -1;
-    // fp64 engine-3 kernels are built with D3K = 0 only, except the <= 256-thread family
-    if (precision != 32 && !use_f64w(bp->engine, precision, DM, bp->TB, bp->VPL, bp->ea_shift, bp->nch) &&
-        !use_f64x(bp->engine, precision, DM, bp->TB, bp->VPL, bp->ea_shift) && !bp->tail && !bp->m2s)
-      bp->d3k = 0;
-    std::vector<int> lab;
-    if (bp->m2s == 3 && env_int("QLDPC_M2V_PERM", 0) != 0) {  // (opt-in: measured 1.6 % slower)
-      // m2v: a variable's V slots sit in its lane's bank pair (slot mod 32 = lane mod 32), so which
-      // lane a variable occupies inside its slot k sets the banks of the check phase's gathers.  A
-      // seeded local search swaps two variables of one slot k (same degree class) whenever that
-      // does not raise Σ_{row group of 32, bank} load² (the check gathers; a group whose bank loads
-      // are all <= 7 admits conflict-free gather orders) + Σ_{32-lane group, edge, bank} count² of
-      // the variable phase's CS gathers (bank pair = (check + 1) mod 32).  Storage only.
-      const int TBm = bp->TB, VPLm = bp->VPL, M = g->m;
-      const int ng = (M + 31) / 32;
-      std::vector<int> L((size_t)ng * 32, 0);                       // check groups x banks
-      std::vector<int> C((size_t)VPLm * DM * (TBm / 32) * 32, 0);   // CS gather groups x banks
-      auto cidx = [&](int k, int d, int h, int b) { return (((size_t)k * DM + d) * (TBm / 32) + h) * 32 + b; };
-      auto add = [&](int j, int pos, int sg) {
-        const int k = pos / TBm, t = pos % TBm, b = t % 32, h = t / 32;
-        const auto& rows = g->col_rows[j];
-        for (int d = 0; d < (int)rows.size(); ++d) {
-          L[(size_t)(rows[d] / 32) * 32 + b] += sg;
-          C[cidx(k, d, h, (rows[d] + 1) % 32)] += sg;
-        }
-      };
-      auto sq = [&](int j, int pos) {  // Σ of the counts this variable's entries see (for the delta)
-        const int k = pos / TBm, t = pos % TBm, b = t % 32, h = t / 32;
-        long long v = 0;
-        const auto& rows = g->col_rows[j];
-        for (int d = 0; d < (int)rows.size(); ++d) v += 2 * L[(size_t)(rows[d] / 32) * 32 + b] + C[cidx(k, d, h, (rows[d] + 1) % 32)];
-        return v;
-      };
-      for (int pos = 0; pos < VPLm * TBm; ++pos)
-        if (bp->slot_var[pos] >= 0) add(bp->slot_var[pos], pos, +1);
-      uint64_t rs = 0xD1B54A32D192ED03ull;
-      auto rnd = [&]() { rs ^= rs << 13; rs ^= rs >> 7; rs ^= rs << 17; return rs; };
-      const int iters = env_int("QLDPC_M2V_PERM_IT", 400000);
-      for (int it = 0; it < iters; ++it) {
-        const int k = (int)(rnd() % (uint64_t)VPLm);
-        const int pa = k * TBm + (int)(rnd() % (uint64_t)TBm), pb = k * TBm + (int)(rnd() % (uint64_t)TBm);
-        const int ja = bp->slot_var[pa], jb = bp->slot_var[pb];
-        if (ja < 0 || jb < 0 || pa == pb || (pa % 32) == (pb % 32) && (pa / 32) == (pb / 32)) continue;
-        if (g->col_rows[ja].size() != g->col_rows[jb].size()) continue;
-        // cost change: remove both, measure, add swapped, measure (counts are small integers)
-        add(ja, pa, -1);
-        add(jb, pb, -1);
-        const long long before = sq(ja, pa) + sq(jb, pb);
-        const long long after = sq(ja, pb) + sq(jb, pa);
-        if (after <= before) {
-          bp->slot_var[pa] = jb;
-          bp->slot_var[pb] = ja;
-          add(jb, pa, +1);
-          add(ja, pb, +1);
-        } else {
-          add(ja, pa, +1);
-          add(jb, pb, +1);
-        }
-      }
-    }
-    // fp64 two-word families (measured +3 % with the bank-aware fp64 v2c placement); fp32 gathers of
-    // the structured codes are already near conflict-free, and the m2s family runs 2.5 % faster on
-    // the identity labels (1.188 M vs 1.159 M shots/s, profiles/r03/m2s_ab/ab_label.txt): off there
-    // (QLDPC_LABEL=1 forces it on)
-    if (bp->engine == 3 && env_int("QLDPC_LABEL", precision == 64 && !bp->m2s ? 1 : 0) != 0) {
-      lab = label_checks(g, bp->slot_var, bp->TB, bp->VPL, DM, tsize, &bp->gather_conf[0], &bp->gather_conf[1], bp->m2s);
+    if (!T.lab.empty()) {
       std::vector<int32_t> inv(g->m);
-      for (int i = 0; i < g->m; ++i) inv[lab[i]] = i;
-      if ((rc = bp->rperm.alloc((size_t)std::max(1, g->m) * 4))) return fail(rc);
-      if (g->m && hipMemcpy(bp->rperm.p, inv.data(), (size_t)g->m * 4, hipMemcpyHostToDevice) != hipSuccess)
-        return fail(set_err(QLDPC_EHIP, "upload check labels"));
+      for (int i = 0; i < g->m; ++i) inv[T.lab[i]] = i;
+      if ((rc = upload(bp->rperm, inv.data(), inv.size() * 4, "upload check labels"))) return fail(rc);
     }
-    int ndummy = 0;
-    build_slot_edges(g, bp->TB, bp->VPL, DM, tsize, bp->nch, bp->slot_var, vchk, vbase_dw, lab, bp->tail,
-                     bp->m2s == 1 && env_int("QLDPC_M2S_PLACE", 1) != 0, bp->d3k,
-                     bp->vslots_dummy ? (1 + g->m * bp->nch) * (16 / tsize) : -1, &ndummy,
-                     (bp->engine == 3 && precision == 64 && bp->m2s != 3)
-                         ? ((bp->m2s || bp->tail) ? 1 : env_int("QLDPC_ANNEAL_2W", 1) != 0 ? 2 : 0)
-                         : 0,
-                     -1,
-                     (bp->tail && bp->vslots_dummy) ? (int)(r_layout(3, vslots2, g->m, tsize, 1, bp->m2s).t - r_layout(3, vslots2, g->m, tsize, 1, bp->m2s).v) / tsize : -1,
-                     bp->d2k, bp->nw);
-    if (ndummy != bp->vslots_dummy) return fail(set_err(QLDPC_EINVAL, "m2s private dummy slot count mismatch"));
-    if (bp->engine == 3 && precision == 64 && bp->m2s != 3 && bp->ea_shift == 0)
-      lds_model_var_phase(vchk, bp->TB, bp->VPL, DM, bp->d3k,
-                          (uint32_t)r_layout(3, vslots2, g->m, tsize, bp->tail, bp->m2s).v, bp->m2s == 1,
-                          bp->lds_model);
-    if (bp->m2s == 3) {
-      // m2v row table (bp_reg.h M2vRows): row i = q * TB + t -> uint4 (q * TB + t): the byte offsets
-      // from the V base of its edges' variable-major slots, two 16-bit offsets per word, the unused
-      // entries at the sentinel slot
-      const int TBm = bp->TB, VPLm = bp->VPL, d3 = std::min(bp->d3k, VPLm);
-      auto ecnt = [&](int k) { return 3 * std::min(k, d3) + 4 * std::max(0, k - d3); };
-      if (ecnt(VPLm - 1) * TBm != bp->m2v_vlast) return fail(set_err(QLDPC_ENOTSUP, "m2v layout mismatch"));
-      const uint32_t sent = (uint32_t)(bp->vslots_m2v - 1) * 8u;
-      std::vector<std::vector<uint32_t>> roff(g->m);
-      for (int k = 0; k < VPLm; ++k)
-        for (int t = 0; t < TBm; ++t) {
-          const int j = bp->slot_var[(size_t)k * TBm + t];
-          if (j < 0) continue;
-          const auto& rows = g->col_rows[j];
-          for (int d = 0; d < (int)rows.size(); ++d) {
-            const int vs = k < VPLm - 1 ? (ecnt(k) + d) * TBm + t : bp->m2v_vlast + d * bp->m2v_nl + t;
-            roff[rows[d]].push_back((uint32_t)vs * 8u);
-          }
-        }
-      for (int i = 0; i < g->m; ++i) {
-        if (roff[i].size() > 7) return fail(set_err(QLDPC_ENOTSUP, "m2v row wider than 7"));
-        while (roff[i].size() < 8) roff[i].push_back(sent);
-      }
-      // The check phase gathers entry e of its rows with one ds_read_b64 per e: 32-lane groups,
-      // bank pair = slot mod 32 (MI355X_MICROARCH.md §LDS).  The order of a row's entries is
-      // free: per group of 32 rows, a seeded local search swaps two entries of a row whenever that
-      // does not raise Σ_e Σ_bank count² (the sentinel broadcasts: not counted).  Host work only.
-      if (env_int("QLDPC_M2V_ORDER", 1) != 0) {
-        uint64_t rs = 0x9E3779B97F4A7C15ull;
-        auto rnd = [&]() { rs ^= rs << 13; rs ^= rs >> 7; rs ^= rs << 17; return rs; };
-        for (int q = 0; q < 4; ++q)
-          for (int g0 = 0; g0 < TBm; g0 += 32) {
-            std::vector<int> rr;
-            for (int l = 0; l < 32; ++l)
-              if (q * TBm + g0 + l < g->m) rr.push_back(q * TBm + g0 + l);
-            if (rr.size() < 2) continue;
-            int cnt[7][32] = {{0}};
-            auto bk = [&](uint32_t o) { return (int)((o / 8u) % 32u); };
-            for (int i : rr)
-              for (int e = 0; e < 7; ++e)
-                if (roff[i][e] != sent) cnt[e][bk(roff[i][e])]++;
-            for (int it = 0; it < 4000; ++it) {
-              const int i = rr[rnd() % rr.size()], a = (int)(rnd() % 7), b = (int)(rnd() % 7);
-              const uint32_t oa = roff[i][a], ob = roff[i][b];
-              if (a == b || oa == ob) continue;
-              auto term = [&](int e, uint32_t o, int dlt) {  // change of count^2 when o enters (+1) / leaves (-1) e
-                if (o == sent) return 0;
-                const int c = cnt[e][bk(o)];
-                return dlt > 0 ? 2 * c + 1 : -(2 * c - 1);
-              };
-              int d = term(a, oa, -1);
-              if (oa != sent) cnt[a][bk(oa)]--;
-              d += term(b, ob, -1);
-              if (ob != sent) cnt[b][bk(ob)]--;
-              d += term(a, ob, +1);
-              if (ob != sent) cnt[a][bk(ob)]++;
-              d += term(b, oa, +1);
-              if (oa != sent) cnt[b][bk(oa)]++;
-              if (d <= 0) {
-                roff[i][a] = ob;
-                roff[i][b] = oa;
-              } else {  // undo
-                if (ob != sent) cnt[a][bk(ob)]--;
-                if (oa != sent) cnt[b][bk(oa)]--;
-                if (oa != sent) cnt[a][bk(oa)]++;
-                if (ob != sent) cnt[b][bk(ob)]++;
-              }
-            }
-          }
-      }
-      std::vector<uint32_t> tab((size_t)4 * TBm * 4, 0);
-      for (int q = 0; q < 4; ++q)
-        for (int t = 0; t < TBm; ++t) {
-          const int i = q * TBm + t;
-          uint32_t o[8];
-          for (int e = 0; e < 8; ++e) o[e] = i < g->m ? roff[i][e] : sent;
-          for (int w = 0; w < 4; ++w) tab[((size_t)q * TBm + t) * 4 + w] = o[2 * w] | (o[2 * w + 1] << 16);
-        }
-      if ((rc = bp->rowtab.alloc(tab.size() * 4))) return fail(rc);
-      if (hipMemcpy(bp->rowtab.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
-        return fail(set_err(QLDPC_EHIP, "upload m2v row table"));
-    }
-    kern = slot_variant(bp->engine, precision, DM, bp->NS, bp->VPL, bp->d3k, bp->ea_shift, bp->TB, bp->nch, bp->tail,
-                        bp->m2s, bp->fb, bp->d2k, bp->m2s_pk).dec_k;
-    if (bp->engine >= 3) {
-      // row degrees by check label: engine 4 keeps them in F, engine 3 their parity (bp_reg.h, w domain)
-      std::vector<uint8_t> deg(std::max(1, g->m));
-      for (int i = 0; i < g->m; ++i) deg[lab.empty() ? i : lab[i]] = (uint8_t)(g->row_ptr[i + 1] - g->row_ptr[i]);
-      if ((rc = bp->rdeg.alloc(deg.size()))) return fail(rc);
-      if (hipMemcpy(bp->rdeg.p, deg.data(), deg.size(), hipMemcpyHostToDevice) != hipSuccess)
-        return fail(set_err(QLDPC_EHIP, "upload row degrees"));
-    }
+    if ((r.m2s == 3 && (rc = upload(bp->rowtab, T.rowtab.data(), T.rowtab.size() * 4, "upload m2v row table"))) ||
+        (r.engine >= 3 && (rc = upload(bp->rdeg, T.rdeg.data(), T.rdeg.size(), "upload row degrees"))) ||
+        (rc = upload(bp->vchk, T.edges.data(), T.edges.size() * 4, "upload edge table")) ||
+        (!bp->slot_var.empty() && (rc = upload(bp->perm, bp->slot_var.data(), bp->slot_var.size() * 4, "upload slot map"))) ||
+        (rc = bp->llr.alloc((size_t)r.VPL * r.TB * tsize)))
+      return fail(rc);
+    kern = r.engine == 1 ? get_variant(precision, r.VPL, r.DMAX).dec_k : slot_variant(r).dec_k;
   }
-  if (!kern && (bp->engine == 3 || bp->engine == 4) && env_int("QLDPC_HBM_FALLBACK", 1) != 0) {
-    // no kernel compiled for this engine-3/4 geometry (e.g. fp32 images past 64 KiB at 8 variables per
-    // thread, GenBicycleA4 over five rounds): the HBM-resident engine serves any graph
-    bp->tail = bp->m2s = bp->fb = bp->m2s_pk = bp->vslots_dummy = bp->d3k = bp->d2k = 0;
-    bp->nw = bp->live_last = 0;
-    bp->rperm.release();
-    bp->rowtab.release();
-    bp->rdeg.release();
-    return setup_hbm();
-  }
-  if (!kern) return fail(set_err(QLDPC_ENOTSUP, "no kernel variant"));
-  if ((rc = bp->vchk.alloc(vchk.size() * 4)) || (rc = bp->llr.alloc((size_t)bp->VPL * bp->TB * tsize))) return fail(rc);
-  if (hipMemcpy(bp->vchk.p, vchk.data(), vchk.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
-    return fail(set_err(QLDPC_EHIP, "upload edge table"));
   if ((rc = upload_llr(bp))) return fail(rc);
-  if (!bp->slot_var.empty()) {
-    if ((rc = bp->perm.alloc(bp->slot_var.size() * 4))) return fail(rc);
-    if (hipMemcpy(bp->perm.p, bp->slot_var.data(), bp->slot_var.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
-      return fail(set_err(QLDPC_EHIP, "upload slot map"));
-  }
   int nb = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, bp->TB, bp->lds_bytes) != hipSuccess) nb = 1;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, r.TB, r.lds_bytes) != hipSuccess) nb = 1;
   bp->blocks_per_cu = std::max(1, nb);
   if ((rc = device_cus(g->device, bp->cus))) return fail(rc);
   bp1_prepare(bp);
   *out = bp;
+  return 0;
+}
+
+int qldpc_bp_plan(const qldpc_graph* g, const double* channel_probs, int32_t bp_method, int32_t precision,
+                  int32_t vars_per_thread, int32_t min_col_slots, int32_t* out, int32_t out_len) {
+  if (!out || out_len < 8) return set_err(QLDPC_EINVAL, "out needs 8 entries");
+  int rc = validate_create(g, channel_probs, precision, bp_method);
+  if (rc) return rc;
+  if (bp_method == QLDPC_PRODUCT_SUM) return set_err(QLDPC_ENOTSUP, "the product-sum geometry needs the device");
+  Route r;
+  std::vector<int32_t> slot_var;
+  if ((rc = plan_route(g, !QLDPC_M2S_UNIL || uniform_priors(channel_probs, g->n), precision, vars_per_thread,
+                       min_col_slots, 0, r, slot_var)))
+    return rc;
+  const int32_t v[8] = {r.engine, route_kernel_id(r), r.nch, r.TB, r.VPL, r.lds_bytes, r.engine == 3 ? r.d3k : 0,
+                        r.engine == 3 ? r.d2k : 0};
+  std::copy(v, v + 8, out);
   return 0;
 }
 
@@ -1659,11 +1697,9 @@ int qldpc_bp_destroy(qldpc_bp* bp) {
 
 int qldpc_bp_set_channel_probs(qldpc_bp* bp, const double* channel_probs) {
   if (!bp || !channel_probs) return set_err(QLDPC_EINVAL, "NULL argument");
-  if (bp->m2s && QLDPC_M2S_UNIL)
-    for (int j = 1; j < bp->g->n; ++j)
-      if (channel_probs[j] != channel_probs[0])
-        return set_err(QLDPC_ENOTSUP, "this decoder's kernels hold one uniform prior: create a new decoder for "
-                                      "non-uniform channel_probs");
+  if (bp->route.m2s && QLDPC_M2S_UNIL && !uniform_priors(channel_probs, bp->g->n))
+    return set_err(QLDPC_ENOTSUP, "this decoder's kernels hold one uniform prior: create a new decoder for "
+                                  "non-uniform channel_probs");
   bp->probs.assign(channel_probs, channel_probs + bp->g->n);
   const int rc = upload_llr(bp);
   if (rc) return rc;
@@ -1673,7 +1709,7 @@ int qldpc_bp_set_channel_probs(qldpc_bp* bp, const double* channel_probs) {
 
 int qldpc_bp_degree3_slots(const qldpc_bp* bp, int32_t* d3k) {
   if (!bp || !d3k) return set_err(QLDPC_EINVAL, "NULL argument");
-  *d3k = bp->engine == 3 ? bp->d3k : 0;
+  *d3k = bp->route.engine == 3 ? bp->route.d3k : 0;
   return 0;
 }
 
@@ -1693,31 +1729,20 @@ int qldpc_m2s_place_model(const qldpc_graph* g, int32_t anneal_iters, int64_t* o
     if (d != 3 && d != 4) return set_err(QLDPC_ENOTSUP, "m2s placement model: column degrees 3 / 4 only");
     n3 += d == 3;
   }
-  int TB = 0, VPL = 0;
-  if (g->max_row < 1 || g->max_row > 7 || choose_rgeometry(g->n, g->m, 0, TB, VPL) || TB > 256 || VPL < 4 || VPL > 8 ||
-      !(n3 % TB == 0 || n3 == g->n))
+  Route r;  // the m2s route of admit_m2s at the default geometry
+  r.engine = 3;
+  r.tail = r.m2s = 1;
+  r.nch = 3;
+  if (g->max_row < 1 || g->max_row > 7 || choose_rgeometry(g->n, g->m, 0, r.TB, r.VPL) || r.TB > 256 || r.VPL < 4 ||
+      r.VPL > 8 || !(n3 % r.TB == 0 || n3 == g->n))
     return set_err(QLDPC_ENOTSUP, "graph outside the m2s envelope (rows <= 7, <= 256 threads x 4-8 slots)");
-  std::vector<int32_t> slot_var((size_t)VPL * TB, -1);
-  int p = 0;
-  for (int c = 0; c < 2; ++c)
-    for (int j = 0; j < g->n; ++j)
-      if (((int)g->col_rows[j].size() <= 3 ? 0 : 1) == c) slot_var[p++] = j;
-  int d3k = 0;
-  for (int k = 0; k < VPL; ++k) {
-    bool ok = true;
-    for (int t = 0; t < TB && ok; ++t) {
-      const int j = slot_var[(size_t)k * TB + t];
-      ok = j < 0 || (int)g->col_rows[j].size() <= 3;
-    }
-    if (!ok) break;
-    d3k = k + 1;
-  }
-  const int vslots = (1 + g->m * 3) * 2;
-  const uint32_t vbase = (uint32_t)r_layout(3, vslots, g->m, 8, 1, 1).v;
+  std::vector<int32_t> slot_var = degree_sorted(g, {3});
+  slot_var.resize((size_t)r.VPL * r.TB, -1);
+  r.d3k = leading_slots(g, slot_var, r.TB, r.VPL, 3);
+  const uint32_t vbase = route_layout(r, route_vslots(r, g->m), g->m).v;
   std::vector<uint32_t> edges;
-  build_slot_edges(g, TB, VPL, 4, 8, 3, slot_var, edges, (int)(vbase / 4), {}, 1, 1, d3k, -1, nullptr, 1,
-                   anneal_iters);
-  lds_model_var_phase(edges, TB, VPL, 4, d3k, vbase, true, out6);
+  build_slot_edges(g, r, slot_var, edges, (int)(vbase / 4), {}, 1, -1, nullptr, 1, anneal_iters);
+  lds_model_var_phase(edges, r, vbase, out6);
   return 0;
 }
 
@@ -1730,39 +1755,23 @@ int qldpc_bp_bank_stats(const qldpc_bp* bp, int32_t* before, int32_t* after) {
 
 int qldpc_bp_kernel_id(const qldpc_bp* bp, int32_t* kernel_id, int32_t* row_chunks) {
   if (!bp) return set_err(QLDPC_EINVAL, "NULL decoder");
-  int id = bp->engine;
-  if (bp->engine == 3) {
-    if (bp->m2s)
-      id = bp->m2s == 2 ? 31103 : bp->m2s == 3 ? 40103 : (bp->tail && bp->nch == 4) ? 11313 + 100000 * std::min(bp->d2k, 1)
-           : bp->tail ? 11103 : bp->m2s_pk ? 10203 : 10103;
-    else if (bp->fb)
-      id = 21013 + ((bp->d3k >= 8 && bp->d2k > 0) ? 100000 * std::min(bp->d2k, 4) : 0);  // + D2K digit
-    else if (bp->tail)
-      id = 1013 + ((bp->precision == 64 && bp->VPL == 6 && bp->d2k >= 1 && bp->d3k >= 1) ? 100000 : 0);
-    else if (use_f64w(bp->engine, bp->precision, bp->DMAX, bp->TB, bp->VPL, bp->ea_shift, bp->nch))
-      id = 103;
-    else if (use_f64x(bp->engine, bp->precision, bp->DMAX, bp->TB, bp->VPL, bp->ea_shift))
-      id = 303;
-    else if (bp->ea_shift == 2)
-      id = 13;
-  }
-  if (kernel_id) *kernel_id = id;
-  if (row_chunks) *row_chunks = bp->nch;
+  if (kernel_id) *kernel_id = route_kernel_id(bp->route);
+  if (row_chunks) *row_chunks = bp->route.nch;
   return 0;
 }
 
 int qldpc_bp_engine(const qldpc_bp* bp, int32_t* engine) {
   if (!bp || !engine) return set_err(QLDPC_EINVAL, "NULL argument");
-  *engine = bp->engine;
+  *engine = bp->route.engine;
   return 0;
 }
 
 int qldpc_bp_geometry(const qldpc_bp* bp, int32_t* threads, int32_t* vpl, int32_t* lds_bytes,
                       int32_t* blocks_per_cu) {
   if (!bp) return set_err(QLDPC_EINVAL, "NULL decoder");
-  if (threads) *threads = bp->TB;
-  if (vpl) *vpl = bp->VPL;
-  if (lds_bytes) *lds_bytes = bp->lds_bytes;
+  if (threads) *threads = bp->route.TB;
+  if (vpl) *vpl = bp->route.VPL;
+  if (lds_bytes) *lds_bytes = bp->route.lds_bytes;
   if (blocks_per_cu) *blocks_per_cu = bp->blocks_per_cu;
   return 0;
 }
@@ -1788,20 +1797,20 @@ static SSector ssector_of(const qldpc_bp* bp, const unsigned long long* lmask, i
   s.rdeg = static_cast<const uint8_t*>(bp->rdeg.p);
   s.perm = static_cast<const int32_t*>(bp->perm.p);
   s.rperm = static_cast<const int32_t*>(bp->rperm.p);
-  s.d3k = bp->d3k;
+  s.d3k = bp->route.d3k;
   s.m = bp->g->m;
   s.n = bp->g->n;
   s.kw = kw;
   s.max_iter = bp->max_iter;
-  s.nch = bp->nch;
-  s.vpl = bp->VPL;
+  s.nch = bp->route.nch;
+  s.vpl = bp->route.VPL;
   s.alpha = bp->alpha;
   s.rows = static_cast<const uint32_t*>(bp->rowtab.p);
-  s.vlast = bp->m2v_vlast;
-  s.vnl = bp->m2v_nl;
+  s.vlast = bp->route.m2v_vlast;
+  s.vnl = bp->route.m2v_nl;
   s.npos = bp->npos > 0 ? bp->npos : bp->g->n;
-  s.nw = bp->nw;
-  s.live_last = bp->live_last;
+  s.nw = bp->route.nw;
+  s.live_last = bp->route.live_last;
   return s;
 }
 
@@ -1827,7 +1836,7 @@ int qldpc_bp_decode_batch_soft(qldpc_bp* bp, const uint8_t* d_synd, uint8_t* d_c
   if (!bp || (B > 0 && !d_post)) return set_err(QLDPC_EINVAL, "NULL argument");
   // engine 1 (min-sum, qldpc_bp_create_soft) or engine 5 (product-sum: any qldpc_bp_create decoder with
   // bp_method 0 writes ldpc's log_prob_ratios on request)
-  if (bp->engine != 1 && bp->engine != 5)
+  if (bp->route.engine != 1 && bp->route.engine != 5)
     return set_err(QLDPC_ENOTSUP, "soft output needs a decoder from qldpc_bp_create_soft (min-sum) or a product-sum decoder");
   return decode_batch(bp, d_synd, d_corr, d_iters, d_conv, d_post, B, stream);
 }
@@ -1842,10 +1851,10 @@ static int decode_batch(qldpc_bp* bp, const uint8_t* d_synd, uint8_t* d_corr, in
   // with every engine); QLDPC_BP1=0 keeps the engine
   // (built with the decoder and on every qldpc_bp_set_channel_probs, bp1_prepare: no uploads here)
   if (!d_post && bp->bp1) return qldpc_rt::bp1_decode(bp->bp1, d_synd, d_corr, d_iters, d_conv, B, (hipStream_t)stream);
-  if (bp->engine == 5) return ps_decode_launch(bp, d_synd, d_corr, d_iters, d_conv, B, (hipStream_t)stream, d_post);
-  if (bp->engine == 6) return hbm_decode_launch(bp, d_synd, d_corr, d_iters, d_conv, B, (hipStream_t)stream);
+  if (bp->route.engine == 5) return ps_decode_launch(bp, d_synd, d_corr, d_iters, d_conv, B, (hipStream_t)stream, d_post);
+  if (bp->route.engine == 6) return hbm_decode_launch(bp, d_synd, d_corr, d_iters, d_conv, B, (hipStream_t)stream);
   const long long cap = (long long)bp->blocks_per_cu * bp->cus;
-  if (bp->engine == 1) {
+  if (bp->route.engine == 1) {
     DecArgs a;
     a.sec = sector_of(bp, nullptr, 0);
     a.synd = d_synd;
@@ -1855,10 +1864,10 @@ static int decode_batch(qldpc_bp* bp, const uint8_t* d_synd, uint8_t* d_corr, in
     a.post = d_post;
     a.B = B;
     const int grid = (int)std::max<long long>(1, std::min<long long>(B, cap));
-    Variant v = get_variant(bp->precision, bp->VPL, bp->DMAX);
-    QLDPC_HIP(v.dec(dim3(grid), dim3(bp->TB), bp->lds_bytes, (hipStream_t)stream, a));
+    Variant v = get_variant(bp->route.precision, bp->route.VPL, bp->route.DMAX);
+    QLDPC_HIP(v.dec(dim3(grid), dim3(bp->route.TB), bp->route.lds_bytes, (hipStream_t)stream, a));
   } else {
-    const int tsize = bp->precision == 32 ? 4 : 8;
+    const int tsize = bp->route.precision == 32 ? 4 : 8;
     SDecArgs a;
     a.sec = ssector_of(bp, nullptr, 0);
     a.synd = d_synd;
@@ -1867,16 +1876,16 @@ static int decode_batch(qldpc_bp* bp, const uint8_t* d_synd, uint8_t* d_corr, in
     a.conv = d_conv;
     a.B = B;
     a.mmax = bp->g->m;
-    a.vslots = bp->vslots_m2v ? bp->vslots_m2v : (1 + bp->g->m * bp->nch) * (16 / tsize) + bp->vslots_dummy;
+    a.vslots = route_vslots(bp->route, bp->g->m);
     a.img_bytes = (int)slot_img_bytes(a.vslots, a.mmax, tsize);
-    a.chunk = chunk_for(B, cap, bp->NS);
+    a.chunk = chunk_for(B, cap, bp->route.NS);
     a.work = nullptr;
 #if QLDPC_STAMPS
     a.stamps = debug_stamps_buffer();
 #else
     a.stamps = nullptr;
 #endif
-    if (bp->engine >= 3 && env_int("QLDPC_DYN", 1) != 0) {  // chunk queue, ~64 chunks per workgroup
+    if (bp->route.engine >= 3 && env_int("QLDPC_DYN", 1) != 0) {  // chunk queue, ~64 chunks per workgroup
       if (!bp->work.p && bp->work.alloc(16)) return QLDPC_ENOMEM;
       // at most kMaxQueuePops pops of the one queue counter per launch: small graphs run many
       // workgroups per CU and decode a syndrome in microseconds, and 65,536 one-syndrome pops of one
@@ -1890,9 +1899,8 @@ static int decode_batch(qldpc_bp* bp, const uint8_t* d_synd, uint8_t* d_corr, in
     }
     const long long nchunks = (B + a.chunk - 1) / a.chunk;
     const int grid = (int)std::max<long long>(1, std::min<long long>(nchunks, cap));
-    SVariant v = slot_variant(bp->engine, bp->precision, bp->DMAX, bp->NS, bp->VPL, bp->d3k, bp->ea_shift, bp->TB, bp->nch,
-                              bp->tail, bp->m2s, bp->fb, bp->d2k, bp->m2s_pk);
-    QLDPC_HIP(v.dec(dim3(grid), dim3(bp->TB), bp->lds_bytes, (hipStream_t)stream, a));
+    SVariant v = slot_variant(bp->route);
+    QLDPC_HIP(v.dec(dim3(grid), dim3(bp->route.TB), bp->route.lds_bytes, (hipStream_t)stream, a));
   }
   return 0;
 }
@@ -1920,18 +1928,18 @@ int qldpc_mc_create(qldpc_bp* dec_x, const qldpc_graph* logical_x, qldpc_bp* dec
                     qldpc_mc** out) {
   if (!out || (!dec_x && !dec_z)) return set_err(QLDPC_EINVAL, "need at least one sector decoder");
   qldpc_bp* d0 = dec_x ? dec_x : dec_z;
-  const bool staged = (dec_x && dec_x->engine >= 5) || (dec_z && dec_z->engine >= 5) ||
+  const bool staged = (dec_x && dec_x->route.engine >= 5) || (dec_z && dec_z->route.engine >= 5) ||
                       // (the space-time tail families, two-word or one-word: decode_batch kernels only)
-                      (dec_x && dec_x->tail && (!dec_x->m2s || dec_x->nch == 4)) ||
-                      (dec_z && dec_z->tail && (!dec_z->m2s || dec_z->nch == 4)) ||
+                      (dec_x && dec_x->route.tail && (!dec_x->route.m2s || dec_x->route.nch == 4)) ||
+                      (dec_z && dec_z->route.tail && (!dec_z->route.m2s || dec_z->route.nch == 4)) ||
                       // the fused kernel runs one layout family for both sectors
                       (dec_x && dec_z &&
-                       (dec_x->m2s != dec_z->m2s || dec_x->tail != dec_z->tail || dec_x->fb != dec_z->fb ||
-                        dec_x->m2s_pk != dec_z->m2s_pk)) ||
+                       (dec_x->route.m2s != dec_z->route.m2s || dec_x->route.tail != dec_z->route.tail || dec_x->route.fb != dec_z->route.fb ||
+                        dec_x->route.m2s_pk != dec_z->route.m2s_pk)) ||
                       // one-slot families (m2s / c2s / m2v) keep no dummy edge on a real variable:
                       // the kernel's compile-time D3K must be each sector's own (a degree-3
                       // variable past it would run the 4-edge path and read the shared dummy slot)
-                      (dec_x && dec_z && dec_x->m2s && dec_x->d3k != dec_z->d3k) ||
+                      (dec_x && dec_z && dec_x->route.m2s && dec_x->route.d3k != dec_z->route.d3k) ||
                       env_int("QLDPC_MC_STAGED", 0) == 1;
   if (staged) {  // staged pipeline around decode_batch (staged.hip): any decoder pair
     if (dec_x && dec_z && (dec_x->g->n != dec_z->g->n || dec_x->g->device != dec_z->g->device))
@@ -1940,10 +1948,7 @@ int qldpc_mc_create(qldpc_bp* dec_x, const qldpc_graph* logical_x, qldpc_bp* dec
     auto* mc = new qldpc_mc();
     mc->dec[0] = dec_x;
     mc->dec[1] = dec_z;
-    mc->engine = d0->engine;
-    mc->precision = d0->precision;
-    mc->TB = d0->TB;
-    mc->VPL = d0->VPL;
+    mc->route = d0->route;
     int rc = mc->counters.alloc(sizeof(qldpc_counters));
     if (!rc) rc = staged_mc_prepare(mc, logical_x, logical_z);
     if (rc) {
@@ -1957,11 +1962,11 @@ int qldpc_mc_create(qldpc_bp* dec_x, const qldpc_graph* logical_x, qldpc_bp* dec
   }
   if (dec_x && dec_z) {
     if (dec_x->g->n != dec_z->g->n) return set_err(QLDPC_EINVAL, "sector code lengths differ");
-    if (dec_x->TB != dec_z->TB || dec_x->VPL != dec_z->VPL || dec_x->DMAX != dec_z->DMAX ||
-        dec_x->precision != dec_z->precision || dec_x->engine != dec_z->engine)
+    if (dec_x->route.TB != dec_z->route.TB || dec_x->route.VPL != dec_z->route.VPL || dec_x->route.DMAX != dec_z->route.DMAX ||
+        dec_x->route.precision != dec_z->route.precision || dec_x->route.engine != dec_z->route.engine)
       return set_err(QLDPC_EINVAL, "sector decoders need identical geometry/precision (same vars_per_thread)");
     if (dec_x->g->device != dec_z->g->device) return set_err(QLDPC_EINVAL, "sector decoders on different devices");
-    if (dec_x->m2s != dec_z->m2s || dec_x->tail != dec_z->tail || dec_x->fb != dec_z->fb)
+    if (dec_x->route.m2s != dec_z->route.m2s || dec_x->route.tail != dec_z->route.tail || dec_x->route.fb != dec_z->route.fb)
       return set_err(QLDPC_EINVAL, "sector decoders use different LDS layouts (QLDPC_M2S)");
   }
   QLDPC_HIP(hipSetDevice(d0->g->device));
@@ -1979,52 +1984,41 @@ int qldpc_mc_create(qldpc_bp* dec_x, const qldpc_graph* logical_x, qldpc_bp* dec
   int rc = 0;
   if (dec_x && (rc = build_lmask(logical_x, dec_x->g->n, mc->lmask[0], mc->kw[0]))) return fail(rc);
   if (dec_z && (rc = build_lmask(logical_z, dec_z->g->n, mc->lmask[1], mc->kw[1]))) return fail(rc);
-  mc->engine = d0->engine;
-  mc->TB = d0->TB;
-  mc->VPL = d0->VPL;
-  mc->DMAX = d0->DMAX;
-  mc->ea_shift = std::max(dec_x ? dec_x->ea_shift : 0, dec_z ? dec_z->ea_shift : 0);
-  if (dec_x && dec_z && dec_x->ea_shift != dec_z->ea_shift)
+  // the sectors' common route: one kernel serves both
+  mc->route = d0->route;
+  if (dec_x && dec_z && dec_x->route.ea_shift != dec_z->route.ea_shift)
     return fail(set_err(QLDPC_EINVAL, "sector decoders use different LDS address scales"));
-  // one kernel serves both sectors: only slots that hold degree <= 3 variables in both skip slot 4
-  mc->d3k = std::min(dec_x ? dec_x->d3k : 1 << 20, dec_z ? dec_z->d3k : 1 << 20);
-  mc->precision = d0->precision;
-  // compile-time row width (fp64 <= 256-thread family): one kernel serves both sectors
-  mc->nch = d0->nch;
-  if (dec_x && dec_z && dec_x->nch != dec_z->nch) mc->nch = 0;
+  // only slots that hold degree <= 3 variables in both sectors skip slot 4; the fused kernels have no D2K
+  mc->route.d3k = std::min(dec_x ? dec_x->route.d3k : 1 << 20, dec_z ? dec_z->route.d3k : 1 << 20);
+  mc->route.d2k = 0;
+  // compile-time row width (fp64 <= 256-thread family)
+  if (dec_x && dec_z && dec_x->route.nch != dec_z->route.nch) mc->route.nch = 0;
   mc->mmax = std::max(dec_x ? dec_x->g->m : 0, dec_z ? dec_z->g->m : 0);
-  mc->tail = d0->tail;
-  mc->m2s = d0->m2s;
-  mc->m2s_pk = d0->m2s_pk;
-  mc->fb = d0->fb;
   const void* kern;
-  if (mc->engine == 1) {
-    mc->lds_bytes = (int)lds_for(mc->precision, mc->mmax);
-    kern = get_variant(mc->precision, mc->VPL, mc->DMAX).mc_k;
+  if (mc->route.engine == 1) {
+    mc->route.lds_bytes = (int)lds_for(mc->route.precision, mc->mmax);
+    kern = get_variant(mc->route.precision, mc->route.VPL, mc->route.DMAX).mc_k;
   } else {
-    const int tsize = mc->precision == 32 ? 4 : 8;
+    const int tsize = mc->route.precision == 32 ? 4 : 8;
     for (qldpc_bp* d : {dec_x, dec_z})
       if (d)
-        mc->vslots = std::max(mc->vslots,
-                              d->vslots_m2v ? d->vslots_m2v : (1 + d->g->m * d->nch) * (16 / tsize) + d->vslots_dummy);
+        mc->vslots = std::max(mc->vslots, route_vslots(d->route, d->g->m));
     mc->img_bytes = (int)slot_img_bytes(mc->vslots, mc->mmax, tsize);
-    if (mc->engine >= 3) {
-      if (!r_fits(mc->engine, mc->vslots, mc->mmax, tsize, mc->ea_shift, mc->tail, mc->m2s, mc->fb))
+    if (mc->route.engine >= 3) {
+      if (!route_fits(mc->route, mc->vslots, mc->mmax))
         return fail(set_err(QLDPC_ENOTSUP, "sector images exceed the register engines' 64 KiB addressing (QLDPC_ENGINE=2)"));
-      mc->NS = 1;
-      mc->lds_bytes =
-          (int)r_lds_bytes((int)r_layout(mc->engine, mc->vslots, mc->mmax, tsize, mc->tail, mc->m2s, mc->fb).total, kChunkMax);
+      mc->route.NS = 1;
+      mc->route.lds_bytes = (int)route_lds(mc->route, mc->vslots, mc->mmax);
     } else {
-      mc->NS = choose_ns(mc->img_bytes);
-      mc->lds_bytes = (int)slot_lds_bytes(mc->NS, mc->img_bytes, kChunkMax);
+      mc->route.NS = choose_ns(mc->img_bytes);
+      mc->route.lds_bytes = (int)slot_lds_bytes(mc->route.NS, mc->img_bytes, kChunkMax);
     }
-    kern = slot_variant(mc->engine, mc->precision, mc->DMAX, mc->NS, mc->VPL, mc->d3k, mc->ea_shift, mc->TB, mc->nch,
-                        mc->tail, mc->m2s, mc->fb, 0, mc->m2s_pk).mc_k;
+    kern = slot_variant(mc->route).mc_k;
   }
-  if (mc->lds_bytes > kLdsMax) return fail(set_err(QLDPC_ENOTSUP, "per-shot LDS image exceeds 160 KiB"));
+  if (mc->route.lds_bytes > kLdsMax) return fail(set_err(QLDPC_ENOTSUP, "per-shot LDS image exceeds 160 KiB"));
   if (!kern) return fail(set_err(QLDPC_ENOTSUP, "no kernel variant"));
   int nb = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, mc->TB, mc->lds_bytes) != hipSuccess) nb = 1;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, mc->route.TB, mc->route.lds_bytes) != hipSuccess) nb = 1;
   mc->blocks_per_cu = std::max(1, nb);
   mc->cus = d0->cus;
   if ((rc = mc->counters.alloc(sizeof(qldpc_counters))) || (rc = mc->work.alloc(16))) return fail(rc);
@@ -2037,7 +2031,7 @@ int qldpc_mc_set_osd(qldpc_mc* mc, qldpc_osd_gpu* osd_x, qldpc_osd_gpu* osd_z) {
   qldpc_osd_gpu* o[2] = {osd_x, osd_z};
   for (int q = 0; q < 2; ++q) {
     if (!o[q]) continue;
-    if (mc->staged || mc->engine != 3)
+    if (mc->staged || mc->route.engine != 3)
       return set_err(QLDPC_ENOTSUP, "BP+OSD shot loop needs the fused engine-3 MC kernel");
     if (!mc->dec[q] || !osd_gpu_matches(o[q], mc->dec[q]->g))
       return set_err(QLDPC_EINVAL, q == 0 ? "X-sector OSD handle was built on a different graph than dec_x"
@@ -2092,7 +2086,7 @@ int qldpc_mc_launch(qldpc_mc* mc, double px, double py, double pz, uint64_t seed
                             d_err, d_corr, d_iters, (hipStream_t)stream);
   }
   QLDPC_HIP(hipSetDevice((mc->dec[0] ? mc->dec[0] : mc->dec[1])->g->device));
-  const bool bposd = mc->engine != 1 && ((need[0] && mc->osd[0]) || (need[1] && mc->osd[1]));
+  const bool bposd = mc->route.engine != 1 && ((need[0] && mc->osd[0]) || (need[1] && mc->osd[1]));
   if (bposd) {
     // capture slots per sector, bounded by a memory budget (QLDPC_OSD_CAPTURE_MB per sector,
     // default 2048); a launch larger than that runs as pieces of at most c_cap shots, each
@@ -2121,7 +2115,7 @@ int qldpc_mc_launch(qldpc_mc* mc, double px, double py, double pz, uint64_t seed
   const long long cap = (long long)mc->blocks_per_cu * mc->cus;
   // thresholds of the 3-way split, in the evaluation order of src/Simulators.py:102-108
   const double t1 = pz, t2 = pz + px, t3 = (pz + px) + py;
-  if (mc->engine == 1) {
+  if (mc->route.engine == 1) {
     McArgs a;
     std::memset(&a, 0, sizeof(a));
     for (int q = 0; q < 2; ++q) {
@@ -2139,8 +2133,8 @@ int qldpc_mc_launch(qldpc_mc* mc, double px, double py, double pz, uint64_t seed
     a.fail = d_fail; a.err = d_err; a.corr = d_corr; a.iters = d_iters;
     long long grid = grid_blocks > 0 ? grid_blocks : cap;
     grid = std::max<long long>(1, std::min<long long>(grid, shot_count));
-    Variant v = get_variant(mc->precision, mc->VPL, mc->DMAX);
-    QLDPC_HIP(v.mc(dim3((unsigned)grid), dim3(mc->TB), mc->lds_bytes, (hipStream_t)stream, a));
+    Variant v = get_variant(mc->route.precision, mc->route.VPL, mc->route.DMAX);
+    QLDPC_HIP(v.mc(dim3((unsigned)grid), dim3(mc->route.TB), mc->route.lds_bytes, (hipStream_t)stream, a));
   } else {
     SMcArgs a;
     std::memset(&a, 0, sizeof(a));
@@ -2157,9 +2151,9 @@ int qldpc_mc_launch(qldpc_mc* mc, double px, double py, double pz, uint64_t seed
     a.vslots = mc->vslots;
     a.img_bytes = mc->img_bytes;
     const long long want = grid_blocks > 0 ? grid_blocks : cap;
-    a.chunk = chunk_for(shot_count, want, mc->NS);
+    a.chunk = chunk_for(shot_count, want, mc->route.NS);
     // engine 3: chunks from a queue, ~64 per workgroup (no tail behind the slowest static share)
-    if (mc->engine >= 3 && mc->work.p && env_int("QLDPC_DYN", 1) != 0) {
+    if (mc->route.engine >= 3 && mc->work.p && env_int("QLDPC_DYN", 1) != 0) {
       const int per = std::max(1, env_int("QLDPC_DYN_PER", 64));  // measured plateau 64-128 (n1600)
       a.chunk = (int)std::max<long long>(1, std::min<long long>(kChunkMax, shot_count / (want * per)));
       QLDPC_HIP(hipMemsetAsync(mc->work.p, 0, 4, (hipStream_t)stream));
@@ -2181,10 +2175,10 @@ int qldpc_mc_launch(qldpc_mc* mc, double px, double py, double pz, uint64_t seed
     // second (SMcArgs::cls_cache; [grid][chunk][TB] u16, one Philox draw per (shot, variable) instead of
     // two; QLDPC_CLS_CACHE=0 draws in both passes)
     a.cls_cache = nullptr;
-    const size_t cc_need = (size_t)grid * (size_t)a.chunk * (size_t)mc->TB * 2;
+    const size_t cc_need = (size_t)grid * (size_t)a.chunk * (size_t)mc->route.TB * 2;
     // (bounded: 256 MiB covers every bundled code at the bench's launch sizes; huge launches of small
     // codes, e.g. 10^9 shots of GenBicycleA1 at 1024-shot chunks, would need ~0.7 GB: they draw twice)
-    if (a.nsec == 2 && !d_uniforms && mc->VPL <= 8 && env_int("QLDPC_CLS_CACHE", 1) != 0 && cc_need <= (256u << 20)) {
+    if (a.nsec == 2 && !d_uniforms && mc->route.VPL <= 8 && env_int("QLDPC_CLS_CACHE", 1) != 0 && cc_need <= (256u << 20)) {
       const size_t need = cc_need;
       if (mc->cls_cache.bytes < need) {
         mc->cls_cache.release();
@@ -2224,9 +2218,8 @@ int qldpc_mc_launch(qldpc_mc* mc, double px, double py, double pz, uint64_t seed
       }
       if (!a.fail) a.fail = static_cast<uint8_t*>(mc->c_fail.p);  // per-shot verdicts the OSD stage revises
     }
-    SVariant v = slot_variant(mc->engine, mc->precision, mc->DMAX, mc->NS, mc->VPL, mc->d3k, mc->ea_shift, mc->TB, mc->nch,
-                              mc->tail, mc->m2s, mc->fb, 0, mc->m2s_pk);
-    QLDPC_HIP(v.mc(dim3((unsigned)grid), dim3(mc->TB), mc->lds_bytes, st, a));
+    SVariant v = slot_variant(mc->route);
+    QLDPC_HIP(v.mc(dim3((unsigned)grid), dim3(mc->route.TB), mc->route.lds_bytes, st, a));
     if (bposd) {
       unsigned int nc[4] = {0, 0, 0, 0};
       QLDPC_HIP(hipMemcpyAsync(nc, mc->c_n.p, 16, hipMemcpyDeviceToHost, st));

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/qldpc_hip.h"
+#include "route.h"
 
 namespace qldpc_rt {
 
@@ -60,12 +61,10 @@ struct qldpc_graph {
 
 struct qldpc_bp {
   qldpc_graph* g = nullptr;
-  int engine = 2;
-  int max_iter = 0, method = 1, precision = 64;
+  qldpc_rt::Route route;
+  int max_iter = 0, method = 1;
   double alpha = 0.625;
-  int TB = 64, VPL = 1, DMAX = 4, NS = 1;
-  int nch = 0;  // engine 2: 16-byte chunks per check row
-  int lds_bytes = 0, blocks_per_cu = 0, cus = 0;
+  int blocks_per_cu = 0, cus = 0;
   std::vector<double> probs;
   // max_iter = 1 min-sum decodes (qldpc_bp_decode_batch): the first-min step kernel's one-iteration
   // BP (firstmin.hip), built on first use from these priors; dropped when they change
@@ -74,31 +73,15 @@ struct qldpc_bp {
   qldpc_rt::DevBuf vchk, llr;  // engine 1: packed u16 check ids; engines 2-4: edge words (check | slot<<16)
   qldpc_rt::DevBuf rdeg;       // engines 3/4: u8 row degrees (by check label)
   qldpc_rt::DevBuf rowtab;     // m2v: the check phase's row table [kM2vRows][TB] x 4 u32
-  int vslots_m2v = 0;          // m2v: V slots of the variable-major layout (0 = row-major formula)
-  int m2v_vlast = 0, m2v_nl = 0;  // m2v: first V slot of the last variable slot, its per-edge stride
-  int m2s_pk = 0;        // m2s rows of 8 with packed absolute edge addresses (engine id 10203)
-  int vslots_dummy = 0;  // m2s rows of 8 (engine id 10103): private V slots of real variables' missing edges
-  uint32_t nw = 0;       // narrow waves of the fp64 space-time m2s family (SSector::nw)
-  uint32_t live_last = 0;  // its waves live in the last variable slot (SSector::live_last)
   int npos = 0;       // 1 + the last slot position holding a variable (SSector::npos)
   qldpc_rt::DevBuf work;       // engine 3 decode_batch: chunk-queue head
-  // engines 3/4: variable of each (k, t) slot (-1 = padding).  Engine 3 sorts
-  // degree <= 3 variables first so that slots k < d3k skip the 4th edge slot.
-  std::vector<int32_t> slot_var;
+  std::vector<int32_t> slot_var;  // engines 2-4: variable of each (k, t) slot (-1 = padding)
   qldpc_rt::DevBuf perm;
   qldpc_rt::DevBuf rperm;  // engine 3: original check of each check label (label_checks)
   int gather_conf[2] = {0, 0};  // engine 3: extra gather cycles per pass before / after labelling
   // engine-3 fp64 variable phase, static LDS model per workgroup-iteration (qldpc_bp_lds_model):
   // CS gather cycles / extra, V-slot read cycles / extra, v2c store group-cycles / extra
   int64_t lds_model[6] = {0, 0, 0, 0, 0, 0};
-  int d3k = 0;
-  int d2k = 0;  // byte-F family: compile-time degree-2 slot count (slots of the measurement variables)
-  int ea_shift = 0;  // engine 3: 2 = dword-scaled LDS addresses in the edge words (images > 64 KiB)
-  int tail = 0;      // engine 3: 1 = rows of nch chunks + one tail slot per row (bp_reg.h eng_tail)
-  int m2s = 0;       // engine 3: 1 = one-word check state, m2 in the argmin slot (bp_reg.h eng_m2s);
-                     // 3 = the same with variable-major V slots (eng_m2v);
-                     // 2 = c2v written into the slots by the check phase (eng_c2s)
-  int fb = 0;        // engine 3: 1 = byte F words (fp32 space-time family, 512 threads; bp_reg.h eng_fb)
   // engine 5 (product-sum, bp_ps.hip): CSR / CSC on the device, optional HBM message workspace
   qldpc_rt::DevBuf ps_rp, ps_ci, ps_cp, ps_ce, ps_ws;
   long long ps_grid = 0;
@@ -113,12 +96,9 @@ struct qldpc_mc {
   qldpc_rt::DevBuf counters;
   qldpc_rt::DevBuf work;  // engine 3: chunk-queue head
   qldpc_rt::DevBuf cls_cache;  // engine 3, both sectors: sampled classes of the first sector's pass (SMcArgs)
-  int engine = 2, TB = 0, VPL = 0, DMAX = 0, NS = 1, precision = 64, lds_bytes = 0, blocks_per_cu = 0, cus = 0;
+  qldpc_rt::Route route;  // the sectors' common route (qldpc_mc_create)
+  int blocks_per_cu = 0, cus = 0;
   int mmax = 0, vslots = 0, img_bytes = 0;
-  int d3k = 0;  // engine 3: compile-time degree-3 slot count of the kernel (min over sectors)
-  int nch = 0;  // 16-byte chunks per check row when both sectors agree (else 0)
-  int ea_shift = 0;
-  int tail = 0, m2s = 0, fb = 0, m2s_pk = 0;  // engine 3 layout flags shared by both sectors
   // staged pipeline (staged.hip): product-sum decoders, or QLDPC_MC_STAGED=1
   bool staged = false;
   long long sbatch = 0;

@@ -589,7 +589,7 @@ int staged_mc_prepare(qldpc_mc* mc, const qldpc_graph* logical_x, const qldpc_gr
   const int n = d0->g->n;
   // the HBM engine decodes one syndrome per lane: a batch of many syndromes per resident lane
   // keeps its lanes refilled instead of waiting on the batch's slowest decode
-  const bool hbm = (mc->dec[0] && mc->dec[0]->engine == 6) || (mc->dec[1] && mc->dec[1]->engine == 6);
+  const bool hbm = (mc->dec[0] && mc->dec[0]->route.engine == 6) || (mc->dec[1] && mc->dec[1]->route.engine == 6);
   const char* eb = std::getenv("QLDPC_STAGED_BATCH");
   // HBM engine: 4M shots per batch (~32 decodes per resident lane and sector: the batch's tail, where
   // lanes run out of syndromes and their partial-wave accesses still move whole lines, drops from 1/2

@@ -218,6 +218,21 @@ class DeviceBP:
             self.handle = None
 
 
+def plan_bp(H, channel_probs, bp_method="minimum_sum", precision: int = 64, vars_per_thread: int = 0,
+            min_col_slots: int = 0) -> dict:
+    """The route :class:`DeviceBP` would take for this graph (``qldpc_bp_plan``), under the QLDPC_*
+    switches of the environment, decided on the host: needs the library, not a GPU.  The keys are
+    those of :meth:`DeviceBP.geometry` that do not depend on the device or the built tables."""
+    graph = DeviceGraph(H, device=0)  # host-side handle; the plan never touches the device
+    probs = np.ascontiguousarray(np.broadcast_to(np.asarray(channel_probs, dtype=np.float64), (graph.n,)))
+    out = (ctypes.c_int32 * 8)()
+    _native.check(_native.lib().qldpc_bp_plan(graph.handle, probs.ctypes.data_as(ctypes.c_void_p),
+                                              bp_method_code(bp_method), int(precision), int(vars_per_thread),
+                                              int(min_col_slots), out, 8), "qldpc_bp_plan")
+    return dict(zip(["engine", "kernel_id", "row_chunks", "threads", "vars_per_thread", "lds_bytes", "degree3_slots",
+                     "degree2_slots"], list(out)))
+
+
 OSD_METHODS = {"osd_0": 0, "osd0": 0, "osd_e": 1, "osde": 1, "exhaustive": 1, "osd_cs": 2, "osdcs": 2,
                "combination_sweep": 2}
 

@@ -5,18 +5,17 @@
 For every bundled code: hz itself and GetSpaceTimeCheckMat(hz, t0) for t0 = 2..5 (the phenomenological
 space-time decoders of CodeFamily_SpaceTime.EvalWER('phenl', num_rep = t0)), and [hz | I] (the
 single-shot CodeSimulator_Phenon decoder1): one JSON line with the shape, the row / column degrees and
-the decoder's geometry.  QLDPC_M2S_ANNEAL=0 skips the placement search (routing does not depend on it).
+the planned route (engine.plan_bp: decided on the host, so this runs without a GPU).
 """
 import json
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ.setdefault("QLDPC_M2S_ANNEAL", "0")
 import numpy as np  # noqa: E402
 
 from qldpc_fault_tolerance_amd import codes  # noqa: E402
-from qldpc_fault_tolerance_amd.engine import DeviceBP  # noqa: E402
+from qldpc_fault_tolerance_amd.engine import plan_bp  # noqa: E402
 
 prec = int(sys.argv[1]) if len(sys.argv) > 1 else 64
 for name in codes.bundled_codes():
@@ -30,8 +29,7 @@ for name in codes.bundled_codes():
         rec = {"code": name, "graph": tag, "m": H.m, "n": H.n, "nnz": int(len(H.col_idx)),
                "max_row": int(np.diff(H.row_ptr).max()), "max_col": int(deg.max())}
         try:
-            g = DeviceBP(H, 0.01 * np.ones(H.n), max_iter=10, precision=prec).geometry()
-            rec.update({k: g[k] for k in ("engine", "kernel_id", "threads", "vars_per_thread", "lds_bytes", "blocks_per_cu")})
+            rec.update(plan_bp(H, 0.01 * np.ones(H.n), precision=prec))
         except Exception as e:  # noqa: BLE001
             rec["error"] = repr(e)[:200]
         print(json.dumps(rec), flush=True)
