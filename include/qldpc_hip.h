@@ -410,6 +410,36 @@ typedef struct qldpc_circ qldpc_circ;
 int qldpc_circ_create(const qldpc_graph *dem, const qldpc_graph *dem_obs, const double *probs, qldpc_bp *dec1,
                       const qldpc_graph *h1_space_cor, const qldpc_graph *L1, qldpc_bp *dec2, const qldpc_graph *L2,
                       int32_t num_rounds, int32_t num_rep, int64_t max_batch, qldpc_circ **out);
+/*
+ * Single-shot mode of the same handle: CodeSimulator_Circuit._decoding_samples (src/Simulators.py:612-644)
+ * on the DEM of the single-shot circuit (num_cycles * m detectors, cycle-major; circuit.py
+ * single_shot_circuit).  Per sample, hist[j] = detector rows j * m .. j * m + m - 1:
+ *   res = 0;  for j in 0 .. num_cycles - 2:  s = hist[j] ^ res;  c = decoder1(s);
+ *                                             res = s ^ h_space c;  logical ^= L1 c;
+ *   s_f = hist[num_cycles - 1] ^ res;  c2 = decoder2(s_f);
+ *   failure = (s_f ^ h2 c2 != 0) or (observables ^ logical ^ L2 c2 != 0).
+ *   dec1    : decoder1 on [hx | I] (m x n1, n1 = n + m), or NULL (below);
+ *   h_space : m x n1 = [hx | 0]: the identity (syndrome-error) part of a correction is NOT applied;
+ *   L1      : K x n1 = [lx | 0];  dec2, L2 : decoder2 on h2 (m x n2) and K x n2 (= lx on hx).
+ * One cycle = one step kernel (residual and logical carry from the previous correction, this
+ * cycle's detector words, the next decode's syndrome bytes), the decode, its statistics.  The handle
+ * works with qldpc_circ_launch / _sample / _set_final_osd / _set_sampler / _info / _destroy; counters:
+ * sector 0 = decoder1 decodes (num_cycles - 1 per sample), sector 1 = decoder2 decodes; d_fail and
+ * d_detobs as above.  Asynchronous, shard- and batch-invariant.  QLDPC_EINVAL: num_cycles < 2,
+ * D != num_cycles * m, decoder1 not m x n1, mismatched shapes or devices.
+ *
+ * qldpc_circ_set_round_firstmin makes the rounds decode with a FirstMinBPDecoder handle (the
+ * Single-Shot notebook's decoder1 on [h | I]) instead of dec1; accepted steps count as iterations
+ * and no decode counts as non-converged, as in qldpc_phenl_set_round_firstmin.  The handle must be
+ * built on exactly decoder1's graph.  With dec1 = NULL at creation that graph is [hx | I] as h_space
+ * gives it (row r = h_space's row r and column n1 - m + r), and qldpc_circ_launch returns
+ * QLDPC_EINVAL until a first-min handle is set; fm = NULL goes back to dec1 (QLDPC_EINVAL when there
+ * is none).  QLDPC_EINVAL on a space-time handle.  The caller keeps fm alive while it is set.
+ */
+int qldpc_circ_create_single_shot(const qldpc_graph *dem, const qldpc_graph *dem_obs, const double *probs,
+                                  qldpc_bp *dec1, const qldpc_graph *h_space, const qldpc_graph *L1, qldpc_bp *dec2,
+                                  const qldpc_graph *L2, int32_t num_cycles, int64_t max_batch, qldpc_circ **out);
+int qldpc_circ_set_round_firstmin(qldpc_circ *circ, qldpc_firstmin *fm);
 /* decoder2 as bposd_decoder (ST_BPOSD_Decoder_Circuit, src/Decoders_SpaceTime.py:277-292): dec2 from
  * qldpc_bp_create_soft and ONE of a GPU OSD or a host OSD stage on h2; a host stage is turned into a
  * GPU OSD with its method, order, rank and soft weights, so the launch never leaves the device —

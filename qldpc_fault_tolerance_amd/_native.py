@@ -30,6 +30,7 @@ EXPORTED = [
     "qldpc_stream_sync", "qldpc_bp_kernel_id", "qldpc_build_flags", "qldpc_circ_create", "qldpc_circ_set_final_osd", "qldpc_circ_set_sampler",
     "qldpc_circ_info", "qldpc_circ_launch", "qldpc_circ_sample", "qldpc_circ_destroy",
     "qldpc_shard_range", "qldpc_bp_lds_model", "qldpc_m2s_place_model", "qldpc_bp_plan",
+    "qldpc_circ_create_single_shot", "qldpc_circ_set_round_firstmin",
 ]
 BUILD_EXPERIMENTAL = 1  # qldpc_build_flags(): the measured-and-not-kept kernel families are compiled in
 COMM_ID_BYTES = 128
@@ -186,6 +187,10 @@ def _declare(L):
     L.qldpc_build_flags.argtypes = []
     L.qldpc_circ_create.restype = ctypes.c_int
     L.qldpc_circ_create.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i64, _pp]
+    L.qldpc_circ_create_single_shot.restype = ctypes.c_int
+    L.qldpc_circ_create_single_shot.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _pp]
+    L.qldpc_circ_set_round_firstmin.restype = ctypes.c_int
+    L.qldpc_circ_set_round_firstmin.argtypes = [_vp, _vp]
     L.qldpc_circ_set_final_osd.restype = ctypes.c_int
     L.qldpc_circ_set_final_osd.argtypes = [_vp, _vp, _vp]
     L.qldpc_circ_set_sampler.restype = ctypes.c_int

@@ -24,7 +24,11 @@ hypergraphs (``GenFaultHyperGraph`` / ``GenCorrecHyperGraph``, ``:551-668``).  s
   logic (first and last ``shift_detectors`` segments);
 * :func:`ColorationCircuit` / :func:`RandomCircuit` — the CX schedules of
   ``src/CircuitScheduling.py:73-131`` (networkx's Hopcroft-Karp matching, the dependency the
-  reference itself calls, on the same graph built in the same order).
+  reference itself calls, on the same graph built in the same order);
+* :func:`syndrome_circuits` / :func:`single_shot_circuit` — the reference's two circuit builders: the
+  space-time one (``CodeSimulator_Circuit_SpaceTime``) and the single-shot one
+  (``CodeSimulator_Circuit._generate_circuit``, ``src/Simulators.py:438-609``; pinned op for op in
+  ``tests/golden/reference_circuit_single_shot.npz``).
 
 Parity: the schedules are pinned against the reference's own ``CircuitScheduling`` (importable
 here: numpy + networkx), ``tests/golden/reference_circuit_schedules.npz``.  The DEM is checked
@@ -623,3 +627,81 @@ def syndrome_circuits(hx, hz, lx, error_params: dict, pz: float, num_rounds: int
     circuit = init + num_rounds * stab + final(False)
     fault = init + stab + final(True)
     return add_cx_error(circuit, ep["p_CX"]), add_cx_error(fault, ep["p_CX"])
+
+
+def single_shot_circuit(hx, hz, lx, error_params: dict, num_cycles: int, scheduling_X, scheduling_Z) -> StimCircuit:
+    """``CodeSimulator_Circuit._generate_circuit`` (``src/Simulators.py:438-609``): the single-shot
+    circuit, ``RX data`` + the initial stabilizer layer + ``(num_cycles - 2) x`` the repeated layer +
+    the final data measurement, with CX noise.  Same qubit layout as :func:`syndrome_circuits`.
+
+    Against the space-time builder: no initial ``DEPOLARIZE1(pz)``; the ancilla resets sit inside the
+    initial layer; after the CX of every time step a ``DEPOLARIZE1(p_i)`` hits the data qubits that
+    step left idle (``"p_idling_gate"`` is not used); ``p_m`` hits the X ancillas only.  Detectors:
+    raw in the initial layer, differenced with the previous layer after it, the final ``MX`` ones
+    differenced with the last ancilla measurement: ``num_cycles * m`` detectors, cycle-major;
+    observables ``lx``.
+
+    The reference strikes each CX's data qubit from the step's idle list with ``list.index``: a
+    schedule that uses a data qubit twice in one time step raises ``ValueError`` there, and here
+    (``RandomCircuit`` does so on the d3 toric code and on ``hgp_34_n225``; ``ColorationCircuit``
+    never does: its steps are matchings)."""
+    hx, hz, lx = (np.asarray(a) for a in (hx, hz, lx))
+    n = hx.shape[1]
+    data = list(range(n))
+    nZ, nX = hz.shape[0], hx.shape[0]
+    Za = list(range(n, n + nZ))
+    Xa = list(range(n + nZ, n + nZ + nX))
+    ep = error_params
+    if num_cycles < 2:
+        raise ValueError("the single-shot circuit needs num_cycles >= 2 (initial layer + final measurement)")
+
+    def cx_steps(c: StimCircuit, schedule, anc, anc_is_control: bool):
+        for t, step in enumerate(schedule):
+            idle = list(data)
+            for j in step:
+                d = int(step[j])
+                c.append("CX", [anc[j], d] if anc_is_control else [d, anc[j]])
+                if d not in idle:
+                    raise ValueError(f"time step {t} of the CX schedule uses data qubit {d} twice: the reference's "
+                                     "idle list (list.index) raises here too; use circuit_type='coloration'")
+                idle.remove(d)
+            c.append("DEPOLARIZE1", idle, ep["p_i"])  # the data qubits this step leaves idle (may be none)
+            c.append("TICK")
+
+    def layer(first: bool) -> StimCircuit:
+        c = StimCircuit()
+        if first:
+            c.append("R", Xa)
+        c.append("H", Xa)
+        c.append("DEPOLARIZE1", Xa, ep["p_state_p"])
+        c.append("DEPOLARIZE1", data, ep["p_i"])
+        c.append("TICK")
+        cx_steps(c, scheduling_X, Xa, True)
+        if first:
+            c.append("R", Za)
+        c.append("DEPOLARIZE1", Za, ep["p_state_p"])
+        c.append("DEPOLARIZE1", data, ep["p_i"])
+        c.append("TICK")
+        cx_steps(c, scheduling_Z, Za, False)
+        c.append("H", Xa)
+        c.append("DEPOLARIZE1", Xa, ep["p_m"])
+        c.append("DEPOLARIZE1", data, ep["p_i"])
+        c.append("MR", Za + Xa)
+        for i in range(nX):
+            c.append("DETECTOR", [-nX + i] if first else [-nX + i, -nX + i - nZ - nX])
+        c.append("TICK")
+        return c
+
+    init = StimCircuit()
+    init.append("RX", data)
+    final = StimCircuit()
+    final.append("DEPOLARIZE1", data, ep["p_m"])
+    final.append("MX", data)
+    for i in range(nX):
+        recs = [-n + int(d) for d in np.where(hx[i, :] == 1)[0]]
+        recs.append(-nX + i - n)
+        final.append("DETECTOR", recs)
+    for i in range(len(lx)):
+        final.append("OBSERVABLE_INCLUDE", [-n + int(d) for d in np.where(lx[i, :] == 1)[0]], i)
+    circuit = init + layer(True) + (num_cycles - 2) * layer(False) + final
+    return add_cx_error(circuit, ep["p_CX"])

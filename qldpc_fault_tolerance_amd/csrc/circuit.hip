@@ -18,6 +18,12 @@
 // State is BIT-SLICED between the stages (word w of row r = row r of samples 64w..64w+63), so the
 // mechanism scatter of (1)-(2) is one wave ballot + one 64-bit atomic xor per (mechanism row, 64
 // samples), and (3)-(5)'s GF(2) products are word XORs; decoder I/O crosses to bytes per sample.
+//
+// The same handle has a single-shot mode (qldpc_circ_create_single_shot): CodeSimulator_Circuit
+// (src/Simulators.py:612-644) on the DEM of the single-shot circuit, num_cycles layers of m detectors.
+// (1), (2), (4), (5) are shared; (3) becomes, per cycle, one step kernel (cs_step: carried residual and
+// logical accumulator from the previous correction, this cycle's detector words, the next decode's
+// syndrome bytes) + the decode of decoder1 on [hx | I] (BP, or a first-min handle) + its statistics.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -147,6 +153,63 @@ __global__ void __launch_bounds__(kTileC) cs_apply(const int32_t* __restrict__ r
   }
 }
 
+// The single-shot circuit loop's cycle step (CodeSimulator_Circuit._decoding_samples,
+// src/Simulators.py:612-644; qldpc_circ_create_single_shot).  Cycle j decodes s_j = hist[j] ^ res_j,
+// res_0 = 0 and res_j = s_{j-1} ^ hx c_{j-1} = res_{j-1} ^ hist[j-1] ^ hx c_{j-1}.  acc rows 0..m-1
+// carry res (cs_final's meaning of them: what is XORed into the final detector rows), rows m..m+K-1
+// the logical accumulator lx (c_0 ^ .. ^ c_{j-1}).  One wave per (64-sample word w, tile of 64 rows
+// of A = [h_space; L1]); per cycle, instead of cs_apply + a word XOR + cs_unpack:
+//  (a) lanes over SAMPLES: the parity of each row of the tile on the previous cycle's byte
+//      corrections, one ballot per row (skipped in the first cycle: corr == nullptr); the ballot is
+//      wave-uniform, and the lane that owns the row in (b)-(d) keeps it (one select per row: the
+//      lane axis turns from samples to rows in registers, no LDS and no barrier, for any m);
+//  (b) lanes over ROWS: acc[r][w] ^= parity ^ (r < m ? previous cycle's detector word : 0);
+//  (c) s_j's word of row r < m = acc[r][w] ^ this cycle's detector word;
+//  (d) the next decode's syndromes as bytes out[s][m], 64 consecutive rows per store.
+// Each (r, w) belongs to one wave: no atomics.  Every exit and loop bound ahead of the ballots is
+// wave-uniform.  grid x = words (one per wave, kTileC / 64 per block), y = row tiles
+constexpr int kStepRows = 64;
+__global__ void __launch_bounds__(kTileC) cs_step(const int32_t* __restrict__ rp, const int32_t* __restrict__ ci,
+                                                 const uint8_t* __restrict__ corr, int n, const u64* __restrict__ DO,
+                                                 int prev0, int cur0, u64* __restrict__ acc, int m, int K,
+                                                 uint8_t* __restrict__ out, int W, long long count) {
+  const int lane = (int)__lane_id();
+  const int w = blockIdx.x * (kTileC / 64) + (int)(threadIdx.x >> 6);
+  if (w >= W || ((long long)w << 6) >= count) return;  // (uniform per wave)
+  const int t0 = blockIdx.y * kStepRows;
+  const int rows = std::min(kStepRows, m + K - t0);
+  if (rows <= 0) return;  // (uniform per wave)
+  const long long s = ((long long)w << 6) + lane;
+  u64 par = 0;  // lane l: the parity word of row t0 + l
+  if (corr) {
+    const uint8_t* c = corr + (s < count ? s : 0) * (long long)n;
+    for (int k = 0; k < rows; ++k) {
+      const int r = t0 + k;
+      uint32_t x = 0;
+      if (s < count)
+        for (int e = rp[r]; e < rp[r + 1]; ++e) x ^= c[ci[e]];
+      const u64 bits = __ballot((x & 1u) != 0);
+      if (lane == k) par = bits;
+    }
+  }
+  const int r = t0 + lane;
+  u64 sw = 0;
+  if (lane < rows) {
+    const long long at = (long long)r * W + w;
+    u64 a = acc[at] ^ par;
+    if (r < m) {
+      if (prev0 >= 0) a ^= DO[(long long)(prev0 + r) * W + w];
+      sw = a ^ DO[(long long)(cur0 + r) * W + w];
+    }
+    if (corr) acc[at] = a;  // (the first cycle leaves the zeroed accumulators as they are)
+  }
+  if (r < m) {  // the tile's syndrome rows: bytes [s][m], lanes over rows
+    const int nb = (int)std::min<long long>(64, count - ((long long)w << 6));
+    uint8_t* o = out + ((long long)w << 6) * m + r;
+    for (int b = 0; b < nb; ++b) o[(long long)b * m] = (uint8_t)((sw >> b) & 1ull);
+  }
+}
+
 // (5): rows 0..m-1 of [h2; L2]: final syndrome (detector rows fin0.., XOR the accumulated space
 // correction) + h2 · c2; rows m..m+K-1: observables (rows obs0..) + the accumulated L1 · c + L2 · c2.
 // Any nonzero residual bit fails its sample.  One thread per sample as cs_apply; lane 0 ORs the
@@ -255,6 +318,11 @@ struct qldpc_circ {
   DevBuf mp, mr, k53, a_rp, a_ci, f_rp, f_ci;  // mechanism rows, thresholds, [Hs; L1], [h2; L2]
   DevBuf skipT;                                // [M][64] geometric-skip thresholds ceil(2^53 (1 - p_j)^k)
   int sampler = 1;                             // 1 = geometric skip (default), 0 = keyed per (sample, mechanism)
+  // single-shot mode (qldpc_circ_create_single_shot): cycles > 0; rounds = cycles - 1 decodes of
+  // decoder1 per sample, by dec1 or by the first-min handle fm1 (qldpc_circ_set_round_firstmin)
+  int cycles = 0;
+  qldpc_firstmin* fm1 = nullptr;
+  qldpc_graph g1;  // dec1 == NULL: [hx | I], the graph a first-min handle has to be built on
   DevBuf DO, acc, failw, synd1, corr1, synd2, corr2, bpcorr2, post2, iters, conv;
 };
 
@@ -327,32 +395,15 @@ void circ_release(qldpc_circ* c) {
     b->release();
 }
 
-}  // namespace
-
-extern "C" {
-
-int qldpc_circ_create(const qldpc_graph* dem, const qldpc_graph* dem_obs, const double* probs, qldpc_bp* dec1,
-                      const qldpc_graph* h1_space_cor, const qldpc_graph* L1, qldpc_bp* dec2, const qldpc_graph* L2,
-                      int32_t num_rounds, int32_t num_rep, int64_t max_batch, qldpc_circ** out) {
-  if (!out || !dem || !dem_obs || !probs) return set_err(QLDPC_EINVAL, "NULL argument");
-  // no decoders at all: a sampler-only handle (qldpc_circ_sample) for decoders outside the engine
-  const bool sampler_only = !dec1 && !dec2;
-  if (!sampler_only && (!dec1 || !h1_space_cor || !L1 || !dec2 || !L2)) return set_err(QLDPC_EINVAL, "NULL argument");
-  if (num_rounds < 0 || num_rep < 1) return set_err(QLDPC_EINVAL, "num_rounds must be >= 0 and num_rep >= 1");
+// the handle of either mode from validated arguments: mechanism tables, [hs; L1] and [h2; L2],
+// batch buffers.  cycles > 0: single-shot mode (num_rounds = cycles - 1, num_rep = 1)
+int circ_build(const qldpc_graph* dem, const qldpc_graph* dem_obs, const double* probs, qldpc_bp* dec1,
+               const qldpc_graph* hs, const qldpc_graph* L1, qldpc_bp* dec2, const qldpc_graph* L2, int num_rounds,
+               int num_rep, int cycles, int m, int n1, int n2, bool sampler_only, int64_t max_batch, qldpc_circ** out) {
   const int M = dem->n, D = dem->m, K = dem_obs->m;
-  if (dem_obs->n != M) return set_err(QLDPC_EINVAL, "DEM detector and observable matrices differ in mechanism count");
-  const int m = sampler_only ? 0 : dec2->g->m, n1 = sampler_only ? 0 : dec1->g->n, n2 = sampler_only ? 0 : dec2->g->n;
-  if (!sampler_only) {
-    if (dec1->g->m != num_rep * m) return set_err(QLDPC_EINVAL, "decoder1's h1 must have num_rep * m rows");
-    if (D != (num_rounds * num_rep + 1) * m)
-      return set_err(QLDPC_EINVAL, "DEM detectors != (num_rounds * num_rep + 1) * m (num_cycles syndrome layers)");
-    if (h1_space_cor->m != m || h1_space_cor->n != n1 || L1->n != n1 || L1->m != K || L2->n != n2 || L2->m != K)
-      return set_err(QLDPC_EINVAL, "h1_space_cor / L1 / L2 shapes do not match the decoders and the DEM");
-    if (dec2->g->device != dec1->g->device) return set_err(QLDPC_EINVAL, "decoders on different devices");
-  }
   for (int j = 0; j < M; ++j)
     if (!(probs[j] >= 0.0 && probs[j] <= 1.0)) return set_err(QLDPC_EINVAL, "mechanism probability outside [0, 1]");
-  const int dev = sampler_only ? dem->device : dec1->g->device;
+  const int dev = sampler_only ? dem->device : dec2->g->device;
   QLDPC_HIP(hipSetDevice(dev));
   auto* c = new qldpc_circ();
   c->device = dev;
@@ -366,6 +417,7 @@ int qldpc_circ_create(const qldpc_graph* dem, const qldpc_graph* dem_obs, const 
   c->n2 = n2;
   c->rounds = num_rounds;
   c->reps = num_rep;
+  c->cycles = cycles;
   if (max_batch <= 0) max_batch = 1 << 16;
   c->max_batch = std::max<long long>(64, (max_batch + 63) / 64 * 64);
   auto fail = [&](int rc) {
@@ -397,7 +449,7 @@ int qldpc_circ_create(const qldpc_graph* dem, const qldpc_graph* dem_obs, const 
   }
   std::vector<int32_t> arp, aci, frp, fci;
   if (!sampler_only) {
-    stack_csr(h1_space_cor, L1, arp, aci);
+    stack_csr(hs, L1, arp, aci);
     stack_csr(dec2->g, L2, frp, fci);
   }
   int rc;
@@ -415,6 +467,80 @@ int qldpc_circ_create(const qldpc_graph* dem, const qldpc_graph* dem_obs, const 
       (rc = c->corr2.alloc((size_t)n2 * B)) || (rc = c->iters.alloc(B * 4)) || (rc = c->conv.alloc(B)))
     return fail(rc);
   *out = c;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int qldpc_circ_create(const qldpc_graph* dem, const qldpc_graph* dem_obs, const double* probs, qldpc_bp* dec1,
+                      const qldpc_graph* h1_space_cor, const qldpc_graph* L1, qldpc_bp* dec2, const qldpc_graph* L2,
+                      int32_t num_rounds, int32_t num_rep, int64_t max_batch, qldpc_circ** out) {
+  if (!out || !dem || !dem_obs || !probs) return set_err(QLDPC_EINVAL, "NULL argument");
+  // no decoders at all: a sampler-only handle (qldpc_circ_sample) for decoders outside the engine
+  const bool sampler_only = !dec1 && !dec2;
+  if (!sampler_only && (!dec1 || !h1_space_cor || !L1 || !dec2 || !L2)) return set_err(QLDPC_EINVAL, "NULL argument");
+  if (num_rounds < 0 || num_rep < 1) return set_err(QLDPC_EINVAL, "num_rounds must be >= 0 and num_rep >= 1");
+  const int M = dem->n, D = dem->m, K = dem_obs->m;
+  if (dem_obs->n != M) return set_err(QLDPC_EINVAL, "DEM detector and observable matrices differ in mechanism count");
+  const int m = sampler_only ? 0 : dec2->g->m, n1 = sampler_only ? 0 : dec1->g->n, n2 = sampler_only ? 0 : dec2->g->n;
+  if (!sampler_only) {
+    if (dec1->g->m != num_rep * m) return set_err(QLDPC_EINVAL, "decoder1's h1 must have num_rep * m rows");
+    if (D != (num_rounds * num_rep + 1) * m)
+      return set_err(QLDPC_EINVAL, "DEM detectors != (num_rounds * num_rep + 1) * m (num_cycles syndrome layers)");
+    if (h1_space_cor->m != m || h1_space_cor->n != n1 || L1->n != n1 || L1->m != K || L2->n != n2 || L2->m != K)
+      return set_err(QLDPC_EINVAL, "h1_space_cor / L1 / L2 shapes do not match the decoders and the DEM");
+    if (dec2->g->device != dec1->g->device) return set_err(QLDPC_EINVAL, "decoders on different devices");
+  }
+  return circ_build(dem, dem_obs, probs, dec1, h1_space_cor, L1, dec2, L2, num_rounds, num_rep, 0, m, n1, n2,
+                    sampler_only, max_batch, out);
+}
+
+int qldpc_circ_create_single_shot(const qldpc_graph* dem, const qldpc_graph* dem_obs, const double* probs,
+                                  qldpc_bp* dec1, const qldpc_graph* h_space, const qldpc_graph* L1, qldpc_bp* dec2,
+                                  const qldpc_graph* L2, int32_t num_cycles, int64_t max_batch, qldpc_circ** out) {
+  if (!out || !dem || !dem_obs || !probs || !h_space || !L1 || !dec2 || !L2)
+    return set_err(QLDPC_EINVAL, "NULL argument");
+  if (num_cycles < 2) return set_err(QLDPC_EINVAL, "num_cycles must be >= 2 (one decoder1 cycle and the final one)");
+  const int M = dem->n, D = dem->m, K = dem_obs->m;
+  if (dem_obs->n != M) return set_err(QLDPC_EINVAL, "DEM detector and observable matrices differ in mechanism count");
+  const int m = dec2->g->m, n1 = h_space->n, n2 = dec2->g->n;
+  if ((long long)D != (long long)num_cycles * m) return set_err(QLDPC_EINVAL, "DEM detectors != num_cycles * m");
+  if (h_space->m != m || L1->n != n1 || L1->m != K || L2->n != n2 || L2->m != K)
+    return set_err(QLDPC_EINVAL, "h_space / L1 / L2 shapes do not match the decoders and the DEM");
+  if (dec1) {
+    if (dec1->g->m != m || dec1->g->n != n1)
+      return set_err(QLDPC_EINVAL, "decoder1 must be on an m x n1 graph (m = decoder2's checks, n1 = h_space's columns)");
+    if (dec1->g->device != dec2->g->device) return set_err(QLDPC_EINVAL, "decoders on different devices");
+  } else if (n1 < m) {
+    return set_err(QLDPC_EINVAL, "h_space must have the m identity columns of [hx | I] after the data columns");
+  }
+  const int rc = circ_build(dem, dem_obs, probs, dec1, h_space, L1, dec2, L2, num_cycles - 1, 1, num_cycles, m, n1, n2,
+                            false, max_batch, out);
+  if (rc || dec1) return rc;
+  // no decoder1: the rounds wait for a first-min handle on [hx | I] = h_space's rows, each with its
+  // identity column n1 - m + r appended (qldpc_circ_set_round_firstmin compares the edges)
+  qldpc_graph& g = (*out)->g1;
+  g.device = dec2->g->device;
+  g.m = m;
+  g.n = n1;
+  g.row_ptr.assign(1, 0);
+  for (int r = 0; r < m; ++r) {
+    for (int e = h_space->row_ptr[r]; e < h_space->row_ptr[r + 1]; ++e) g.col_idx.push_back(h_space->col_idx[e]);
+    g.col_idx.push_back(n1 - m + r);
+    g.row_ptr.push_back((int32_t)g.col_idx.size());
+  }
+  return 0;
+}
+
+int qldpc_circ_set_round_firstmin(qldpc_circ* c, qldpc_firstmin* fm) {
+  if (!c) return set_err(QLDPC_EINVAL, "NULL circuit handle");
+  if (c->cycles == 0) return set_err(QLDPC_EINVAL, "first-min rounds need a single-shot circuit handle");
+  if (!fm && !c->dec1) return set_err(QLDPC_EINVAL, "a single-shot handle without decoder1 needs a first-min handle");
+  if (fm && !firstmin_matches(fm, c->dec1 ? c->dec1->g : &c->g1))
+    return set_err(QLDPC_EINVAL, "first-min handle was built on a different graph than decoder1's [hx | I]");
+  c->fm1 = fm;
   return 0;
 }
 
@@ -512,7 +638,9 @@ int qldpc_circ_sample(qldpc_circ* c, uint64_t seed, uint64_t shot_begin, int64_t
 int qldpc_circ_launch(qldpc_circ* c, uint64_t seed, uint64_t shot_begin, int64_t shot_count, void* d_counters,
                       uint8_t* d_fail, uint8_t* d_detobs, void* stream) {
   if (!c || !d_counters) return set_err(QLDPC_EINVAL, "NULL argument");
-  if (!c->dec1) return set_err(QLDPC_EINVAL, "sampler-only circuit handle: qldpc_circ_launch needs the decoders");
+  if (!c->dec2) return set_err(QLDPC_EINVAL, "sampler-only circuit handle: qldpc_circ_launch needs the decoders");
+  if (!c->dec1 && !c->fm1)
+    return set_err(QLDPC_EINVAL, "single-shot handle without decoder1: set a first-min handle first");
   if (shot_count <= 0) return 0;
   QLDPC_HIP(hipSetDevice(c->device));
   hipStream_t st = (hipStream_t)stream;
@@ -536,8 +664,35 @@ int qldpc_circ_launch(qldpc_circ* c, uint64_t seed, uint64_t shot_begin, int64_t
                          DO, acc, 0, D + K, 0, d_detobs + c0 * (long long)(D + K), W, B);
       QLDPC_HIP(hipGetLastError());
     }
+    // single-shot mode: cycle step (residual / logical carry, next syndromes), decoder1 or first-min,
+    // statistics; the last step writes decoder2's syndromes
+    for (int j = 0; j < c->cycles; ++j) {
+      const bool last = j == c->cycles - 1;
+      hipLaunchKernelGGL(cs_step, dim3((unsigned)((W + kTileC / 64 - 1) / (kTileC / 64)),
+                                       (unsigned)((m + K + kStepRows - 1) / kStepRows)),
+                         dim3(kTileC), 0, st, static_cast<const int32_t*>(c->a_rp.p),
+                         static_cast<const int32_t*>(c->a_ci.p), j ? static_cast<const uint8_t*>(c->corr1.p) : nullptr,
+                         c->n1, DO, j ? (j - 1) * m : -1, j * m, acc, m, K,
+                         static_cast<uint8_t*>(last ? c->synd2.p : c->synd1.p), W, B);
+      QLDPC_HIP(hipGetLastError());
+      if (last) break;
+      int rc;
+      if (c->fm1) {  // FirstMinBPDecoder: accepted steps as "iterations", never non-converged (as qldpc_phenl)
+        rc = qldpc_firstmin_decode(c->fm1, static_cast<const uint8_t*>(c->synd1.p), static_cast<uint8_t*>(c->corr1.p),
+                                   static_cast<int32_t*>(c->iters.p), B, stream);
+        if (rc) return rc;
+        QLDPC_HIP(hipMemsetAsync(c->conv.p, 1, (size_t)B, st));
+      } else {
+        rc = qldpc_bp_decode_batch(c->dec1, static_cast<const uint8_t*>(c->synd1.p), static_cast<uint8_t*>(c->corr1.p),
+                                   static_cast<int32_t*>(c->iters.p), static_cast<uint8_t*>(c->conv.p), B, stream);
+        if (rc) return rc;
+      }
+      hipLaunchKernelGGL(cs_iters, dim3(iters_grid(B)), dim3(kTileC), 0, st,
+                         static_cast<const int32_t*>(c->iters.p), static_cast<const uint8_t*>(c->conv.p), cnt, 0, B);
+      QLDPC_HIP(hipGetLastError());
+    }
     // (3) the noisy rounds: decoder1 on h1, space / logical corrections accumulated
-    for (int r = 0; r < c->rounds; ++r) {
+    for (int r = 0; r < (c->cycles ? 0 : c->rounds); ++r) {
       hipLaunchKernelGGL(cs_unpack, dim3((unsigned)((R1 + kTileC - 1) / kTileC), (unsigned)W), dim3(kTileC), 0, st,
                          DO, acc, r * R1, R1, m, static_cast<uint8_t*>(c->synd1.p), W, B);
       QLDPC_HIP(hipGetLastError());
@@ -554,9 +709,11 @@ int qldpc_circ_launch(qldpc_circ* c, uint64_t seed, uint64_t shot_begin, int64_t
     }
     // (4) the final layer: decoder2 on h2
     const int fin0 = c->rounds * R1;
-    hipLaunchKernelGGL(cs_unpack, dim3((unsigned)((m + kTileC - 1) / kTileC), (unsigned)W), dim3(kTileC), 0, st, DO,
-                       acc, fin0, m, m, static_cast<uint8_t*>(c->synd2.p), W, B);
-    QLDPC_HIP(hipGetLastError());
+    if (!c->cycles) {
+      hipLaunchKernelGGL(cs_unpack, dim3((unsigned)((m + kTileC - 1) / kTileC), (unsigned)W), dim3(kTileC), 0, st, DO,
+                         acc, fin0, m, m, static_cast<uint8_t*>(c->synd2.p), W, B);
+      QLDPC_HIP(hipGetLastError());
+    }
     int rc;
     auto* synd2 = static_cast<const uint8_t*>(c->synd2.p);
     auto* corr2 = static_cast<uint8_t*>(c->corr2.p);

@@ -800,3 +800,66 @@ class DeviceCircuit:
         if h and _native._lib is not None:
             _native.lib().qldpc_circ_destroy(h)
             self.handle = None
+
+
+def _dem_csr(rows_of, num_rows: int, num_cols: int):
+    """CSR of a DEM matrix from its per-mechanism row lists (``dem.dets`` / ``dem.obs``), without the
+    dense [rows x mechanisms] array: the threshold sweeps reach 10^4 detectors x 10^5 mechanisms."""
+    lens = np.fromiter((len(r) for r in rows_of), dtype=np.int64, count=len(rows_of))
+    rows = np.fromiter((d for r in rows_of for d in r), dtype=np.int64, count=int(lens.sum()))
+    cols = np.repeat(np.arange(len(rows_of), dtype=np.int64), lens)
+    order = np.lexsort((cols, rows))
+    row_ptr = np.zeros(num_rows + 1, dtype=np.int64)
+    np.add.at(row_ptr, rows + 1, 1)
+    return CSR(int(num_rows), int(num_cols), np.cumsum(row_ptr).astype(np.int32), cols[order].astype(np.int32))
+
+
+class DeviceCircuitSingleShot(DeviceCircuit):
+    """Single-shot circuit loop of ``CodeSimulator_Circuit`` on one GPU (``qldpc_circ_create_single_shot``,
+    csrc/circuit.hip): ``dem`` is the single-shot circuit's DEM (``num_cycles * m`` detectors),
+    ``dec1`` decodes every cycle but the last on ``[hx | I]``, ``dec2`` the last one on ``hx``; only
+    the data part of a decoder1 correction is applied (``hx``, ``lx``: dense 0/1 matrices of the
+    evaluated sector).  ``firstmin``: a :class:`DeviceFirstMin` on ``[hx | I]`` decodes the cycles
+    instead (``dec1`` may then be None).  ``launch`` / ``sample`` / ``run``, the OSD and the sampler
+    are :class:`DeviceCircuit`'s; counters: sector 0 = decoder1 (``num_cycles - 1`` per sample),
+    sector 1 = decoder2."""
+
+    def __init__(self, dem, dec1: "DeviceBP | None", hx, lx, dec2: "DeviceBP", num_cycles: int, osd=None,
+                 firstmin: "DeviceFirstMin | None" = None, max_batch: int = 0, sampler: str = "skip"):
+        dev = dec2.graph.device
+        self.device = dev
+        self.dem = dem
+        self.decoders = (dec1, dec2)
+        self.num_cycles = int(num_cycles)
+        self.num_rounds, self.num_rep = self.num_cycles - 1, 1
+        hx = np.asarray(hx, dtype=np.uint8) % 2
+        lx = np.asarray(lx, dtype=np.uint8) % 2
+        m = hx.shape[0]
+        pad = np.zeros((lx.shape[0], m), np.uint8)
+        M = dem.num_errors
+        mats = [_dem_csr(dem.dets, dem.num_detectors, M), _dem_csr(dem.obs, dem.num_observables, M),
+                np.hstack([hx, np.zeros((m, m), np.uint8)]), np.hstack([lx, pad]), lx]
+        self._g = [DeviceGraph(a, device=dev) for a in mats]
+        self._probs = np.ascontiguousarray(np.asarray(dem.probs, dtype=np.float64))
+        h = ctypes.c_void_p()
+        _native.check(_native.lib().qldpc_circ_create_single_shot(
+            self._g[0].handle, self._g[1].handle, self._probs.ctypes.data_as(ctypes.c_void_p),
+            dec1.handle if dec1 is not None else None, self._g[2].handle, self._g[3].handle, dec2.handle,
+            self._g[4].handle, self.num_cycles, int(max_batch), ctypes.byref(h)), "qldpc_circ_create_single_shot")
+        self.handle = h
+        self.sampler = sampler
+        _native.check(_native.lib().qldpc_circ_set_sampler(h, self.SAMPLERS[sampler]), "qldpc_circ_set_sampler")
+        self._osd = osd
+        if osd is not None:
+            gpu = osd.handle if isinstance(osd, DeviceOSD) else None
+            host = osd.handle if isinstance(osd, HostOSD) else None
+            _native.check(_native.lib().qldpc_circ_set_final_osd(h, gpu, host), "qldpc_circ_set_final_osd")
+        self._fm1 = None
+        if firstmin is not None:
+            self.set_round_firstmin(firstmin)
+
+    def set_round_firstmin(self, fm: "DeviceFirstMin | None"):
+        """Cycles decoded by FirstMinBPDecoder (``qldpc_circ_set_round_firstmin``); None: back to dec1."""
+        _native.check(_native.lib().qldpc_circ_set_round_firstmin(self.handle, fm.handle if fm is not None else None),
+                      "qldpc_circ_set_round_firstmin")
+        self._fm1 = fm  # keep the handle alive

@@ -11,7 +11,10 @@ Mirrors the code-capacity part of ``src/Simulators.py``:
   (:mod:`.parallel`).  Decoders from elsewhere (any object with
   ``.decode(synd)``, the reference's plugin contract ``src/Decoders.py:94-97``)
   run through the per-shot ``_single_run`` loop, as in the reference.
-* :class:`CodeFamily` (``:746-908``) — ``EvalWER('data', ...)``.
+* :class:`CodeSimulator_Circuit` (``:386-671``) — single-shot circuit-level noise on this
+  package's own circuits and detector error models (:mod:`.circuit`), every sample on the GPU
+  (``qldpc_circ_create_single_shot``) with engine decoders.
+* :class:`CodeFamily` (``:746-908``) — ``EvalWER('data' | 'phenl' | 'circuit', ...)``.
 * the threshold-fit helpers (``:675-741``), host-side post-processing.
 
 Shot randomness: the reference draws ``random.random()`` per qubit (MT19937,
@@ -907,11 +910,195 @@ class CodeSimulator_Circuit_SpaceTime:
         return word_error_rate_per_cycle(fails, total, self.K, self.num_cycles), total
 
 
+class CodeSimulator_Circuit:
+    """Single-shot circuit-level simulator (``src/Simulators.py:386-671``).
+
+    ``_generate_circuit`` builds the reference's single-shot circuit (:func:`.circuit.single_shot_circuit`:
+    ``RX data``, the initial stabilizer layer, ``num_cycles - 2`` repeated layers, the final data
+    measurement; ``AddCXError`` noise) and its detector error model, the sampler.  Per sample every
+    cycle but the last is decoded by decoder1 on ``[hx | I]`` (only the data part of its correction
+    is applied), the last by decoder2 on ``hx`` (``_decoding_samples``, ``:612-644``).
+    ``WordErrorRate`` runs every sample on the GPU (``qldpc_circ_create_single_shot``: one step kernel
+    + one batched decode per cycle) when decoder1 is this engine's ``BPDecoder`` or
+    ``FirstMinBPDecoder`` and decoder2 its ``BPDecoder`` or ``BPOSD_Decoder``; any other decoder
+    (``BPOSD_Decoder`` as decoder1 included) runs ``_decoding_samples`` per sample on GPU-sampled
+    detectors.
+
+    Kept from the reference:
+
+    * ``eval_logical_type='X'`` swaps ``hx``/``hz`` and ``lx``/``lz`` IN the passed code object
+      (``:390-402``; its CSR cache is cleared) and decodes with decoder1_x / decoder2_x: a caller
+      that reuses the object, as ``CodeFamily.EvalWER('circuit', 'X', [p0, p1, ..])`` does, evaluates
+      X, Z, X, .. (DESIGN.md quirk Q8);
+    * ``circuit_type='random'`` raises ``ValueError`` in ``_generate_circuit`` whenever the schedule
+      uses a data qubit twice in a time step (d3 toric, ``hgp_34_n225``); ``'coloration'`` works;
+    * ``error_params["p_idling_gate"]`` is not used by this circuit.
+    """
+
+    def __init__(self, code=None, decoder1_z=None, decoder1_x=None, decoder2_z=None, decoder2_x=None, p=0,
+                 num_cycles=1, error_params=None, eval_logical_type="Z", circuit_type="coloration",
+                 rand_scheduling_seed=0, seed=None, max_batch=0, sampler="skip"):
+        from . import circuit as _circ
+
+        if eval_logical_type == "X":  # :390-402, in place
+            code.hx, code.hz = code.hz, code.hx
+            code.lx, code.lz = code.lz, code.lx
+            if isinstance(getattr(code, "_csr", None), dict):
+                code._csr.clear()
+            decoder1_z, decoder2_z = decoder1_x, decoder2_x
+        self.eval_code = code
+        self.hx_ext = np.hstack([code.hx, np.identity(np.shape(code.hx)[0])])
+        self.hz_ext = np.hstack([code.hz, np.identity(np.shape(code.hz)[0])])
+        self.decoder1_z = decoder1_z
+        self.decoder2_z = decoder2_z
+        self.N = code.N
+        self.K = code.K
+        self.pz = p
+        self.synd_prob = p
+        self.error_x = np.zeros(self.N).astype(int)
+        self.error_z = np.zeros(self.N).astype(int)
+        self.min_logical_weight = self.N
+        self.num_cycles = num_cycles
+        self.circuit = _circ.StimCircuit()
+        self.error_params = error_params
+        self.max_stab_weight_x = int(np.max(np.sum(code.hx, axis=1)))
+        self.max_stab_weight_z = int(np.max(np.sum(code.hz, axis=1)))
+        if circuit_type == "random":
+            self.scheduling_X = _circ.RandomCircuit(code.hx)
+            self.scheduling_Z = _circ.RandomCircuit(code.hz)
+        elif circuit_type == "coloration":
+            self.scheduling_X = _circ.ColorationCircuit(code.hx)
+            self.scheduling_Z = _circ.ColorationCircuit(code.hz)
+        self.dem = None
+        self.detector_sampler = None
+        self.seed = int(seed) if seed is not None else None
+        self.sampler = sampler  # DEM sampler of the device loop: "skip" (geometric gaps) or "keyed"
+        self.max_batch = int(max_batch)
+        self._shot_offset = 0
+        self._dev = None
+        self._dev_key = None
+        self.last_result = None
+
+    def _generate_circuit(self):
+        """``:438-609``; the circuit's DEM is the sampler."""
+        from . import circuit as _circ
+
+        c = self.eval_code
+        self.circuit = _circ.single_shot_circuit(c.hx, c.hz, c.lx, self.error_params, self.num_cycles,
+                                                 self.scheduling_X, self.scheduling_Z)
+        self.dem = self.circuit.detector_error_model(flatten_loops=True)
+        self.detector_sampler = _DetectorSampler(self)
+        self._dev, self._dev_key = None, None  # a cached device loop holds the previous DEM
+
+    # -- reference per-sample path (plugin decoders) -------------------------------
+    def _decoding_samples(self, samples):
+        """``:612-644``: per sample the cycle loop of decoder1, then decoder2; 1 = failure."""
+        hx, lx = self.eval_code.hx, self.eval_code.lx
+        m, K, N = np.shape(hx)[0], len(lx), self.N
+        out = []
+        for sample in np.asarray(samples):
+            hist = 1.0 * np.reshape(np.array(sample[:-K]), [self.num_cycles, m])
+            logical = 1.0 * np.array(sample[-K:])
+            correction = np.zeros(N)
+            residual = 0
+            for j in range(len(hist) - 1):
+                syn = (hist[j] + residual) % 2
+                new = np.asarray(self.decoder1_z.decode(syn))
+                correction = (new[:N] + correction) % 2
+                residual = (syn + hx @ new[:N]) % 2
+            syn_f = (hist[-1] + residual) % 2
+            fin = np.asarray(self.decoder2_z.decode(syn_f))
+            total = (correction + fin) % 2
+            res_syn = (syn_f + self.decoder2_z.h @ fin) % 2
+            res_log = (logical + (lx @ total) % 2) % 2
+            out.append(1 if (res_syn.any() or res_log.any()) else 0)
+        return out
+
+    def _single_run(self):
+        samples = self.detector_sampler.sample(shots=1, append_observables=True)
+        return self._decoding_samples(samples)[0]
+
+    # -- fused engine path ---------------------------------------------------------
+    def _engine_parts(self):
+        """(decoder1's DeviceBP or None, its DeviceFirstMin or None, decoder2's DeviceBP, decoder2's
+        OSD or None) when both decoders are this engine's, else None."""
+        from .decoders import BPDecoder, BPOSD_Decoder, FirstMinBPDecoder
+
+        d1, d2 = self.decoder1_z, self.decoder2_z
+        if isinstance(d1, FirstMinBPDecoder):
+            ext = self.hx_ext
+            if d1._fm is None or d1.h.shape != ext.shape or not np.array_equal(d1.h % 2, ext % 2):
+                return None
+            b1, fm = None, d1._fm
+        elif isinstance(d1, BPDecoder) and _engine_bp(d1) is not None:
+            b1, fm = d1.decoder, None
+        else:
+            return None
+        if isinstance(d2, BPOSD_Decoder):
+            return b1, fm, d2.decoder, (getattr(d2, "gpu_osd", None) or d2.osd)
+        if isinstance(d2, BPDecoder) and _engine_bp(d2) is not None:
+            return b1, fm, d2.decoder, None
+        return None
+
+    def _device(self):
+        from .engine import DeviceCircuit, DeviceCircuitSingleShot
+
+        parts = self._engine_parts()
+        key = None if parts is None else tuple(id(x) for x in parts)
+        if self._dev is None or self._dev_key != key:
+            if self.dem is None:
+                raise RuntimeError("call _generate_circuit() first")
+            if parts is None:
+                self._dev = DeviceCircuit(self.dem, max_batch=self.max_batch, sampler=self.sampler)
+            else:
+                b1, fm, b2, osd = parts
+                self._dev = DeviceCircuitSingleShot(self.dem, b1, self.eval_code.hx, self.eval_code.lx, b2,
+                                                    self.num_cycles, osd=osd, firstmin=fm, max_batch=self.max_batch,
+                                                    sampler=self.sampler)
+            self._dev_key = key
+        return self._dev
+
+    def fused_counts(self, num_samples: int):
+        """``num_samples`` samples on the GPU (sharded over the torch.distributed ranks); the
+        all-reduced :class:`~.engine.MCResult`."""
+        from .engine import MCResult, _torch
+
+        if self._engine_parts() is None:
+            raise TypeError("fused path needs engine decoders (BPDecoder / FirstMinBPDecoder on [hx | I], "
+                            "BPDecoder / BPOSD_Decoder on hx)")
+        torch = _torch()
+        if self.seed is None:
+            self.seed = random.getrandbits(64)
+        dev = self._device()
+        rank, ws = parallel.world()
+        b, c = parallel.shard_range(num_samples, rank, ws, begin=self._shot_offset)
+        self._shot_offset += int(num_samples)
+        cnt = dev.new_counters()
+        dev.launch(self.seed, b, c, cnt)
+        parallel.allreduce_counters(cnt)
+        torch.cuda.synchronize(cnt.device)
+        res = MCResult.from_words(cnt.cpu().numpy())
+        self.last_result = res
+        return res
+
+    def _batch_failures(self, n: int) -> int:
+        if self._engine_parts() is not None:
+            return self.fused_counts(n).failures
+        samples = self.detector_sampler.sample(shots=n, append_observables=True)
+        return int(np.sum(self._decoding_samples(samples)))
+
+    def WordErrorRate(self, num_samples: int):
+        """``:653-671``: ``(wer per qubit per cycle, None)``; num_cycles must be odd."""
+        assert int(self.num_cycles) % 2 == 1
+        error_count = self._batch_failures(num_samples)
+        return word_error_rate_phenl(error_count, num_samples, self.K, self.num_cycles), None
+
+
 class _DetectorSampler:
     """``self.circuit.compile_detector_sampler()`` (``:940``) on the GPU: the full circuit's DEM
     mechanisms sampled by Philox (``qldpc_circ_sample``); consecutive calls draw consecutive samples."""
 
-    def __init__(self, sim: "CodeSimulator_Circuit_SpaceTime"):
+    def __init__(self, sim: "CodeSimulator_Circuit_SpaceTime | CodeSimulator_Circuit"):
         self.sim = sim
 
     def sample(self, shots: int, append_observables: bool = True):
@@ -932,7 +1119,8 @@ class _DetectorSampler:
 
 
 class CodeFamily:
-    """``src/Simulators.py:746-963`` (``'data'`` and ``'phenl'`` noise models; ``'circuit'`` needs stim)."""
+    """``src/Simulators.py:746-963``: the ``'data'``, ``'phenl'`` and ``'circuit'`` noise models
+    (``'circuit'``: :class:`CodeSimulator_Circuit` on this package's own circuits and DEMs)."""
 
     def __init__(self, code_list: list, decoder1_class, decoder2_class):
         self.code_list = code_list
@@ -943,11 +1131,14 @@ class CodeFamily:
                 data_synd_noise_ratio=1, circuit_type="coloration", circuit_error_params=None, if_plot=True):
         assert noise_model in ["data", "phenl", "circuit"], "noise_model should be one of [data, phenl, circuit]"
         assert eval_logical_type in ["X", "Z", "Total"], "eval_type should be one of [X, Y, Total]"
-        if noise_model == "circuit":
-            raise NotImplementedError("circuit-level noise needs stim's circuits / detector error models (absent)")
         eval_wer_list = []
         for eval_code in self.code_list:
             for eval_p in eval_p_list:
+                if noise_model == "circuit":  # src/Simulators.py:815-870
+                    eval_wer_list.append(self._circuit_wer(eval_code, eval_p, eval_logical_type, num_samples,
+                                                           num_cycles, data_synd_noise_ratio, circuit_type,
+                                                           circuit_error_params))
+                    continue
                 p = eval_p * 3 / 2
                 pauli_error_probs = [p / 3, p / 3, p / 3]  # src/Simulators.py:763-764
                 if noise_model == "phenl":  # src/Simulators.py:779-809
@@ -974,6 +1165,30 @@ class CodeFamily:
         if if_plot:
             _plot_wer(self.code_list, eval_p_list, eval_wer_array, num_cycles)
         return eval_wer_array
+
+    def _circuit_wer(self, eval_code, eval_p, eval_logical_type, num_samples, num_cycles, data_synd_noise_ratio,
+                     circuit_type, circuit_error_params):
+        """One point of the circuit threshold (``src/Simulators.py:815-870``): decoder1 on ``[h | I]``
+        with ``p_data = data_synd_noise_ratio * p``, ``p_syndrome = p``, decoder2 on ``h`` with ``p``;
+        ``'Total'`` = the Z run + the X run.  The X run swaps the sectors of ``eval_code`` in place
+        (quirk Q8), so the decoders are built from the code as the previous point left it."""
+        p = eval_p
+        error_params = {k: circuit_error_params[k] * p for k in ("p_i", "p_state_p", "p_m", "p_CX", "p_idling_gate")}
+        p_data, p_synd = data_synd_noise_ratio * p, 1 * p
+        hx_ext = np.hstack([eval_code.hx, np.identity(np.shape(eval_code.hx)[0])])
+        hz_ext = np.hstack([eval_code.hz, np.identity(np.shape(eval_code.hz)[0])])
+        d1z = self.decoder1_class.GetDecoder({"h": hx_ext, "p_data": p_data, "p_syndrome": p_synd})
+        d1x = self.decoder1_class.GetDecoder({"h": hz_ext, "p_data": p_data, "p_syndrome": p_synd})
+        d2z = self.decoder2_class.GetDecoder({"h": eval_code.hx, "p_data": eval_p})
+        d2x = self.decoder2_class.GetDecoder({"h": eval_code.hz, "p_data": eval_p})
+        wer = 0.0
+        for t in (["Z", "X"] if eval_logical_type == "Total" else [eval_logical_type]):
+            sim = CodeSimulator_Circuit(code=eval_code, decoder1_z=d1z, decoder1_x=d1x, decoder2_z=d2z,
+                                        decoder2_x=d2x, p=p, num_cycles=num_cycles, error_params=error_params,
+                                        eval_logical_type=t, circuit_type=circuit_type, rand_scheduling_seed=1)
+            sim._generate_circuit()
+            wer = wer + sim.WordErrorRate(num_samples=num_samples)[0]
+        return wer
 
     def EvalThreshold(self, noise_model: str, eval_logical_type: str, eval_method: str, est_threshold: float,
                       num_samples: int, num_cycles=1, data_synd_noise_ratio=1, circuit_type="coloration",
