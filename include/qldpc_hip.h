@@ -472,6 +472,36 @@ int qldpc_circ_destroy(qldpc_circ *circ);
 int qldpc_sample_errors(double px, double py, double pz, uint64_t seed, uint64_t shot_begin, int64_t shot_count,
                         int32_t n, const double *d_uniforms, uint8_t *d_err, void *stream);
 
+/*
+ * Random information-set minimum-distance search (distance.hip): what replaces the reference's
+ * compute_code_distance(H) / hgp(..., compute_distance=True) (src/QuantumExanderCodesGene.py) at sizes
+ * where enumeration is impossible.  gen_words: a generator matrix of the kernel of a check matrix, rows x n
+ * bits packed 64 columns per uint64 word (bit c & 63 of word c >> 6), row-major; pair_words: its pairing
+ * G L^T with the k logical operators of the other sector, packed the same way, or NULL with k = 0 for a
+ * classical code.  Trial t orders the columns by ascending (key, c), key = first word of Philox4x32-10 at
+ * counter (c, t_lo, t_hi, 0x51D50005) and key (seed_lo, seed_hi), runs a greedy Gauss-Jordan in that
+ * order and reports min (weight, pivot position) over the rows that hold a pivot and have non-zero
+ * pairing; a range reports min (weight, trial), that row (n bits, original column numbering) and the
+ * per-trial minima (0x7FFFFFFF: no candidate).  Results are independent of the grid and of how a
+ * range is cut into calls.  device = -1: host-only handle (no HIP call, any size); a device handle
+ * needs 1 <= rows <= 1024 and at most 28 row words, code plus pairing (QLDPC_ENOTSUP otherwise).
+ * Outputs are host memory; qldpc_dist_run synchronizes `stream`.  workgroups = 0: compute units x
+ * (1024 / threads) workgroups, 1024 threads' worth per compute unit (LDS may keep fewer resident;
+ * the trial loop is grid-strided, so residency is not needed).
+ */
+typedef struct qldpc_dist qldpc_dist;
+int qldpc_dist_create(int device, int32_t rows, int32_t n, int32_t k, const uint64_t *gen_words,
+                      const uint64_t *pair_words, qldpc_dist **out);
+int qldpc_dist_run_host(qldpc_dist *h, uint64_t seed, uint64_t trial_begin, int64_t trials, int32_t *trial_min,
+                        int32_t *best_weight, uint64_t *best_trial, uint64_t *witness_words);
+int qldpc_dist_run(qldpc_dist *h, uint64_t seed, uint64_t trial_begin, int64_t trials, int32_t workgroups,
+                   int32_t *trial_min, int32_t *best_weight, uint64_t *best_trial, uint64_t *witness_words,
+                   void *stream);
+/* threads per workgroup, code words and pairing words per row, LDS bytes (0 threads / bytes: host handle) */
+int qldpc_dist_geometry(const qldpc_dist *h, int32_t *threads, int32_t *row_words, int32_t *pair_words,
+                        int32_t *lds_bytes);
+int qldpc_dist_destroy(qldpc_dist *h);
+
 /* hipStreamSynchronize(stream) for hosts without a HIP binding (NULL = legacy default stream). */
 int qldpc_stream_sync(void *stream);
 

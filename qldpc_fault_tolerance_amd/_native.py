@@ -31,6 +31,7 @@ EXPORTED = [
     "qldpc_circ_info", "qldpc_circ_launch", "qldpc_circ_sample", "qldpc_circ_destroy",
     "qldpc_shard_range", "qldpc_bp_lds_model", "qldpc_m2s_place_model", "qldpc_bp_plan",
     "qldpc_circ_create_single_shot", "qldpc_circ_set_round_firstmin",
+    "qldpc_dist_create", "qldpc_dist_run_host", "qldpc_dist_run", "qldpc_dist_geometry", "qldpc_dist_destroy",
 ]
 BUILD_EXPERIMENTAL = 1  # qldpc_build_flags(): the measured-and-not-kept kernel families are compiled in
 COMM_ID_BYTES = 128
@@ -209,6 +210,17 @@ def _declare(L):
     L.qldpc_shard_range.argtypes = [_i64, _i32, _i32, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]
     L.qldpc_circ_destroy.restype = ctypes.c_int
     L.qldpc_circ_destroy.argtypes = [_vp]
+    L.qldpc_dist_create.restype = ctypes.c_int
+    L.qldpc_dist_create.argtypes = [ctypes.c_int, _i32, _i32, _i32, _vp, _vp, _pp]
+    L.qldpc_dist_run_host.restype = ctypes.c_int
+    L.qldpc_dist_run_host.argtypes = [_vp, _u64, _u64, _i64, _vp, ctypes.POINTER(_i32), ctypes.POINTER(_u64), _vp]
+    L.qldpc_dist_run.restype = ctypes.c_int
+    L.qldpc_dist_run.argtypes = [_vp, _u64, _u64, _i64, _i32, _vp, ctypes.POINTER(_i32), ctypes.POINTER(_u64), _vp,
+                                 _vp]
+    L.qldpc_dist_geometry.restype = ctypes.c_int
+    L.qldpc_dist_geometry.argtypes = [_vp] + [ctypes.POINTER(_i32)] * 4
+    L.qldpc_dist_destroy.restype = ctypes.c_int
+    L.qldpc_dist_destroy.argtypes = [_vp]
 
 
 def lib():

@@ -95,6 +95,7 @@ class CSSCode:
     name: str = "<Unnamed CSS code>"
     h1: np.ndarray | None = None
     h2: np.ndarray | None = None
+    D: int | None = None  # distance, when known (hgp(..., compute_distance=True))
     _csr: dict = field(default_factory=dict, repr=False)
 
     def __post_init__(self):
@@ -130,12 +131,27 @@ class CSSCode:
             lx, lz = gf2.compute_logicals(hx, hz)
         return CSSCode(hx=hx, hz=hz, lx=lx, lz=lz, name=name)
 
+    def distance_search(self, kind: str, **kw) -> "DistanceResult":
+        """:func:`distance_search` on one sector: ``"Z"`` searches ker(hx) against ``lx`` (the
+        Z-type operators the reference's ``residual_z`` checks catch), ``"X"`` ker(hz) against ``lz``."""
+        if kind not in ("X", "Z"):
+            raise ValueError("kind must be 'X' or 'Z'")
+        return distance_search(self.hx, self.lx, **kw) if kind == "Z" else distance_search(self.hz, self.lz, **kw)
 
-def hgp(h1, h2=None, name: str | None = None) -> CSSCode:
+    def distance_bound(self, **kw):
+        """``(dx, dz)``: the search's upper bounds on the X- and Z-type distance."""
+        return self.distance_search("X", **kw).weight, self.distance_search("Z", **kw).weight
+
+
+def hgp(h1, h2=None, name: str | None = None, compute_distance: bool = False) -> CSSCode:
     """Hypergraph product ``hx=[h1⊗I_n2 | I_m1⊗h2ᵀ]``, ``hz=[I_n1⊗h2 | h1ᵀ⊗I_m2]``.
 
     Same block layout as ``bposd.hgp.hgp`` (``hx1,hx2,hz1,hz2`` attributes of the
     reference pickle).  Logicals from :func:`gf2.compute_logicals`.
+    ``compute_distance`` sets ``code.D`` as ``bposd.hgp`` does, by the HGP distance theorem: the
+    minimum of the classical distances of ``h1``, ``h2``, ``h1ᵀ``, ``h2ᵀ`` that exist (``k > 0``).
+    Each comes from :func:`classical_distance`: exact for factors with ``k <= 16``, the search's
+    upper bound beyond, so ``D`` is then an upper bound too.
     """
     h1 = (np.asarray(h1).astype(np.int64) % 2).astype(np.uint8)
     h2 = h1 if h2 is None else (np.asarray(h2).astype(np.int64) % 2).astype(np.uint8)
@@ -145,7 +161,158 @@ def hgp(h1, h2=None, name: str | None = None) -> CSSCode:
     hz = np.hstack([np.kron(np.eye(n1, dtype=np.uint8), h2), np.kron(h1.T, np.eye(m2, dtype=np.uint8))])
     code = CSSCode.from_checks(hx, hz, name=name or f"hgp[[{hx.shape[1]}]]")
     code.h1, code.h2 = h1, h2
+    if compute_distance:
+        ds = [classical_distance(h) for h in (h1, h2, h1.T, h2.T)]
+        ds = [d for d in ds if d is not None]
+        code.D = min(ds) if ds else None
     return code
+
+
+# ------------------------------------------------- minimum-distance search
+NO_CANDIDATE = 0x7FFFFFFF  # per-trial weight of a trial without a candidate
+
+
+@dataclass
+class DistanceResult:
+    """Outcome of :func:`distance_search` over ``[trial_begin, trial_begin + trials)``."""
+
+    weight: int | None      # smallest candidate weight (an upper bound on the distance), None: no candidate
+    witness: np.ndarray     # uint8 [n]: the operator of that weight found first
+    trial: int              # the trial that found it
+    trials: int
+    trial_min: np.ndarray   # int32 [trials]: each trial's minimum (NO_CANDIDATE if it had none)
+    hits: int               # trials that reached ``weight``
+    seconds: float = 0.0    # wall time of the search itself (without building the generator matrix)
+
+
+def _pack_rows(M: np.ndarray) -> np.ndarray:
+    """uint64 [rows, ceil(cols / 64)]: bit ``c & 63`` of word ``c >> 6`` is ``M[r, c]``."""
+    M = np.ascontiguousarray(M, dtype=np.uint8)
+    w = max(1, (M.shape[1] + 63) // 64)
+    P = np.zeros((M.shape[0], w * 8), dtype=np.uint8)
+    if M.shape[1]:
+        b = np.packbits(M, axis=1, bitorder="little")
+        P[:, :b.shape[1]] = b
+    return np.ascontiguousarray(P.view("<u8"))
+
+
+def _unpack_row(words: np.ndarray, n: int) -> np.ndarray:
+    return np.unpackbits(np.ascontiguousarray(words, dtype="<u8").view(np.uint8), bitorder="little")[:n].copy()
+
+
+def distance_search(H, L=None, trials: int = 1024, seed: int = 0, trial_begin: int = 0, backend: str = "auto",
+                    device: int | None = None, workgroups: int = 0) -> DistanceResult:
+    """Random information-set search for low-weight vectors of ker(H) (QDistRnd's method).
+
+    With ``L`` (the logical operators of the other sector) a candidate is a reduced row of a
+    generator matrix of ker(H) that pairs non-trivially with ``L``: ``H = hx, L = lx`` bounds the
+    Z-type distance of a CSS code.  Without ``L`` every reduced row counts (a classical code).
+    Each trial reduces the generator matrix on a Philox-ordered column set; the outputs are a
+    function of ``(H, L, seed, trial range)`` alone, identical on the GPU and the host path.
+    ``backend``: ``"gpu"`` (the HIP kernel; an error when it cannot serve), ``"host"`` (the C++
+    restatement) or ``"auto"`` (the GPU when a device is visible and the matrix fits its envelope).
+    """
+    import ctypes
+
+    from . import _native
+
+    if backend not in ("auto", "gpu", "host"):
+        raise ValueError("backend must be 'auto', 'gpu' or 'host'")
+    Hd = H.to_dense() if isinstance(H, CSR) else gf2._as_u8(H)
+    n = int(Hd.shape[1])
+    trials = int(trials)
+    if trials < 0 or n <= 0:
+        raise ValueError("need trials >= 0 and at least one column")
+    G = gf2.nullspace(Hd)
+    rows = int(G.shape[0])
+    k = 0
+    Pw = None
+    if L is not None:
+        Ld = L.to_dense() if isinstance(L, CSR) else gf2._as_u8(L)
+        if Ld.shape[1] != n:
+            raise ValueError("L and H must have the same number of columns")
+        k = int(Ld.shape[0])
+        if k:
+            Pw = _pack_rows(gf2.matmul(G, Ld.T))
+    empty = DistanceResult(None, np.zeros(n, np.uint8), 0, trials, np.full(trials, NO_CANDIDATE, np.int32), 0)
+    if rows == 0 or (L is not None and k == 0):
+        if backend == "gpu":
+            _native.require_gpu()
+        return empty
+    Gw = _pack_rows(G)
+    lib = _native.lib()
+    vp = ctypes.c_void_p
+
+    def create(dev):
+        h = vp()
+        rc = lib.qldpc_dist_create(dev, rows, n, k, Gw.ctypes.data_as(vp), Pw.ctypes.data_as(vp) if k else None,
+                                   ctypes.byref(h))
+        return rc, h
+
+    h = None
+    if backend != "host":
+        have = _native.device_count() > 0
+        if backend == "gpu":
+            _native.require_gpu()
+        if have:
+            dev = 0 if device is None else int(device)
+            rc, h = create(dev)
+            if rc == _native.ENOTSUP and backend == "auto":
+                h = None
+            else:
+                _native.check(rc, "qldpc_dist_create")
+    on_gpu = h is not None
+    if h is None:
+        rc, h = create(-1)
+        _native.check(rc, "qldpc_dist_create")
+    import time
+
+    t0 = time.perf_counter()
+    try:
+        tmin = np.empty(trials, dtype=np.int32)
+        bw, bt = ctypes.c_int32(), ctypes.c_uint64()
+        wit = np.zeros(Gw.shape[1], dtype="<u8")
+        if on_gpu:
+            rc = lib.qldpc_dist_run(h, seed, trial_begin, trials, int(workgroups), tmin.ctypes.data_as(vp),
+                                    ctypes.byref(bw), ctypes.byref(bt), wit.ctypes.data_as(vp), None)
+            _native.check(rc, "qldpc_dist_run")
+        else:
+            rc = lib.qldpc_dist_run_host(h, seed, trial_begin, trials, tmin.ctypes.data_as(vp), ctypes.byref(bw),
+                                         ctypes.byref(bt), wit.ctypes.data_as(vp))
+            _native.check(rc, "qldpc_dist_run_host")
+    finally:
+        lib.qldpc_dist_destroy(h)
+    dt = time.perf_counter() - t0
+    if bw.value == NO_CANDIDATE:
+        empty.trial_min, empty.seconds = tmin, dt
+        return empty
+    return DistanceResult(int(bw.value), _unpack_row(wit, n), int(bt.value), trials, tmin,
+                          int(np.count_nonzero(tmin == bw.value)), dt)
+
+
+def classical_distance(H, exact_max_k: int = 16, **kw):
+    """Minimum distance of the classical code ker(H); ``None`` when it has no codeword (``k = 0``).
+
+    Enumerates all ``2^k - 1`` codewords when ``k <= exact_max_k`` (what the reference's
+    ``compute_code_distance`` does at any size); otherwise the upper bound of
+    :func:`distance_search` (``**kw``: its trials / seed / backend)."""
+    Hd = H.to_dense() if isinstance(H, CSR) else gf2._as_u8(H)
+    G = gf2.nullspace(Hd)
+    k = int(G.shape[0])
+    if k == 0:
+        return None
+    if k > exact_max_k:
+        return distance_search(Hd, None, **kw).weight
+    # Gray-code walk over the non-zero combinations, on packed words
+    Gw = _pack_rows(G)
+    cur = np.zeros(Gw.shape[1], dtype="<u8")
+    best = Hd.shape[1] + 1
+    for i in range(1, 1 << k):
+        cur ^= Gw[(i & -i).bit_length() - 1]
+        w = int(np.unpackbits(cur.view(np.uint8)).sum())
+        if w < best:
+            best = w
+    return best
 
 
 # ---------------------------------------------------------------------- loaders
@@ -309,7 +476,7 @@ def _girth_and_short_cycles(H: np.ndarray):
 
 def random_biregular_check_matrix(n0: int, delta_c: int, delta_v: int, seed: int,
                                   min_girth: int = 6, max_tries: int = 10000,
-                                  require_full_rank: bool = True) -> np.ndarray:
+                                  require_full_rank: bool = True, min_distance: int | None = None) -> np.ndarray:
     """``n0·Δv × n0·Δc`` check matrix with row weight Δc and column weight Δv.
 
     Restates ``RandomaGraphs`` (configuration model over shuffled check/variable
@@ -318,6 +485,10 @@ def random_biregular_check_matrix(n0: int, delta_c: int, delta_v: int, seed: int
     ``RandSwapEdges1`` (``:286-310``) does, until ``min_girth`` is reached.
     ``require_full_rank`` keeps instances whose HGP has the reference's K
     (``[[1600,64]]``, ``[[1225,49]]``: ``Threshold-checkpoint.ipynb:233-236``).
+    ``min_distance`` rejects instances whose :func:`classical_distance` is below it, the filter
+    of ``GeneRandGraphsLargeGirth``; ``None`` draws exactly the stream it drew without the argument.
+    The distance is exact for ``k <= 16`` (enumeration); a larger code is judged by the search's upper
+    bound, which can let an instance below the bound through.
     """
     rng = _pyrandom.Random(seed)
     m, n = n0 * delta_v, n0 * delta_c
@@ -364,5 +535,9 @@ def random_biregular_check_matrix(n0: int, delta_c: int, delta_v: int, seed: int
         Hu = H.astype(np.uint8)
         if require_full_rank and gf2.rank(Hu) != m:
             continue
+        if min_distance is not None:
+            d = classical_distance(Hu)
+            if d is None or d < min_distance:
+                continue
         return Hu
     raise RuntimeError("could not build a biregular check matrix with the requested properties")
