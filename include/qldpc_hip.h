@@ -218,6 +218,33 @@ int qldpc_mc_launch(qldpc_mc *mc, double px, double py, double pz, uint64_t seed
                     uint8_t *d_fail, uint8_t *d_err, uint8_t *d_corr, int32_t *d_iters, int32_t grid_blocks,
                     void *stream);
 
+/*
+ * qldpc_mc_create with the staged pipeline forced (sample -> H e -> unpack -> qldpc_bp_decode_batch ->
+ * fold -> [H; L] check -> tally, bit-sliced 64 shots per word) whatever the decoders' routes: the
+ * handle qldpc_mc_launch_weight needs.  Same arguments and contract as qldpc_mc_create;
+ * qldpc_mc_launch / qldpc_mc_run work on it as on any handle; qldpc_mc_set_osd does not.
+ */
+int qldpc_mc_create_staged(qldpc_bp *dec_x, const qldpc_graph *logical_x, qldpc_bp *dec_z,
+                           const qldpc_graph *logical_z, qldpc_mc **out);
+
+/*
+ * The shot loop on errors of FIXED weight: every shot's error is a uniform random `weight`-subset of
+ * the n qubits with i.i.d. Pauli classes in the ratio px : py : pz (a depolarizing error conditioned
+ * on its weight; the decoders keep their own priors).  Shot s, step i = 0 .. weight-1, t = n - weight + i:
+ * (o0..o3) = Philox4x32-10(key = seed, ctr = (i, s_lo, s_hi, 0x51D50006)); r = (((o1 << 32) | o0) *
+ * (t + 1)) >> 64; the step takes qubit r, or qubit t if r is taken already (Floyd's algorithm); its
+ * class is Z if k < ceil(2^53 pz / T), else X if k < ceil(2^53 (pz + px) / T), else Y, with
+ * k = ((o2 >> 5) << 26) | (o3 >> 6) and T = (pz + px) + py.  A shot depends on (seed, s, weight, n,
+ * px : py : pz) only; the same (seed, s) at two weights shares draws, so give every weight its own
+ * shot range.  Counters and optional per-shot outputs as qldpc_mc_launch.  Needs a handle of
+ * qldpc_mc_create_staged (or any staged handle) without OSD: QLDPC_ENOTSUP otherwise, and for
+ * n > 4096.  QLDPC_EINVAL: weight outside 0 .. n, a negative probability, px = py = pz = 0 with
+ * weight > 0.
+ */
+int qldpc_mc_launch_weight(qldpc_mc *mc, int32_t weight, double px, double py, double pz, uint64_t seed,
+                           uint64_t shot_begin, int64_t shot_count, int32_t logical_mode, void *d_counters,
+                           uint8_t *d_fail, uint8_t *d_err, uint8_t *d_corr, int32_t *d_iters, void *stream);
+
 /* Synchronous convenience: launch + copy counters to host (accumulating into *out). */
 int qldpc_mc_run(qldpc_mc *mc, double px, double py, double pz, uint64_t seed, uint64_t shot_begin,
                  int64_t shot_count, int32_t logical_mode, qldpc_counters *out, void *stream);
@@ -471,6 +498,16 @@ int qldpc_circ_destroy(qldpc_circ *circ);
  */
 int qldpc_sample_errors(double px, double py, double pz, uint64_t seed, uint64_t shot_begin, int64_t shot_count,
                         int32_t n, const double *d_uniforms, uint8_t *d_err, void *stream);
+
+/*
+ * The fixed-weight sampler of qldpc_mc_launch_weight alone: d_err uint8 [S][n], bit0 = x, bit1 = z,
+ * exactly `weight` non-zero entries per row; bit-identical to that call's d_err output.  Async.
+ * The _host form is the same law in plain C++ on host memory (no HIP call, any n).
+ */
+int qldpc_sample_errors_weight(int32_t weight, double px, double py, double pz, uint64_t seed, uint64_t shot_begin,
+                               int64_t shot_count, int32_t n, uint8_t *d_err, void *stream);
+int qldpc_sample_errors_weight_host(int32_t weight, double px, double py, double pz, uint64_t seed,
+                                    uint64_t shot_begin, int64_t shot_count, int32_t n, uint8_t *err);
 
 /*
  * Random information-set minimum-distance search (distance.hip): what replaces the reference's

@@ -32,6 +32,8 @@ EXPORTED = [
     "qldpc_shard_range", "qldpc_bp_lds_model", "qldpc_m2s_place_model", "qldpc_bp_plan",
     "qldpc_circ_create_single_shot", "qldpc_circ_set_round_firstmin",
     "qldpc_dist_create", "qldpc_dist_run_host", "qldpc_dist_run", "qldpc_dist_geometry", "qldpc_dist_destroy",
+    "qldpc_mc_create_staged", "qldpc_mc_launch_weight", "qldpc_sample_errors_weight",
+    "qldpc_sample_errors_weight_host",
 ]
 BUILD_EXPERIMENTAL = 1  # qldpc_build_flags(): the measured-and-not-kept kernel families are compiled in
 COMM_ID_BYTES = 128
@@ -221,6 +223,15 @@ def _declare(L):
     L.qldpc_dist_geometry.argtypes = [_vp] + [ctypes.POINTER(_i32)] * 4
     L.qldpc_dist_destroy.restype = ctypes.c_int
     L.qldpc_dist_destroy.argtypes = [_vp]
+    L.qldpc_mc_create_staged.restype = ctypes.c_int
+    L.qldpc_mc_create_staged.argtypes = [_vp, _vp, _vp, _vp, _pp]
+    L.qldpc_mc_launch_weight.restype = ctypes.c_int
+    L.qldpc_mc_launch_weight.argtypes = [_vp, _i32, _dbl, _dbl, _dbl, _u64, _u64, _i64, _i32, _vp, _vp, _vp, _vp,
+                                         _vp, _vp]
+    L.qldpc_sample_errors_weight.restype = ctypes.c_int
+    L.qldpc_sample_errors_weight.argtypes = [_i32, _dbl, _dbl, _dbl, _u64, _u64, _i64, _i32, _vp, _vp]
+    L.qldpc_sample_errors_weight_host.restype = ctypes.c_int
+    L.qldpc_sample_errors_weight_host.argtypes = [_i32, _dbl, _dbl, _dbl, _u64, _u64, _i64, _i32, _vp]
 
 
 def lib():

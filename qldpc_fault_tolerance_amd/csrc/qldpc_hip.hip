@@ -1924,6 +1924,35 @@ static int build_lmask(const qldpc_graph* L, int n, DevBuf& buf, int& kw) {
   return 0;
 }
 
+// staged pipeline around decode_batch (staged.hip): any decoder pair
+static int mc_create_staged(qldpc_bp* dec_x, const qldpc_graph* logical_x, qldpc_bp* dec_z,
+                            const qldpc_graph* logical_z, qldpc_mc** out) {
+  qldpc_bp* d0 = dec_x ? dec_x : dec_z;
+  if (dec_x && dec_z && (dec_x->g->n != dec_z->g->n || dec_x->g->device != dec_z->g->device))
+    return set_err(QLDPC_EINVAL, "sector decoders differ in code length or device");
+  QLDPC_HIP(hipSetDevice(d0->g->device));
+  auto* mc = new qldpc_mc();
+  mc->dec[0] = dec_x;
+  mc->dec[1] = dec_z;
+  mc->route = d0->route;
+  int rc = mc->counters.alloc(sizeof(qldpc_counters));
+  if (!rc) rc = staged_mc_prepare(mc, logical_x, logical_z);
+  if (rc) {
+    staged_mc_release(mc);
+    mc->counters.release();
+    delete mc;
+    return rc;
+  }
+  *out = mc;
+  return 0;
+}
+
+int qldpc_mc_create_staged(qldpc_bp* dec_x, const qldpc_graph* logical_x, qldpc_bp* dec_z,
+                           const qldpc_graph* logical_z, qldpc_mc** out) {
+  if (!out || (!dec_x && !dec_z)) return set_err(QLDPC_EINVAL, "need at least one sector decoder");
+  return mc_create_staged(dec_x, logical_x, dec_z, logical_z, out);
+}
+
 int qldpc_mc_create(qldpc_bp* dec_x, const qldpc_graph* logical_x, qldpc_bp* dec_z, const qldpc_graph* logical_z,
                     qldpc_mc** out) {
   if (!out || (!dec_x && !dec_z)) return set_err(QLDPC_EINVAL, "need at least one sector decoder");
@@ -1941,25 +1970,7 @@ int qldpc_mc_create(qldpc_bp* dec_x, const qldpc_graph* logical_x, qldpc_bp* dec
                       // variable past it would run the 4-edge path and read the shared dummy slot)
                       (dec_x && dec_z && dec_x->route.m2s && dec_x->route.d3k != dec_z->route.d3k) ||
                       env_int("QLDPC_MC_STAGED", 0) == 1;
-  if (staged) {  // staged pipeline around decode_batch (staged.hip): any decoder pair
-    if (dec_x && dec_z && (dec_x->g->n != dec_z->g->n || dec_x->g->device != dec_z->g->device))
-      return set_err(QLDPC_EINVAL, "sector decoders differ in code length or device");
-    QLDPC_HIP(hipSetDevice(d0->g->device));
-    auto* mc = new qldpc_mc();
-    mc->dec[0] = dec_x;
-    mc->dec[1] = dec_z;
-    mc->route = d0->route;
-    int rc = mc->counters.alloc(sizeof(qldpc_counters));
-    if (!rc) rc = staged_mc_prepare(mc, logical_x, logical_z);
-    if (rc) {
-      staged_mc_release(mc);
-      mc->counters.release();
-      delete mc;
-      return rc;
-    }
-    *out = mc;
-    return 0;
-  }
+  if (staged) return mc_create_staged(dec_x, logical_x, dec_z, logical_z, out);
   if (dec_x && dec_z) {
     if (dec_x->g->n != dec_z->g->n) return set_err(QLDPC_EINVAL, "sector code lengths differ");
     if (dec_x->route.TB != dec_z->route.TB || dec_x->route.VPL != dec_z->route.VPL || dec_x->route.DMAX != dec_z->route.DMAX ||
@@ -2239,6 +2250,29 @@ int qldpc_mc_launch(qldpc_mc* mc, double px, double py, double pz, uint64_t seed
     }
   }
   return 0;
+}
+
+int qldpc_mc_launch_weight(qldpc_mc* mc, int32_t weight, double px, double py, double pz, uint64_t seed,
+                           uint64_t shot_begin, int64_t shot_count, int32_t logical_mode, void* d_counters,
+                           uint8_t* d_fail, uint8_t* d_err, uint8_t* d_corr, int32_t* d_iters, void* stream) {
+  if (!mc || !d_counters) return set_err(QLDPC_EINVAL, "NULL argument");
+  if (logical_mode < 0 || logical_mode > 2) return set_err(QLDPC_EINVAL, "logical_mode must be 0 (X), 1 (Z), 2 (Total)");
+  if (!mc->staged)
+    return set_err(QLDPC_ENOTSUP, "fixed-weight shots need a staged handle (qldpc_mc_create_staged)");
+  if (mc->osd[0] || mc->osd[1]) return set_err(QLDPC_ENOTSUP, "fixed-weight shots do not run the BP+OSD stage");
+  const qldpc_bp* d0 = mc->dec[0] ? mc->dec[0] : mc->dec[1];
+  StagedWeight fw;
+  fw.weight = weight;
+  if (int rc = weight_thresholds(weight, d0->g->n, px, py, pz, &fw.K1, &fw.K2)) return rc;
+  if (shot_count <= 0) return 0;
+  const bool need[2] = {logical_mode != 1, logical_mode != 0};
+  for (int q = 0; q < 2; ++q)
+    if (need[q] && !mc->dec[q])
+      return set_err(QLDPC_EINVAL, q == 0 ? "logical_mode needs the X sector (hz decoder)"
+                                          : "logical_mode needs the Z sector (hx decoder)");
+  QLDPC_HIP(hipSetDevice(d0->g->device));
+  return staged_mc_launch(mc, px, py, pz, seed, shot_begin, shot_count, logical_mode, nullptr, d_counters, d_fail,
+                          d_err, d_corr, d_iters, (hipStream_t)stream, &fw);
 }
 
 int qldpc_mc_run(qldpc_mc* mc, double px, double py, double pz, uint64_t seed, uint64_t shot_begin,

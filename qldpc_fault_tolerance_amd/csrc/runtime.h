@@ -153,8 +153,23 @@ int hbm_decode_launch(qldpc_bp* bp, const uint8_t* synd, uint8_t* corr, int32_t*
 // checks around qldpc_bp_decode_batch, for decoders the fused kernels do not serve
 int staged_mc_prepare(qldpc_mc* mc, const qldpc_graph* logical_x, const qldpc_graph* logical_z);
 void staged_mc_release(qldpc_mc* mc);
+// fixed-weight sampling (weight.hip) in place of the i.i.d. channel: weight and class thresholds
+struct StagedWeight {
+  int weight;
+  unsigned long long K1, K2;
+};
 int staged_mc_launch(qldpc_mc* mc, double px, double py, double pz, uint64_t seed, uint64_t shot_begin,
                      int64_t shot_count, int32_t logical_mode, const double* d_uniforms, void* d_counters,
-                     uint8_t* d_fail, uint8_t* d_err, uint8_t* d_corr, int32_t* d_iters, hipStream_t stream);
+                     uint8_t* d_fail, uint8_t* d_err, uint8_t* d_corr, int32_t* d_iters, hipStream_t stream,
+                     const StagedWeight* fixed = nullptr);
+
+// fixed-weight error sampler (weight.hip).  weight_thresholds: argument checks (QLDPC_EINVAL) and the
+// class thresholds K1 = ceil(2^53 pz / T), K2 = ceil(2^53 (pz + px) / T).  weight_sample_words: shots
+// shot0 .. shot0 + count - 1 into the bit-sliced [n][W] X / Z error words, every word overwritten.
+int weight_thresholds(int64_t weight, int64_t n, double px, double py, double pz, unsigned long long* K1,
+                      unsigned long long* K2);
+int weight_sample_words(int weight, unsigned long long K1, unsigned long long K2, uint64_t seed, uint64_t shot0,
+                        long long count, int n, int W, unsigned long long* cur_x, unsigned long long* cur_z,
+                        hipStream_t stream);
 
 }  // namespace qldpc_rt

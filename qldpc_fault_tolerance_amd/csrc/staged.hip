@@ -572,6 +572,7 @@ int qldpc_phenl_launch(qldpc_phenl* P, double px, double py, double pz, double q
 // pipeline: Philox sampling of both Pauli components with the fused kernels'
 // stream (kStreamData, ctr = (qubit, shot)) -> per needed sector: bit-sliced
 // H e, unpack, qldpc_bp_decode_batch, residual fold, [H; L] check -> tally.
+// qldpc_mc_launch_weight runs the same stages behind the fixed-weight sampler of weight.hip.
 namespace qldpc_rt {
 
 constexpr long long kStagedBatch = 1 << 16;
@@ -629,7 +630,8 @@ int staged_mc_prepare(qldpc_mc* mc, const qldpc_graph* logical_x, const qldpc_gr
 
 int staged_mc_launch(qldpc_mc* mc, double px, double py, double pz, uint64_t seed, uint64_t shot_begin,
                      int64_t shot_count, int32_t logical_mode, const double* d_uniforms, void* d_counters,
-                     uint8_t* d_fail, uint8_t* d_err, uint8_t* d_corr, int32_t* d_iters, hipStream_t st) {
+                     uint8_t* d_fail, uint8_t* d_err, uint8_t* d_corr, int32_t* d_iters, hipStream_t st,
+                     const StagedWeight* fixed) {
   const bool need[2] = {logical_mode != 1, logical_mode != 0};
   const qldpc_bp* d0 = mc->dec[0] ? mc->dec[0] : mc->dec[1];
   const int n = d0->g->n;
@@ -655,11 +657,18 @@ int staged_mc_launch(qldpc_mc* mc, double px, double py, double pz, uint64_t see
     const dim3 wgrid((W + kTile - 1) / kTile);
     for (int q = 0; q < 2; ++q) {
       A.cur[q] = static_cast<unsigned long long*>(mc->s_cur[q].p);
-      QLDPC_HIP(hipMemsetAsync(mc->s_cur[q].p, 0, (size_t)n * W * 8, st));
+      // (the fixed-weight sampler overwrites every error word of the batch; ph_sample xors into them)
+      if (!fixed) QLDPC_HIP(hipMemsetAsync(mc->s_cur[q].p, 0, (size_t)n * W * 8, st));
       QLDPC_HIP(hipMemsetAsync(mc->s_failw[q].p, 0, (size_t)W * 8, st));
     }
-    hipLaunchKernelGGL(ph_sample, dim3((unsigned)((B + kTile - 1) / kTile), (unsigned)n), dim3(kTile), 0, st, A);
-    QLDPC_HIP(hipGetLastError());
+    if (fixed) {
+      int rc = weight_sample_words(fixed->weight, fixed->K1, fixed->K2, seed, shot_begin + (uint64_t)c0, B, n, W,
+                                   A.cur[0], A.cur[1], st);
+      if (rc) return rc;
+    } else {
+      hipLaunchKernelGGL(ph_sample, dim3((unsigned)((B + kTile - 1) / kTile), (unsigned)n), dim3(kTile), 0, st, A);
+      QLDPC_HIP(hipGetLastError());
+    }
     if (d_err) {
       hipLaunchKernelGGL(ph_err_out, dim3((unsigned)((n + kTile - 1) / kTile), (unsigned)W), dim3(kTile), 0, st,
                          static_cast<const unsigned long long*>(mc->s_cur[0].p),

@@ -462,21 +462,24 @@ class DeviceMC:
     """Fused shot loop of ``CodeSimulator_DataError`` on one GPU (``qldpc_mc_*``).
 
     Sector X decodes X errors with the hz decoder and checks lz; sector Z
-    decodes Z errors with the hx decoder and checks lx.
+    decodes Z errors with the hx decoder and checks lx.  ``staged=True`` forces the staged
+    pipeline (``qldpc_mc_create_staged``), the one :meth:`launch_weight` runs on.
     """
 
-    def __init__(self, code: CSSCode, dec_x: DeviceBP | None, dec_z: DeviceBP | None):
+    def __init__(self, code: CSSCode, dec_x: DeviceBP | None, dec_z: DeviceBP | None, staged: bool = False):
         self.code = code
         self.dec_x, self.dec_z = dec_x, dec_z
         dev = (dec_x or dec_z).graph.device
         self.device = dev
+        self.staged = bool(staged)
         self.lz = DeviceGraph(code.csr("lz"), device=dev) if dec_x is not None else None
         self.lx = DeviceGraph(code.csr("lx"), device=dev) if dec_z is not None else None
         h = ctypes.c_void_p()
-        _native.check(_native.lib().qldpc_mc_create(
+        create = _native.lib().qldpc_mc_create_staged if staged else _native.lib().qldpc_mc_create
+        _native.check(create(
             dec_x.handle if dec_x else None, self.lz.handle if self.lz else None,
             dec_z.handle if dec_z else None, self.lx.handle if self.lx else None, ctypes.byref(h)),
-            "qldpc_mc_create")
+            "qldpc_mc_create_staged" if staged else "qldpc_mc_create")
         self.handle = h
 
     def set_osd(self, osd_x: "DeviceOSD | None", osd_z: "DeviceOSD | None"):
@@ -530,11 +533,77 @@ class DeviceMC:
             res.fail, res.err, res.corr, res.iters = f.cpu().numpy(), e.cpu().numpy(), c.cpu().numpy(), it.cpu().numpy()
         return res
 
+    def launch_weight(self, weight, px, py, pz, seed, shot_begin, shot_count, logical_mode="X", counters=None,
+                      fail=None, err=None, corr=None, iters=None, stream=None):
+        """:meth:`launch` on errors of fixed ``weight`` (``qldpc_mc_launch_weight``): uniform random
+        ``weight``-subsets of the qubits with Pauli classes in the ratio ``px : py : pz``.  Needs a
+        ``staged=True`` handle."""
+        torch = _torch()
+        if counters is None:
+            raise ValueError("counters buffer required")
+        mode = LOGICAL_MODES[logical_mode] if isinstance(logical_mode, str) else int(logical_mode)
+        s = stream if stream is not None else _stream_handle(torch, counters.device)
+
+        def ptr(t):
+            return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+        _native.check(_native.lib().qldpc_mc_launch_weight(
+            self.handle, int(weight), float(px), float(py), float(pz), int(seed) & (2**64 - 1), int(shot_begin),
+            int(shot_count), mode, ptr(counters), ptr(fail), ptr(err), ptr(corr), ptr(iters), s),
+            "qldpc_mc_launch_weight")
+
+    def run_weight(self, weight, px, py, pz, seed, shot_begin, shot_count, logical_mode="X",
+                   per_shot=False) -> MCResult:
+        torch = _torch()
+        dev = torch.device("cuda", self.device)
+        n = self.code.N
+        S = int(shot_count)
+        cnt = self.new_counters()
+        f = e = c = it = None
+        if per_shot:
+            f = torch.zeros(S, dtype=torch.uint8, device=dev)
+            e = torch.zeros((S, n), dtype=torch.uint8, device=dev)
+            c = torch.zeros((S, 2, n), dtype=torch.uint8, device=dev)
+            it = torch.zeros((S, 2), dtype=torch.int32, device=dev)
+        self.launch_weight(weight, px, py, pz, seed, shot_begin, S, logical_mode, cnt, f, e, c, it)
+        torch.cuda.synchronize(dev)
+        res = MCResult.from_words(cnt.cpu().numpy())
+        if per_shot:
+            res.fail, res.err, res.corr, res.iters = f.cpu().numpy(), e.cpu().numpy(), c.cpu().numpy(), it.cpu().numpy()
+        return res
+
     def __del__(self):
         h = getattr(self, "handle", None)
         if h and _native._lib is not None:
             _native.lib().qldpc_mc_destroy(h)
             self.handle = None
+
+
+def sample_errors_weight(n, weight, px, py, pz, seed, shot_begin, shot_count, host: bool = False,
+                         device: int | None = None, stream=None):
+    """``qldpc_sample_errors_weight``: ``shot_count`` errors of exactly ``weight`` non-zero Pauli
+    classes on ``n`` qubits, the sampler of :meth:`DeviceMC.launch_weight` alone, as a uint8
+    ``[S, n]`` device tensor (bit0 = x, bit1 = z).  ``host=True``: the same law in plain C++
+    (``qldpc_sample_errors_weight_host``, no GPU needed) as a numpy array."""
+    S = int(shot_count)
+    args = (int(weight), float(px), float(py), float(pz), int(seed) & (2**64 - 1), int(shot_begin), S, int(n))
+    if host:
+        out = np.zeros((max(S, 0), max(int(n), 0)), dtype=np.uint8)
+        _native.check(_native.lib().qldpc_sample_errors_weight_host(*args, out.ctypes.data_as(ctypes.c_void_p)),
+                      "qldpc_sample_errors_weight_host")
+        return out
+    torch = _torch()
+    if device is None:
+        from .parallel import local_device_index
+
+        device = local_device_index()
+    dev = torch.device("cuda", device)
+    out = torch.empty((S, int(n)), dtype=torch.uint8, device=dev)
+    s = stream if stream is not None else _stream_handle(torch, dev)
+    with torch.cuda.device(dev):
+        _native.check(_native.lib().qldpc_sample_errors_weight(*args, ctypes.c_void_p(out.data_ptr()), s),
+                      "qldpc_sample_errors_weight")
+    return out
 
 
 def sample_errors(n, px, py, pz, seed, shot_begin, shot_count, uniforms=None, device: int | None = None,
