@@ -17,6 +17,8 @@ from .codes import CSR, CSSCode
 
 METHODS = {"product_sum": 0, "prod_sum": 0, "ps": 0, "minimum_sum": 1, "min_sum": 1, "ms": 1}
 LOGICAL_MODES = {"X": 0, "Z": 1, "Total": 2}
+OSD_METHODS = {"osd_0": 0, "osd0": 0, "osd_e": 1, "osde": 1, "exhaustive": 1, "osd_cs": 2, "osdcs": 2,
+               "combination_sweep": 2}
 
 
 def _torch():
@@ -31,6 +33,75 @@ def _stream_handle(torch, device):
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
+def _stream(stream, device):
+    """``stream`` as given, or the current HIP stream of ``device``."""
+    torch = _torch()
+    return stream if stream is not None else _stream_handle(torch, device)
+
+
+def _ptr(t):
+    """Device address of a tensor as ``c_void_p``; None stays None (an optional ABI buffer)."""
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _np_ptr(a):
+    return a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _handle(obj):
+    """The C handle of an optional engine object."""
+    return obj.handle if obj is not None else None
+
+
+def _seed64(seed) -> int:
+    return int(seed) & (2**64 - 1)
+
+
+def _logical_mode(logical_mode) -> int:
+    return LOGICAL_MODES[logical_mode] if isinstance(logical_mode, str) else int(logical_mode)
+
+
+def _device_index(device):
+    """``device``, or this rank's GPU (LOCAL_RANK under torch.distributed.run) for None."""
+    if device is None:
+        from .parallel import local_device_index
+
+        device = local_device_index()
+    return device
+
+
+def _new_counters(device):
+    """A zeroed ``qldpc_counters`` image (int64 words) on GPU ``device``."""
+    torch = _torch()
+    return torch.zeros(_native.COUNTER_WORDS, dtype=torch.int64, device=torch.device("cuda", device))
+
+
+def _launch_prep(counters, logical_mode, stream):
+    """(mode, stream) of a fused launch that accumulates into ``counters``."""
+    torch = _torch()
+    if counters is None:
+        raise ValueError("counters buffer required")
+    return _logical_mode(logical_mode), (stream if stream is not None else _stream_handle(torch, counters.device))
+
+
+def _syndromes(synd, m=None):
+    """``synd`` as a contiguous uint8 0/1 array [B, m]; with ``m``, the width is checked."""
+    s = np.ascontiguousarray(np.atleast_2d(np.asarray(synd)).astype(np.int64) % 2, dtype=np.uint8)
+    if m is not None and s.shape[1] != m:
+        raise ValueError(f"syndrome length {s.shape[1]} != number of checks {m}")
+    return s
+
+
+def _channel_probs(channel_probs, n, check_length=True):
+    """A scalar or a length-``n`` vector of priors as a contiguous float64 vector."""
+    probs = np.asarray(channel_probs, dtype=np.float64)
+    if probs.ndim == 0:
+        probs = np.full(n, float(probs))
+    if check_length and probs.shape != (n,):
+        raise ValueError(f"channel_probs must have length {n}")
+    return np.ascontiguousarray(probs)
+
+
 def bp_method_code(bp_method) -> int:
     if isinstance(bp_method, (int, np.integer)):
         return int(bp_method)
@@ -40,46 +111,81 @@ def bp_method_code(bp_method) -> int:
     return METHODS[key]
 
 
-class DeviceGraph:
-    """A parity-check matrix uploaded once (``qldpc_graph_create``)."""
+def osd_method_code(osd_method) -> int:
+    if isinstance(osd_method, (int, np.integer)):
+        return int(osd_method)
+    key = str(osd_method).lower()
+    if key not in OSD_METHODS:
+        raise ValueError(f"unknown osd_method {osd_method!r}")
+    return OSD_METHODS[key]
 
-    def __init__(self, H, device: int | None = None):
-        c = H if isinstance(H, CSR) else CSR.from_dense(H)
-        if device is None:  # this rank's GPU (LOCAL_RANK under torch.distributed.run)
-            from .parallel import local_device_index
 
-            device = local_device_index()
-        self.csr = c
-        self.m, self.n = c.m, c.n
-        self.device = device
-        L = _native.lib()
-        self._rp = np.ascontiguousarray(c.row_ptr, dtype=np.int32)
-        self._ci = np.ascontiguousarray(c.col_idx, dtype=np.int32)
+class _Handle:
+    """Owner of one C-ABI handle: ``_create`` fills ``handle``, ``__del__`` frees it with the
+    library function the class names in ``_destroy``."""
+
+    _destroy = None
+
+    def _create(self, what: str, *args):
+        """``handle`` from the library's ``what(*args, &handle)``."""
         h = ctypes.c_void_p()
-        _native.check(L.qldpc_graph_create(device, c.m, c.n, self._rp.ctypes.data_as(ctypes.c_void_p),
-                                           self._ci.ctypes.data_as(ctypes.c_void_p), ctypes.byref(h)),
-                      "qldpc_graph_create")
+        _native.check(getattr(_native.lib(), what)(*args, ctypes.byref(h)), what)
         self.handle = h
 
-    def info(self):
-        v = [ctypes.c_int32() for _ in range(5)]
-        _native.check(_native.lib().qldpc_graph_info(self.handle, *[ctypes.byref(x) for x in v]), "graph_info")
-        return dict(zip(["m", "n", "nnz", "max_row_deg", "max_col_deg"], [x.value for x in v]))
+    def _ints(self, fn: str, what: str, count: int) -> list:
+        """The ``count`` int32 values the library's ``fn(handle, &v0, &v1, ..)`` reports."""
+        v = [ctypes.c_int32() for _ in range(count)]
+        _native.check(getattr(_native.lib(), fn)(self.handle, *[ctypes.byref(x) for x in v]), what)
+        return [x.value for x in v]
 
     def __del__(self):
         h = getattr(self, "handle", None)
-        if h and _native._lib is not None:
-            _native.lib().qldpc_graph_destroy(h)
+        if h and _native._lib is not None:  # the library is gone at interpreter shutdown
+            getattr(_native.lib(), self._destroy)(h)
             self.handle = None
 
 
-class DeviceBP:
+def _decode_buffers(graph, synd, check_width=True):
+    """(torch, device, syndromes [B, m], corrections [B, n], iterations [B], converged [B]) on
+    ``graph``'s GPU: the host syndromes normalised and uploaded, and the output buffers of one
+    batched decode."""
+    torch = _torch()
+    s = _syndromes(synd, graph.m if check_width else None)
+    B = s.shape[0]
+    dev = torch.device("cuda", graph.device)
+    return (torch, dev, torch.from_numpy(s).to(dev), torch.empty((B, graph.n), dtype=torch.uint8, device=dev),
+            torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.uint8, device=dev))
+
+
+class DeviceGraph(_Handle):
+    """A parity-check matrix uploaded once (``qldpc_graph_create``)."""
+
+    _destroy = "qldpc_graph_destroy"
+
+    def __init__(self, H, device: int | None = None):
+        c = H if isinstance(H, CSR) else CSR.from_dense(H)
+        device = _device_index(device)
+        self.csr = c
+        self.m, self.n = c.m, c.n
+        self.device = device
+        self._rp = np.ascontiguousarray(c.row_ptr, dtype=np.int32)
+        self._ci = np.ascontiguousarray(c.col_idx, dtype=np.int32)
+        self._create("qldpc_graph_create", device, c.m, c.n, _np_ptr(self._rp), _np_ptr(self._ci))
+
+    def info(self):
+        return dict(zip(["m", "n", "nnz", "max_row_deg", "max_col_deg"],
+                        self._ints("qldpc_graph_info", "graph_info", 5)))
+
+
+class DeviceBP(_Handle):
     """``ldpc.bp_decoder`` equivalent on the GPU (``qldpc_bp_create``).
 
     ``anneal_iters``: moves of the annealed V-slot placement the fp64 engine-3 families run at
     creation (host time, one core: ~0.18 us per move; default 4000 per edge capped at 2^25, memoised
     per process for the same graph).  0 keeps the greedy placement (decodes identically; the placement
     only moves LDS bank conflicts), for short runs over many codes."""
+
+    _destroy = "qldpc_bp_destroy"
 
     def __init__(self, H, channel_probs, max_iter: int = 0, bp_method="minimum_sum", ms_scaling_factor=0.625,
                  precision: int = 64, vars_per_thread: int = 0, device: int | None = None, graph: DeviceGraph | None = None,
@@ -98,37 +204,25 @@ class DeviceBP:
             return
         self.graph = graph if graph is not None else DeviceGraph(H, device=device)
         n = self.graph.n
-        probs = np.asarray(channel_probs, dtype=np.float64)
-        if probs.ndim == 0:
-            probs = np.full(n, float(probs))
-        if probs.shape != (n,):
-            raise ValueError(f"channel_probs must have length {n}")
-        self.channel_probs = np.ascontiguousarray(probs)
+        self.channel_probs = _channel_probs(channel_probs, n)
         self.max_iter = int(max_iter) if int(max_iter) > 0 else n
         self.bp_method = bp_method_code(bp_method)
         self.ms_scaling_factor = float(ms_scaling_factor)
         self.precision = int(precision)
         self.soft = bool(soft)
-        h = ctypes.c_void_p()
+        common = (self.graph.handle, _np_ptr(self.channel_probs), self.max_iter)
         if hbm:
             # engine 6: HBM-resident messages (automatic when no LDS engine holds the image)
             if self.bp_method != 1:
                 raise NotImplementedError("the HBM-resident engine implements minimum_sum")
-            _native.check(_native.lib().qldpc_bp_create_hbm(
-                self.graph.handle, self.channel_probs.ctypes.data_as(ctypes.c_void_p), self.max_iter,
-                self.ms_scaling_factor, self.precision, ctypes.byref(h)), "qldpc_bp_create_hbm")
+            self._create("qldpc_bp_create_hbm", *common, self.ms_scaling_factor, self.precision)
         elif self.soft and self.bp_method == 1:
             # BP+OSD: engine 1 hands back the final posteriors (qldpc_bp_create_soft); a product-sum
             # decoder (engine 5) writes ldpc's log(1 / ratio) posteriors from the default create
-            _native.check(_native.lib().qldpc_bp_create_soft(
-                self.graph.handle, self.channel_probs.ctypes.data_as(ctypes.c_void_p), self.max_iter,
-                self.ms_scaling_factor, self.precision, ctypes.byref(h)), "qldpc_bp_create_soft")
+            self._create("qldpc_bp_create_soft", *common, self.ms_scaling_factor, self.precision)
         else:
-            _native.check(_native.lib().qldpc_bp_create(
-                self.graph.handle, self.channel_probs.ctypes.data_as(ctypes.c_void_p), self.max_iter,
-                self.bp_method, self.ms_scaling_factor, self.precision, int(vars_per_thread), int(min_col_slots),
-                ctypes.byref(h)), "qldpc_bp_create")
-        self.handle = h
+            self._create("qldpc_bp_create", *common, self.bp_method, self.ms_scaling_factor, self.precision,
+                         int(vars_per_thread), int(min_col_slots))
 
     @property
     def m(self):
@@ -139,23 +233,12 @@ class DeviceBP:
         return self.graph.n
 
     def geometry(self):
-        v = [ctypes.c_int32() for _ in range(4)]
-        _native.check(_native.lib().qldpc_bp_geometry(self.handle, *[ctypes.byref(x) for x in v]), "bp_geometry")
-        e = ctypes.c_int32()
-        _native.check(_native.lib().qldpc_bp_engine(self.handle, ctypes.byref(e)), "bp_engine")
-        g = dict(zip(["threads", "vars_per_thread", "lds_bytes", "blocks_per_cu"], [x.value for x in v]))
-        g["engine"] = e.value
-        d = ctypes.c_int32()
-        _native.check(_native.lib().qldpc_bp_degree3_slots(self.handle, ctypes.byref(d)), "bp_degree3_slots")
-        g["degree3_slots"] = d.value
-        b0, b1 = ctypes.c_int32(), ctypes.c_int32()
-        _native.check(_native.lib().qldpc_bp_bank_stats(self.handle, ctypes.byref(b0), ctypes.byref(b1)),
-                      "bp_bank_stats")
-        g["gather_conflicts"] = (b0.value, b1.value)
-        kid, nch = ctypes.c_int32(), ctypes.c_int32()
-        _native.check(_native.lib().qldpc_bp_kernel_id(self.handle, ctypes.byref(kid), ctypes.byref(nch)),
-                      "bp_kernel_id")
-        g["kernel_id"], g["row_chunks"] = kid.value, nch.value
+        g = dict(zip(["threads", "vars_per_thread", "lds_bytes", "blocks_per_cu"],
+                     self._ints("qldpc_bp_geometry", "bp_geometry", 4)))
+        g["engine"], = self._ints("qldpc_bp_engine", "bp_engine", 1)
+        g["degree3_slots"], = self._ints("qldpc_bp_degree3_slots", "bp_degree3_slots", 1)
+        g["gather_conflicts"] = tuple(self._ints("qldpc_bp_bank_stats", "bp_bank_stats", 2))
+        g["kernel_id"], g["row_chunks"] = self._ints("qldpc_bp_kernel_id", "bp_kernel_id", 2)
         lm = (ctypes.c_int64 * 6)()
         _native.check(_native.lib().qldpc_bp_lds_model(self.handle, lm), "bp_lds_model")
         g["lds_model"] = dict(zip(["cs_gather", "cs_gather_extra", "v_read", "v_read_extra", "v_store", "v_store_extra"],
@@ -168,54 +251,34 @@ class DeviceBP:
         B = int(synd_dev.shape[0])
         assert synd_dev.dtype == torch.uint8 and synd_dev.is_contiguous() and synd_dev.shape[1] == self.m
         assert corr_dev.dtype == torch.uint8 and corr_dev.is_contiguous() and tuple(corr_dev.shape) == (B, self.n)
-        s = stream if stream is not None else _stream_handle(torch, synd_dev.device)
         _native.check(_native.lib().qldpc_bp_decode_batch(
-            self.handle, ctypes.c_void_p(synd_dev.data_ptr()), ctypes.c_void_p(corr_dev.data_ptr()),
-            ctypes.c_void_p(iters_dev.data_ptr()) if iters_dev is not None else None,
-            ctypes.c_void_p(conv_dev.data_ptr()) if conv_dev is not None else None, B, s), "qldpc_bp_decode_batch")
+            self.handle, _ptr(synd_dev), _ptr(corr_dev), _ptr(iters_dev), _ptr(conv_dev), B,
+            _stream(stream, synd_dev.device)), "qldpc_bp_decode_batch")
 
     def decode_batch(self, synd):
         """Host convenience: ``synd`` [B, m] (0/1) -> (corr [B, n] int, iters [B], converged [B])."""
-        torch = _torch()
-        s = np.ascontiguousarray(np.atleast_2d(np.asarray(synd)).astype(np.int64) % 2, dtype=np.uint8)
-        if s.shape[1] != self.m:
-            raise ValueError(f"syndrome length {s.shape[1]} != number of checks {self.m}")
-        dev = torch.device("cuda", self.graph.device)
-        sd = torch.from_numpy(s).to(dev)
-        corr = torch.empty((s.shape[0], self.n), dtype=torch.uint8, device=dev)
-        iters = torch.empty(s.shape[0], dtype=torch.int32, device=dev)
-        conv = torch.empty(s.shape[0], dtype=torch.uint8, device=dev)
+        torch, dev, sd, corr, iters, conv = _decode_buffers(self.graph, synd)
         self.decode_batch_device(sd, corr, iters, conv)
         torch.cuda.synchronize(dev)
         return corr.cpu().numpy().astype(np.int64), iters.cpu().numpy(), conv.cpu().numpy().astype(bool)
 
+    def _decode_soft_device(self, sd, corr, iters, conv, stream):
+        """Soft decode of device syndromes ``sd`` (async); returns the posteriors [B, n] float64."""
+        torch = _torch()
+        post = torch.empty(corr.shape, dtype=torch.float64, device=sd.device)
+        _native.check(_native.lib().qldpc_bp_decode_batch_soft(
+            self.handle, _ptr(sd), _ptr(corr), _ptr(iters), _ptr(conv), _ptr(post), sd.shape[0], stream),
+            "qldpc_bp_decode_batch_soft")
+        return post
+
     def decode_batch_soft(self, synd):
         """Like :meth:`decode_batch` plus the final posteriors ``post`` [B, n] float64
         (ldpc's ``log_prob_ratios``); needs ``soft=True``."""
-        torch = _torch()
-        s = np.ascontiguousarray(np.atleast_2d(np.asarray(synd)).astype(np.int64) % 2, dtype=np.uint8)
-        if s.shape[1] != self.m:
-            raise ValueError(f"syndrome length {s.shape[1]} != number of checks {self.m}")
-        B = s.shape[0]
-        dev = torch.device("cuda", self.graph.device)
-        sd = torch.from_numpy(s).to(dev)
-        corr = torch.empty((B, self.n), dtype=torch.uint8, device=dev)
-        iters = torch.empty(B, dtype=torch.int32, device=dev)
-        conv = torch.empty(B, dtype=torch.uint8, device=dev)
-        post = torch.empty((B, self.n), dtype=torch.float64, device=dev)
-        _native.check(_native.lib().qldpc_bp_decode_batch_soft(
-            self.handle, ctypes.c_void_p(sd.data_ptr()), ctypes.c_void_p(corr.data_ptr()),
-            ctypes.c_void_p(iters.data_ptr()), ctypes.c_void_p(conv.data_ptr()), ctypes.c_void_p(post.data_ptr()),
-            B, _stream_handle(torch, dev)), "qldpc_bp_decode_batch_soft")
+        torch, dev, sd, corr, iters, conv = _decode_buffers(self.graph, synd)
+        post = self._decode_soft_device(sd, corr, iters, conv, _stream_handle(torch, dev))
         torch.cuda.synchronize(dev)
         return (corr.cpu().numpy().astype(np.int64), iters.cpu().numpy(), conv.cpu().numpy().astype(bool),
                 post.cpu().numpy())
-
-    def __del__(self):
-        h = getattr(self, "handle", None)
-        if h and _native._lib is not None:
-            _native.lib().qldpc_bp_destroy(h)
-            self.handle = None
 
 
 def plan_bp(H, channel_probs, bp_method="minimum_sum", precision: int = 64, vars_per_thread: int = 0,
@@ -226,18 +289,13 @@ def plan_bp(H, channel_probs, bp_method="minimum_sum", precision: int = 64, vars
     graph = DeviceGraph(H, device=0)  # host-side handle; the plan never touches the device
     probs = np.ascontiguousarray(np.broadcast_to(np.asarray(channel_probs, dtype=np.float64), (graph.n,)))
     out = (ctypes.c_int32 * 8)()
-    _native.check(_native.lib().qldpc_bp_plan(graph.handle, probs.ctypes.data_as(ctypes.c_void_p),
-                                              bp_method_code(bp_method), int(precision), int(vars_per_thread),
-                                              int(min_col_slots), out, 8), "qldpc_bp_plan")
+    _native.check(_native.lib().qldpc_bp_plan(graph.handle, _np_ptr(probs), bp_method_code(bp_method), int(precision),
+                                              int(vars_per_thread), int(min_col_slots), out, 8), "qldpc_bp_plan")
     return dict(zip(["engine", "kernel_id", "row_chunks", "threads", "vars_per_thread", "lds_bytes", "degree3_slots",
                      "degree2_slots"], list(out)))
 
 
-OSD_METHODS = {"osd_0": 0, "osd0": 0, "osd_e": 1, "osde": 1, "exhaustive": 1, "osd_cs": 2, "osdcs": 2,
-               "combination_sweep": 2}
-
-
-class HostOSD:
+class HostOSD(_Handle):
     """Ordered-statistics post-processing stage (``qldpc_osd_*``, csrc/osd.hip).
 
     Native host code (GF(2) elimination on bit-packed columns, a std::thread
@@ -245,173 +303,114 @@ class HostOSD:
     library, not a GPU.
     """
 
+    _destroy = "qldpc_osd_destroy"
+
     def __init__(self, H, channel_probs, osd_method="osd_e", osd_order=10):
         c = H if isinstance(H, CSR) else CSR.from_dense(H)
         self.m, self.n = c.m, c.n
-        key = str(osd_method).lower() if not isinstance(osd_method, (int, np.integer)) else None
-        if key is not None and key not in OSD_METHODS:
-            raise ValueError(f"unknown osd_method {osd_method!r}")
-        self.osd_method = OSD_METHODS[key] if key is not None else int(osd_method)
+        self.osd_method = osd_method_code(osd_method)
         self.osd_order = int(osd_order)
-        probs = np.asarray(channel_probs, dtype=np.float64)
-        if probs.ndim == 0:
-            probs = np.full(self.n, float(probs))
-        self._probs = np.ascontiguousarray(probs)
+        self._probs = _channel_probs(channel_probs, self.n, check_length=False)
         rp = np.ascontiguousarray(c.row_ptr, dtype=np.int32)
         ci = np.ascontiguousarray(c.col_idx, dtype=np.int32)
-        h = ctypes.c_void_p()
-        _native.check(_native.lib().qldpc_osd_create(
-            self.m, self.n, rp.ctypes.data_as(ctypes.c_void_p), ci.ctypes.data_as(ctypes.c_void_p),
-            self._probs.ctypes.data_as(ctypes.c_void_p), self.osd_method, self.osd_order, ctypes.byref(h)),
-            "qldpc_osd_create")
-        self.handle = h
-        r = ctypes.c_int32()
-        _native.check(_native.lib().qldpc_osd_rank(h, ctypes.byref(r)), "qldpc_osd_rank")
-        self.rank = r.value
+        self._create("qldpc_osd_create", self.m, self.n, _np_ptr(rp), _np_ptr(ci), _np_ptr(self._probs),
+                     self.osd_method, self.osd_order)
+        self.rank, = self._ints("qldpc_osd_rank", "qldpc_osd_rank", 1)
 
     def decode_batch(self, synd, post, conv=None, bp_corr=None, threads: int = 0):
         """(osd0 [B, n], osdw [B, n]) uint8; converged rows (``conv``) copy ``bp_corr``."""
-        s = np.ascontiguousarray(np.atleast_2d(np.asarray(synd)).astype(np.int64) % 2, dtype=np.uint8)
+        s = _syndromes(synd, self.m)
         B = s.shape[0]
         pst = np.ascontiguousarray(np.asarray(post, dtype=np.float64).reshape(B, self.n))
-        if s.shape[1] != self.m:
-            raise ValueError(f"syndrome length {s.shape[1]} != number of checks {self.m}")
         cv = None if conv is None else np.ascontiguousarray(np.asarray(conv).reshape(B), dtype=np.uint8)
         bc = None if bp_corr is None else np.ascontiguousarray(np.asarray(bp_corr).reshape(B, self.n),
                                                                  dtype=np.uint8)
         o0 = np.zeros((B, self.n), np.uint8)
         ow = np.zeros((B, self.n), np.uint8)
-        vp = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+        vp = lambda a: None if a is None else _np_ptr(a)  # noqa: E731
         _native.check(_native.lib().qldpc_osd_decode_batch(self.handle, vp(s), vp(pst), vp(cv), vp(bc), vp(o0),
                                                            vp(ow), B, int(threads)), "qldpc_osd_decode_batch")
         return o0, ow
 
-    def __del__(self):
-        h = getattr(self, "handle", None)
-        if h and _native._lib is not None:
-            _native.lib().qldpc_osd_destroy(h)
-            self.handle = None
 
-
-class DeviceOSD:
+class DeviceOSD(_Handle):
     """OSD on the GPU (``qldpc_osd_gpu_*``): one workgroup per non-converged syndrome, fed
     straight from the soft-output BP's device buffers.  Uniform priors weigh candidates by
     popcount; non-uniform ones (the circuit-level DEM priors) by sum log(1/p_j) in column order,
     as the host stage.  ``supported`` says whether a graph qualifies (n <= 8192, osd_e order <= 24)."""
 
     MAX_N = 8192
+    _destroy = "qldpc_osd_gpu_destroy"
 
     @staticmethod
     def supported(n, channel_probs, osd_method, osd_order) -> bool:
         p = np.broadcast_to(np.asarray(channel_probs, dtype=np.float64), (n,))
-        key = str(osd_method).lower() if not isinstance(osd_method, (int, np.integer)) else None
-        meth = OSD_METHODS.get(key, -1) if key is not None else int(osd_method)
+        try:
+            meth = osd_method_code(osd_method)
+        except ValueError:
+            return False
         return (n <= DeviceOSD.MAX_N and bool(np.all((p > 0) & (p < 1))) and meth in (0, 1, 2)
                 and not (meth == 1 and int(osd_order) > 24))
 
     def __init__(self, graph: DeviceGraph, channel_probs, osd_method="osd_e", osd_order=10):
         self.graph = graph
-        n = graph.n
-        key = str(osd_method).lower() if not isinstance(osd_method, (int, np.integer)) else None
-        if key is not None and key not in OSD_METHODS:
-            raise ValueError(f"unknown osd_method {osd_method!r}")
-        self.osd_method = OSD_METHODS[key] if key is not None else int(osd_method)
+        self.osd_method = osd_method_code(osd_method)
         self.osd_order = int(osd_order)
-        probs = np.asarray(channel_probs, dtype=np.float64)
-        self._probs = np.ascontiguousarray(np.full(n, float(probs)) if probs.ndim == 0 else probs)
-        h = ctypes.c_void_p()
-        _native.check(_native.lib().qldpc_osd_gpu_create(graph.handle, self._probs.ctypes.data_as(ctypes.c_void_p),
-                                                         self.osd_method, self.osd_order, ctypes.byref(h)),
-                      "qldpc_osd_gpu_create")
-        self.handle = h
+        self._probs = _channel_probs(channel_probs, graph.n, check_length=False)
+        self._create("qldpc_osd_gpu_create", graph.handle, _np_ptr(self._probs), self.osd_method, self.osd_order)
 
     def geometry(self) -> dict:
         """The elimination layout the handle chose: register-row words, column-window words (0 =
         none), threads per workgroup and the persistent grid."""
-        v = [ctypes.c_int32() for _ in range(4)]
-        _native.check(_native.lib().qldpc_osd_gpu_geometry(self.handle, *[ctypes.byref(x) for x in v]),
-                      "qldpc_osd_gpu_geometry")
-        return dict(zip(("row_words", "window_words", "threads", "workgroups"), (x.value for x in v)))
+        return dict(zip(("row_words", "window_words", "threads", "workgroups"),
+                        self._ints("qldpc_osd_gpu_geometry", "qldpc_osd_gpu_geometry", 4)))
 
     def decode_device(self, synd_dev, post_dev, conv_dev, corr_dev, out0_dev, outw_dev, stream=None):
-        torch = _torch()
         B = int(synd_dev.shape[0])
-        s = stream if stream is not None else _stream_handle(torch, synd_dev.device)
-
-        def ptr(t):
-            return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-        _native.check(_native.lib().qldpc_osd_gpu_decode(self.handle, ptr(synd_dev), ptr(post_dev), ptr(conv_dev),
-                                                         ptr(corr_dev), ptr(out0_dev), ptr(outw_dev), B, s),
-                      "qldpc_osd_gpu_decode")
+        _native.check(_native.lib().qldpc_osd_gpu_decode(
+            self.handle, _ptr(synd_dev), _ptr(post_dev), _ptr(conv_dev), _ptr(corr_dev), _ptr(out0_dev),
+            _ptr(outw_dev), B, _stream(stream, synd_dev.device)), "qldpc_osd_gpu_decode")
 
     def bposd_batch(self, bp: "DeviceBP", synd, host_post: bool = True):
         """Soft BP (``bp``, soft=True) then GPU OSD, all on the device: ``synd`` [B, m] ->
         (osdw, osd0, bp_corr, iters, conv, post) as host arrays (``post`` stays a device
         tensor when ``host_post`` is False: 8 bytes per variable not worth copying back)."""
-        torch = _torch()
-        s = np.ascontiguousarray(np.atleast_2d(np.asarray(synd)).astype(np.int64) % 2, dtype=np.uint8)
-        B, n = s.shape[0], self.graph.n
-        dev = torch.device("cuda", self.graph.device)
-        sd = torch.from_numpy(s).to(dev)
-        corr = torch.empty((B, n), dtype=torch.uint8, device=dev)
-        iters = torch.empty(B, dtype=torch.int32, device=dev)
-        conv = torch.empty(B, dtype=torch.uint8, device=dev)
-        post = torch.empty((B, n), dtype=torch.float64, device=dev)
-        o0 = torch.empty((B, n), dtype=torch.uint8, device=dev)
-        ow = torch.empty((B, n), dtype=torch.uint8, device=dev)
+        torch, dev, sd, corr, iters, conv = _decode_buffers(self.graph, synd, check_width=False)
+        o0 = torch.empty_like(corr)
+        ow = torch.empty_like(corr)
         st = _stream_handle(torch, dev)
-        _native.check(_native.lib().qldpc_bp_decode_batch_soft(
-            bp.handle, ctypes.c_void_p(sd.data_ptr()), ctypes.c_void_p(corr.data_ptr()),
-            ctypes.c_void_p(iters.data_ptr()), ctypes.c_void_p(conv.data_ptr()), ctypes.c_void_p(post.data_ptr()),
-            B, st), "qldpc_bp_decode_batch_soft")
+        post = bp._decode_soft_device(sd, corr, iters, conv, st)
         self.decode_device(sd, post, conv, corr, o0, ow, st)
         torch.cuda.synchronize(dev)
         return (ow.cpu().numpy(), o0.cpu().numpy(), corr.cpu().numpy().astype(np.int64), iters.cpu().numpy(),
                 conv.cpu().numpy().astype(bool), post.cpu().numpy() if host_post else post)
 
-    def __del__(self):
-        h = getattr(self, "handle", None)
-        if h and _native._lib is not None:
-            _native.lib().qldpc_osd_gpu_destroy(h)
-            self.handle = None
 
-
-class DeviceFirstMin:
+class DeviceFirstMin(_Handle):
     """``FirstMinBPDecoder`` (``src/Decoders.py:49-74``) on the GPU (``qldpc_firstmin_*``): one-iteration
     min-sum BP repeated on the running syndrome while its weight does not grow, at most
     ``max_iter`` accepted steps, the whole loop in one kernel (one workgroup per syndrome)."""
 
+    _destroy = "qldpc_firstmin_destroy"
+
     def __init__(self, H, channel_probs, max_iter: int, ms_scaling_factor=0.625, precision: int = 64,
                  device: int | None = None, graph: DeviceGraph | None = None):
         self.graph = graph if graph is not None else DeviceGraph(H, device=device)
-        n = self.graph.n
-        probs = np.asarray(channel_probs, dtype=np.float64)
-        self._probs = np.ascontiguousarray(np.full(n, float(probs)) if probs.ndim == 0 else probs)
-        if self._probs.shape != (n,):
-            raise ValueError(f"channel_probs must have {n} entries")
+        self._probs = _channel_probs(channel_probs, self.graph.n)
         self.max_iter = int(max_iter)
-        h = ctypes.c_void_p()
-        _native.check(_native.lib().qldpc_firstmin_create(self.graph.handle, self._probs.ctypes.data_as(ctypes.c_void_p),
-                                                          self.max_iter, float(ms_scaling_factor), int(precision),
-                                                          ctypes.byref(h)), "qldpc_firstmin_create")
-        self.handle = h
+        self._create("qldpc_firstmin_create", self.graph.handle, _np_ptr(self._probs), self.max_iter,
+                     float(ms_scaling_factor), int(precision))
 
     def decode_device(self, synd_dev, corr_dev, steps_dev=None, stream=None):
-        torch = _torch()
-        s = stream if stream is not None else _stream_handle(torch, synd_dev.device)
         _native.check(_native.lib().qldpc_firstmin_decode(
-            self.handle, ctypes.c_void_p(synd_dev.data_ptr()), ctypes.c_void_p(corr_dev.data_ptr()),
-            ctypes.c_void_p(steps_dev.data_ptr()) if steps_dev is not None else None, int(synd_dev.shape[0]), s),
-            "qldpc_firstmin_decode")
+            self.handle, _ptr(synd_dev), _ptr(corr_dev), _ptr(steps_dev), int(synd_dev.shape[0]),
+            _stream(stream, synd_dev.device)), "qldpc_firstmin_decode")
 
     def decode_batch(self, synd):
         """[B, m] syndromes -> (corrections [B, n] int64, accepted steps [B] int32)."""
         torch = _torch()
-        S = np.ascontiguousarray(np.atleast_2d(np.asarray(synd)).astype(np.int64) % 2, dtype=np.uint8)
+        S = _syndromes(synd, self.graph.m)
         B, n = S.shape[0], self.graph.n
-        if S.shape[1] != self.graph.m:
-            raise ValueError(f"syndromes must have {self.graph.m} columns")
         dev = torch.device("cuda", self.graph.device)
         sd = torch.from_numpy(S).to(dev)
         corr = torch.empty((B, n), dtype=torch.uint8, device=dev)
@@ -419,12 +418,6 @@ class DeviceFirstMin:
         self.decode_device(sd, corr, steps)
         torch.cuda.synchronize(dev)
         return corr.cpu().numpy().astype(np.int64), steps.cpu().numpy()
-
-    def __del__(self):
-        h = getattr(self, "handle", None)
-        if h and _native._lib is not None:
-            _native.lib().qldpc_firstmin_destroy(h)
-            self.handle = None
 
 
 @dataclass
@@ -458,13 +451,44 @@ class MCResult:
                         [a + b for a, b in zip(self.sector_fail, o.sector_fail)], self.iter_hist + o.iter_hist)
 
 
-class DeviceMC:
+def _upload_uniforms(uniforms, device, shots, per_shot):
+    """External uniforms ``[shots, per_shot]`` (CPython ``random()`` values) as a float64 tensor on
+    GPU ``device``; None stays None (the kernels then draw from Philox)."""
+    torch = _torch()
+    if uniforms is None:
+        return None
+    u = torch.from_numpy(np.ascontiguousarray(uniforms, dtype=np.float64)).to(torch.device("cuda", device))
+    if tuple(u.shape) != (shots, per_shot):
+        raise ValueError(f"uniforms must be [{shots}, {per_shot}]")
+    return u
+
+
+def _run_and_read(device, launch, per_shot: dict) -> MCResult:
+    """One synchronous run of a fused loop on GPU ``device``: fresh counters, ``launch(counters,
+    *buffers)``, synchronise, the counters as an :class:`MCResult`.  ``per_shot`` maps MCResult
+    fields to (shape, dtype name) of the zeroed device buffers the launch fills, in the launch's
+    argument order; they are read back into those fields."""
+    torch = _torch()
+    dev = torch.device("cuda", device)
+    cnt = _new_counters(device)
+    bufs = [torch.zeros(shape, dtype=getattr(torch, dtype), device=dev) for shape, dtype in per_shot.values()]
+    launch(cnt, *bufs)
+    torch.cuda.synchronize(dev)
+    res = MCResult.from_words(cnt.cpu().numpy())
+    for name, b in zip(per_shot, bufs):
+        setattr(res, name, b.cpu().numpy())
+    return res
+
+
+class DeviceMC(_Handle):
     """Fused shot loop of ``CodeSimulator_DataError`` on one GPU (``qldpc_mc_*``).
 
     Sector X decodes X errors with the hz decoder and checks lz; sector Z
     decodes Z errors with the hx decoder and checks lx.  ``staged=True`` forces the staged
     pipeline (``qldpc_mc_create_staged``), the one :meth:`launch_weight` runs on.
     """
+
+    _destroy = "qldpc_mc_destroy"
 
     def __init__(self, code: CSSCode, dec_x: DeviceBP | None, dec_z: DeviceBP | None, staged: bool = False):
         self.code = code
@@ -474,109 +498,60 @@ class DeviceMC:
         self.staged = bool(staged)
         self.lz = DeviceGraph(code.csr("lz"), device=dev) if dec_x is not None else None
         self.lx = DeviceGraph(code.csr("lx"), device=dev) if dec_z is not None else None
-        h = ctypes.c_void_p()
-        create = _native.lib().qldpc_mc_create_staged if staged else _native.lib().qldpc_mc_create
-        _native.check(create(
-            dec_x.handle if dec_x else None, self.lz.handle if self.lz else None,
-            dec_z.handle if dec_z else None, self.lx.handle if self.lx else None, ctypes.byref(h)),
-            "qldpc_mc_create_staged" if staged else "qldpc_mc_create")
-        self.handle = h
+        self._create("qldpc_mc_create_staged" if staged else "qldpc_mc_create", _handle(dec_x), _handle(self.lz),
+                     _handle(dec_z), _handle(self.lx))
 
     def set_osd(self, osd_x: "DeviceOSD | None", osd_z: "DeviceOSD | None"):
         """BP+OSD in the fused loop (``qldpc_mc_set_osd``): decodes that reach max_iter go through the
         GPU OSD stage and their failures are re-checked on the device."""
         self._osd = (osd_x, osd_z)  # keep the handles alive
-        _native.check(_native.lib().qldpc_mc_set_osd(self.handle, osd_x.handle if osd_x is not None else None,
-                                                     osd_z.handle if osd_z is not None else None), "qldpc_mc_set_osd")
+        _native.check(_native.lib().qldpc_mc_set_osd(self.handle, _handle(osd_x), _handle(osd_z)), "qldpc_mc_set_osd")
 
     def new_counters(self):
-        torch = _torch()
-        return torch.zeros(_native.COUNTER_WORDS, dtype=torch.int64, device=torch.device("cuda", self.device))
+        return _new_counters(self.device)
 
     def launch(self, px, py, pz, seed, shot_begin, shot_count, logical_mode="X", counters=None, uniforms=None,
                fail=None, err=None, corr=None, iters=None, grid_blocks=0, stream=None):
         """Asynchronous launch on the current stream; counters accumulate in ``counters`` (device int64)."""
-        torch = _torch()
-        if counters is None:
-            raise ValueError("counters buffer required")
-        mode = LOGICAL_MODES[logical_mode] if isinstance(logical_mode, str) else int(logical_mode)
-        s = stream if stream is not None else _stream_handle(torch, counters.device)
-
-        def ptr(t):
-            return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
+        mode, s = _launch_prep(counters, logical_mode, stream)
         _native.check(_native.lib().qldpc_mc_launch(
-            self.handle, float(px), float(py), float(pz), int(seed) & (2**64 - 1), int(shot_begin), int(shot_count),
-            mode, ptr(uniforms), ptr(counters), ptr(fail), ptr(err), ptr(corr), ptr(iters), int(grid_blocks), s),
+            self.handle, float(px), float(py), float(pz), _seed64(seed), int(shot_begin), int(shot_count),
+            mode, _ptr(uniforms), _ptr(counters), _ptr(fail), _ptr(err), _ptr(corr), _ptr(iters), int(grid_blocks), s),
             "qldpc_mc_launch")
+
+    def _per_shot(self, shot_count, per_shot) -> dict:
+        """The per-shot buffers of :meth:`launch` / :meth:`launch_weight` for :func:`_run_and_read`."""
+        S, n = int(shot_count), self.code.N
+        if not per_shot:
+            return {}
+        return {"fail": (S, "uint8"), "err": ((S, n), "uint8"), "corr": ((S, 2, n), "uint8"), "iters": ((S, 2), "int32")}
 
     def run(self, px, py, pz, seed, shot_begin, shot_count, logical_mode="X", uniforms=None, per_shot=False,
             grid_blocks=0) -> MCResult:
-        torch = _torch()
-        dev = torch.device("cuda", self.device)
-        n = self.code.N
         S = int(shot_count)
-        cnt = self.new_counters()
-        u = torch.from_numpy(np.ascontiguousarray(uniforms, dtype=np.float64)).to(dev) if uniforms is not None else None
-        if u is not None and tuple(u.shape) != (S, n):
-            raise ValueError(f"uniforms must be [{S}, {n}]")
-        f = e = c = it = None
-        if per_shot:
-            f = torch.zeros(S, dtype=torch.uint8, device=dev)
-            e = torch.zeros((S, n), dtype=torch.uint8, device=dev)
-            c = torch.zeros((S, 2, n), dtype=torch.uint8, device=dev)
-            it = torch.zeros((S, 2), dtype=torch.int32, device=dev)
-        self.launch(px, py, pz, seed, shot_begin, S, logical_mode, cnt, u, f, e, c, it, grid_blocks)
-        torch.cuda.synchronize(dev)
-        res = MCResult.from_words(cnt.cpu().numpy())
-        if per_shot:
-            res.fail, res.err, res.corr, res.iters = f.cpu().numpy(), e.cpu().numpy(), c.cpu().numpy(), it.cpu().numpy()
-        return res
+        u = _upload_uniforms(uniforms, self.device, S, self.code.N)
+
+        def launch(cnt, *b):
+            self.launch(px, py, pz, seed, shot_begin, S, logical_mode, cnt, u, *(b or (None,) * 4), grid_blocks)
+
+        return _run_and_read(self.device, launch, self._per_shot(S, per_shot))
 
     def launch_weight(self, weight, px, py, pz, seed, shot_begin, shot_count, logical_mode="X", counters=None,
                       fail=None, err=None, corr=None, iters=None, stream=None):
         """:meth:`launch` on errors of fixed ``weight`` (``qldpc_mc_launch_weight``): uniform random
         ``weight``-subsets of the qubits with Pauli classes in the ratio ``px : py : pz``.  Needs a
         ``staged=True`` handle."""
-        torch = _torch()
-        if counters is None:
-            raise ValueError("counters buffer required")
-        mode = LOGICAL_MODES[logical_mode] if isinstance(logical_mode, str) else int(logical_mode)
-        s = stream if stream is not None else _stream_handle(torch, counters.device)
-
-        def ptr(t):
-            return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
+        mode, s = _launch_prep(counters, logical_mode, stream)
         _native.check(_native.lib().qldpc_mc_launch_weight(
-            self.handle, int(weight), float(px), float(py), float(pz), int(seed) & (2**64 - 1), int(shot_begin),
-            int(shot_count), mode, ptr(counters), ptr(fail), ptr(err), ptr(corr), ptr(iters), s),
+            self.handle, int(weight), float(px), float(py), float(pz), _seed64(seed), int(shot_begin),
+            int(shot_count), mode, _ptr(counters), _ptr(fail), _ptr(err), _ptr(corr), _ptr(iters), s),
             "qldpc_mc_launch_weight")
 
     def run_weight(self, weight, px, py, pz, seed, shot_begin, shot_count, logical_mode="X",
                    per_shot=False) -> MCResult:
-        torch = _torch()
-        dev = torch.device("cuda", self.device)
-        n = self.code.N
         S = int(shot_count)
-        cnt = self.new_counters()
-        f = e = c = it = None
-        if per_shot:
-            f = torch.zeros(S, dtype=torch.uint8, device=dev)
-            e = torch.zeros((S, n), dtype=torch.uint8, device=dev)
-            c = torch.zeros((S, 2, n), dtype=torch.uint8, device=dev)
-            it = torch.zeros((S, 2), dtype=torch.int32, device=dev)
-        self.launch_weight(weight, px, py, pz, seed, shot_begin, S, logical_mode, cnt, f, e, c, it)
-        torch.cuda.synchronize(dev)
-        res = MCResult.from_words(cnt.cpu().numpy())
-        if per_shot:
-            res.fail, res.err, res.corr, res.iters = f.cpu().numpy(), e.cpu().numpy(), c.cpu().numpy(), it.cpu().numpy()
-        return res
-
-    def __del__(self):
-        h = getattr(self, "handle", None)
-        if h and _native._lib is not None:
-            _native.lib().qldpc_mc_destroy(h)
-            self.handle = None
+        return _run_and_read(self.device, lambda cnt, *b: self.launch_weight(
+            weight, px, py, pz, seed, shot_begin, S, logical_mode, cnt, *b), self._per_shot(S, per_shot))
 
 
 def sample_errors_weight(n, weight, px, py, pz, seed, shot_begin, shot_count, host: bool = False,
@@ -586,23 +561,18 @@ def sample_errors_weight(n, weight, px, py, pz, seed, shot_begin, shot_count, ho
     ``[S, n]`` device tensor (bit0 = x, bit1 = z).  ``host=True``: the same law in plain C++
     (``qldpc_sample_errors_weight_host``, no GPU needed) as a numpy array."""
     S = int(shot_count)
-    args = (int(weight), float(px), float(py), float(pz), int(seed) & (2**64 - 1), int(shot_begin), S, int(n))
+    args = (int(weight), float(px), float(py), float(pz), _seed64(seed), int(shot_begin), S, int(n))
     if host:
         out = np.zeros((max(S, 0), max(int(n), 0)), dtype=np.uint8)
-        _native.check(_native.lib().qldpc_sample_errors_weight_host(*args, out.ctypes.data_as(ctypes.c_void_p)),
+        _native.check(_native.lib().qldpc_sample_errors_weight_host(*args, _np_ptr(out)),
                       "qldpc_sample_errors_weight_host")
         return out
     torch = _torch()
-    if device is None:
-        from .parallel import local_device_index
-
-        device = local_device_index()
-    dev = torch.device("cuda", device)
+    dev = torch.device("cuda", _device_index(device))
     out = torch.empty((S, int(n)), dtype=torch.uint8, device=dev)
-    s = stream if stream is not None else _stream_handle(torch, dev)
+    s = _stream(stream, dev)
     with torch.cuda.device(dev):
-        _native.check(_native.lib().qldpc_sample_errors_weight(*args, ctypes.c_void_p(out.data_ptr()), s),
-                      "qldpc_sample_errors_weight")
+        _native.check(_native.lib().qldpc_sample_errors_weight(*args, _ptr(out), s), "qldpc_sample_errors_weight")
     return out
 
 
@@ -613,11 +583,7 @@ def sample_errors(n, px, py, pz, seed, shot_begin, shot_count, uniforms=None, de
     ``[S, n]`` device tensor (bit0 = x, bit1 = z), from the Philox stream keyed by the
     global shot index or from external uniforms ``[S, n]`` (CPython ``random()`` values)."""
     torch = _torch()
-    if device is None:
-        from .parallel import local_device_index
-
-        device = local_device_index()
-    dev = torch.device("cuda", device)
+    dev = torch.device("cuda", _device_index(device))
     S = int(shot_count)
     out = torch.empty((S, int(n)), dtype=torch.uint8, device=dev)
     u = None
@@ -627,11 +593,10 @@ def sample_errors(n, px, py, pz, seed, shot_begin, shot_count, uniforms=None, de
         u = u.to(dev, dtype=torch.float64).contiguous()
         if tuple(u.shape) != (S, int(n)):
             raise ValueError(f"uniforms must be [{S}, {n}]")
-    s = stream if stream is not None else _stream_handle(torch, dev)
+    s = _stream(stream, dev)
     with torch.cuda.device(dev):
         _native.check(_native.lib().qldpc_sample_errors(
-            float(px), float(py), float(pz), int(seed) & (2**64 - 1), int(shot_begin), S, int(n),
-            ctypes.c_void_p(u.data_ptr()) if u is not None else None, ctypes.c_void_p(out.data_ptr()), s),
+            float(px), float(py), float(pz), _seed64(seed), int(shot_begin), S, int(n), _ptr(u), _ptr(out), s),
             "qldpc_sample_errors")
     return out
 
@@ -651,21 +616,22 @@ def run_sharded(mcs, comms, px, py, pz, seed, shot_begin, shot_count, logical_mo
             raise ValueError("one communicator per MC handle")
         carr = (ctypes.c_void_p * nd)(*[c.handle.value for c in comms])
     out = _native.Counters()
-    mode = LOGICAL_MODES[logical_mode] if isinstance(logical_mode, str) else int(logical_mode)
     _native.check(_native.lib().qldpc_mc_run_sharded(
         ctypes.cast(arr, ctypes.POINTER(ctypes.c_void_p)),
         ctypes.cast(carr, ctypes.POINTER(ctypes.c_void_p)) if carr is not None else None, nd, float(px), float(py),
-        float(pz), int(seed) & (2**64 - 1), int(shot_begin), int(shot_count), mode, ctypes.byref(out)),
+        float(pz), _seed64(seed), int(shot_begin), int(shot_count), _logical_mode(logical_mode), ctypes.byref(out)),
         "qldpc_mc_run_sharded")
     return MCResult.from_words(np.frombuffer(bytes(out), dtype=np.int64))
 
 
-class DevicePhenl:
+class DevicePhenl(_Handle):
     """Phenomenological space-time shot loop of ``CodeSimulator_Phenon_SpaceTime`` on one GPU (``qldpc_phenl_*``).
 
     ``st_x`` / ``st_z`` decode the X / Z detector histories on the space-time
     graphs of hz / hx; ``dec2_x`` / ``dec2_z`` decode the perfect final round.
     """
+
+    _destroy = "qldpc_phenl_destroy"
 
     def __init__(self, code: CSSCode, st_x: DeviceBP, st_z: DeviceBP, dec2_x: DeviceBP, dec2_z: DeviceBP,
                  num_rep: int, max_batch: int = 0):
@@ -676,11 +642,8 @@ class DevicePhenl:
         self.device = dev
         self.lz = DeviceGraph(code.csr("lz"), device=dev)
         self.lx = DeviceGraph(code.csr("lx"), device=dev)
-        h = ctypes.c_void_p()
-        _native.check(_native.lib().qldpc_phenl_create(
-            st_x.handle, st_z.handle, dec2_x.handle, dec2_z.handle, self.lz.handle, self.lx.handle, self.num_rep,
-            int(max_batch), ctypes.byref(h)), "qldpc_phenl_create")
-        self.handle = h
+        self._create("qldpc_phenl_create", st_x.handle, st_z.handle, dec2_x.handle, dec2_z.handle, self.lz.handle,
+                     self.lx.handle, self.num_rep, int(max_batch))
 
     def set_final_osd(self, osd_x: "DeviceOSD | None", osd_z: "DeviceOSD | None"):
         """BP+OSD final round (decoder2 = BPOSD_Decoder): ``qldpc_phenl_set_final_osd``."""
@@ -688,17 +651,15 @@ class DevicePhenl:
             if o is not None and o.graph.n != d.n:
                 raise ValueError("OSD graph does not match the final-round decoder")
         self._osd2 = (osd_x, osd_z)  # keep the handles alive
-        _native.check(_native.lib().qldpc_phenl_set_final_osd(
-            self.handle, osd_x.handle if osd_x is not None else None, osd_z.handle if osd_z is not None else None),
-            "qldpc_phenl_set_final_osd")
+        _native.check(_native.lib().qldpc_phenl_set_final_osd(self.handle, _handle(osd_x), _handle(osd_z)),
+                      "qldpc_phenl_set_final_osd")
 
     def set_round_firstmin(self, fm_x: "DeviceFirstMin | None", fm_z: "DeviceFirstMin | None"):
         """Noisy rounds decoded by FirstMinBPDecoder (``qldpc_phenl_set_round_firstmin``): each
         handle must be built on exactly its sector's space-time graph."""
         self._fm1 = (fm_x, fm_z)  # keep the handles alive
-        _native.check(_native.lib().qldpc_phenl_set_round_firstmin(
-            self.handle, fm_x.handle if fm_x is not None else None, fm_z.handle if fm_z is not None else None),
-            "qldpc_phenl_set_round_firstmin")
+        _native.check(_native.lib().qldpc_phenl_set_round_firstmin(self.handle, _handle(fm_x), _handle(fm_z)),
+                      "qldpc_phenl_set_round_firstmin")
 
     def trace_len(self, num_rounds: int) -> int:
         v = ctypes.c_int64()
@@ -711,56 +672,29 @@ class DevicePhenl:
         return ((num_rounds - 1) * self.num_rep + 1) * (c.N + c.hx.shape[0] + c.hz.shape[0])
 
     def new_counters(self):
-        torch = _torch()
-        return torch.zeros(_native.COUNTER_WORDS, dtype=torch.int64, device=torch.device("cuda", self.device))
+        return _new_counters(self.device)
 
     def launch(self, px, py, pz, q, seed, shot_begin, shot_count, num_rounds, logical_mode="Total", counters=None,
                uniforms=None, fail=None, trace=None, stream=None):
-        torch = _torch()
-        if counters is None:
-            raise ValueError("counters buffer required")
-        mode = LOGICAL_MODES[logical_mode] if isinstance(logical_mode, str) else int(logical_mode)
-        s = stream if stream is not None else _stream_handle(torch, counters.device)
-
-        def ptr(t):
-            return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
+        mode, s = _launch_prep(counters, logical_mode, stream)
         _native.check(_native.lib().qldpc_phenl_launch(
-            self.handle, float(px), float(py), float(pz), float(q), int(seed) & (2**64 - 1), int(shot_begin),
-            int(shot_count), int(num_rounds), mode, ptr(uniforms), ptr(counters), ptr(fail), ptr(trace), s),
+            self.handle, float(px), float(py), float(pz), float(q), _seed64(seed), int(shot_begin),
+            int(shot_count), int(num_rounds), mode, _ptr(uniforms), _ptr(counters), _ptr(fail), _ptr(trace), s),
             "qldpc_phenl_launch")
 
     def run(self, px, py, pz, q, seed, shot_begin, shot_count, num_rounds, logical_mode="Total", uniforms=None,
             per_shot=False) -> MCResult:
-        torch = _torch()
-        dev = torch.device("cuda", self.device)
         S = int(shot_count)
-        cnt = self.new_counters()
-        u = None
-        if uniforms is not None:
-            u = torch.from_numpy(np.ascontiguousarray(uniforms, dtype=np.float64)).to(dev)
-            if tuple(u.shape) != (S, self.uniforms_per_sample(num_rounds)):
-                raise ValueError(f"uniforms must be [{S}, {self.uniforms_per_sample(num_rounds)}]")
-        f = tr = None
-        if per_shot:
-            f = torch.zeros(S, dtype=torch.uint8, device=dev)
-            tr = torch.zeros((S, self.trace_len(num_rounds)), dtype=torch.uint8, device=dev)
-        self.launch(px, py, pz, q, seed, shot_begin, S, num_rounds, logical_mode, cnt, u, f, tr)
-        torch.cuda.synchronize(dev)
-        res = MCResult.from_words(cnt.cpu().numpy())
-        if per_shot:
-            res.fail = f.cpu().numpy()
-            res.trace = tr.cpu().numpy()
-        return res
+        u = _upload_uniforms(uniforms, self.device, S, self.uniforms_per_sample(num_rounds))
+        bufs = {"fail": (S, "uint8"), "trace": ((S, self.trace_len(num_rounds)), "uint8")} if per_shot else {}
 
-    def __del__(self):
-        h = getattr(self, "handle", None)
-        if h and _native._lib is not None:
-            _native.lib().qldpc_phenl_destroy(h)
-            self.handle = None
+        def launch(cnt, *b):
+            self.launch(px, py, pz, q, seed, shot_begin, S, num_rounds, logical_mode, cnt, u, *b)
+
+        return _run_and_read(self.device, launch, bufs)
 
 
-class DeviceCircuit:
+class DeviceCircuit(_Handle):
     """Circuit-level space-time shot loop of ``CodeSimulator_Circuit_SpaceTime`` on one GPU
     (``qldpc_circ_*``, csrc/circuit.hip).
 
@@ -775,19 +709,15 @@ class DeviceCircuit:
     """
 
     SAMPLERS = {"keyed": 0, "skip": 1}
+    _destroy = "qldpc_circ_destroy"
 
     def __init__(self, dem, dec1: "DeviceBP | None" = None, hs=None, L1=None, dec2: "DeviceBP | None" = None, L2=None,
                  num_rounds: int = 0, num_rep: int = 1, osd=None, max_batch: int = 0, device: int | None = None,
                  sampler: str = "skip"):
         sampler_only = dec1 is None and dec2 is None
-        if device is None:
-            if dec1 is not None:
-                device = dec1.graph.device
-            else:
-                from .parallel import local_device_index
-
-                device = local_device_index()
-        dev = device
+        if device is None and dec1 is not None:
+            device = dec1.graph.device
+        dev = _device_index(device)
         self.device = dev
         self.dem = dem
         self.decoders = (dec1, dec2)
@@ -796,19 +726,21 @@ class DeviceCircuit:
         self._g = [DeviceGraph(np.asarray(a, dtype=np.uint8) % 2, device=dev) for a in mats]
         self._probs = np.ascontiguousarray(np.asarray(dem.probs, dtype=np.float64))
         hd = (lambda i: None) if sampler_only else (lambda i: self._g[i].handle)  # noqa: E731
-        h = ctypes.c_void_p()
-        _native.check(_native.lib().qldpc_circ_create(
-            self._g[0].handle, self._g[1].handle, self._probs.ctypes.data_as(ctypes.c_void_p),
-            None if sampler_only else dec1.handle, hd(2), hd(3), None if sampler_only else dec2.handle, hd(4),
-            self.num_rounds, self.num_rep, int(max_batch), ctypes.byref(h)), "qldpc_circ_create")
-        self.handle = h
+        self._create("qldpc_circ_create", self._g[0].handle, self._g[1].handle, _np_ptr(self._probs),
+                     None if sampler_only else dec1.handle, hd(2), hd(3), None if sampler_only else dec2.handle, hd(4),
+                     self.num_rounds, self.num_rep, int(max_batch))
+        self._set_sampler_and_osd(sampler, osd)
+
+    def _set_sampler_and_osd(self, sampler, osd):
+        """The tail of construction: the DEM sampler and decoder2's OSD stage."""
         self.sampler = sampler
-        _native.check(_native.lib().qldpc_circ_set_sampler(h, self.SAMPLERS[sampler]), "qldpc_circ_set_sampler")
+        _native.check(_native.lib().qldpc_circ_set_sampler(self.handle, self.SAMPLERS[sampler]),
+                      "qldpc_circ_set_sampler")
         self._osd = osd
         if osd is not None:
             gpu = osd.handle if isinstance(osd, DeviceOSD) else None
             host = osd.handle if isinstance(osd, HostOSD) else None
-            _native.check(_native.lib().qldpc_circ_set_final_osd(h, gpu, host), "qldpc_circ_set_final_osd")
+            _native.check(_native.lib().qldpc_circ_set_final_osd(self.handle, gpu, host), "qldpc_circ_set_final_osd")
 
     @property
     def num_detectors(self) -> int:
@@ -819,19 +751,12 @@ class DeviceCircuit:
         return self.dem.num_observables
 
     def new_counters(self):
-        torch = _torch()
-        return torch.zeros(_native.COUNTER_WORDS, dtype=torch.int64, device=torch.device("cuda", self.device))
+        return _new_counters(self.device)
 
     def launch(self, seed, shot_begin, shot_count, counters, fail=None, detobs=None, stream=None):
-        torch = _torch()
-        s = stream if stream is not None else _stream_handle(torch, counters.device)
-
-        def ptr(t):
-            return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-        _native.check(_native.lib().qldpc_circ_launch(self.handle, int(seed) & (2**64 - 1), int(shot_begin),
-                                                      int(shot_count), ptr(counters), ptr(fail), ptr(detobs), s),
-                      "qldpc_circ_launch")
+        _native.check(_native.lib().qldpc_circ_launch(
+            self.handle, _seed64(seed), int(shot_begin), int(shot_count), _ptr(counters), _ptr(fail), _ptr(detobs),
+            _stream(stream, counters.device)), "qldpc_circ_launch")
 
     def sample(self, seed, shot_begin, shot_count):
         """Detector + observable bits [S, D + K] (uint8, host) of samples ``shot_begin..`` — the
@@ -840,35 +765,18 @@ class DeviceCircuit:
         dev = torch.device("cuda", self.device)
         S = int(shot_count)
         out = torch.zeros((S, self.num_detectors + self.num_observables), dtype=torch.uint8, device=dev)
-        _native.check(_native.lib().qldpc_circ_sample(self.handle, int(seed) & (2**64 - 1), int(shot_begin), S,
-                                                      ctypes.c_void_p(out.data_ptr()), _stream_handle(torch, dev)),
-                      "qldpc_circ_sample")
+        _native.check(_native.lib().qldpc_circ_sample(self.handle, _seed64(seed), int(shot_begin), S, _ptr(out),
+                                                      _stream_handle(torch, dev)), "qldpc_circ_sample")
         torch.cuda.synchronize(dev)
         return out.cpu().numpy()
 
     def run(self, seed, shot_begin, shot_count, per_shot: bool = False) -> "MCResult":
         """Counters of ``shot_count`` samples (``per_shot``: also ``fail`` [S] and the sampled
         detector / observable bits ``detobs`` [S, D + K] as host arrays)."""
-        torch = _torch()
-        dev = torch.device("cuda", self.device)
-        cnt = self.new_counters()
         S = int(shot_count)
-        fail = torch.zeros(S, dtype=torch.uint8, device=dev) if per_shot else None
-        detobs = torch.zeros((S, self.num_detectors + self.num_observables), dtype=torch.uint8, device=dev) \
-            if per_shot else None
-        self.launch(seed, shot_begin, S, cnt, fail, detobs)
-        torch.cuda.synchronize(dev)
-        res = MCResult.from_words(cnt.cpu().numpy())
-        if per_shot:
-            res.fail = fail.cpu().numpy()
-            res.detobs = detobs.cpu().numpy()
-        return res
-
-    def __del__(self):
-        h = getattr(self, "handle", None)
-        if h and _native._lib is not None:
-            _native.lib().qldpc_circ_destroy(h)
-            self.handle = None
+        bufs = {"fail": (S, "uint8"), "detobs": ((S, self.num_detectors + self.num_observables), "uint8")} \
+            if per_shot else {}
+        return _run_and_read(self.device, lambda cnt, *b: self.launch(seed, shot_begin, S, cnt, *b), bufs)
 
 
 def _dem_csr(rows_of, num_rows: int, num_cols: int):
@@ -910,25 +818,16 @@ class DeviceCircuitSingleShot(DeviceCircuit):
                 np.hstack([hx, np.zeros((m, m), np.uint8)]), np.hstack([lx, pad]), lx]
         self._g = [DeviceGraph(a, device=dev) for a in mats]
         self._probs = np.ascontiguousarray(np.asarray(dem.probs, dtype=np.float64))
-        h = ctypes.c_void_p()
-        _native.check(_native.lib().qldpc_circ_create_single_shot(
-            self._g[0].handle, self._g[1].handle, self._probs.ctypes.data_as(ctypes.c_void_p),
-            dec1.handle if dec1 is not None else None, self._g[2].handle, self._g[3].handle, dec2.handle,
-            self._g[4].handle, self.num_cycles, int(max_batch), ctypes.byref(h)), "qldpc_circ_create_single_shot")
-        self.handle = h
-        self.sampler = sampler
-        _native.check(_native.lib().qldpc_circ_set_sampler(h, self.SAMPLERS[sampler]), "qldpc_circ_set_sampler")
-        self._osd = osd
-        if osd is not None:
-            gpu = osd.handle if isinstance(osd, DeviceOSD) else None
-            host = osd.handle if isinstance(osd, HostOSD) else None
-            _native.check(_native.lib().qldpc_circ_set_final_osd(h, gpu, host), "qldpc_circ_set_final_osd")
+        self._create("qldpc_circ_create_single_shot", self._g[0].handle, self._g[1].handle, _np_ptr(self._probs),
+                     _handle(dec1), self._g[2].handle, self._g[3].handle, dec2.handle, self._g[4].handle,
+                     self.num_cycles, int(max_batch))
+        self._set_sampler_and_osd(sampler, osd)
         self._fm1 = None
         if firstmin is not None:
             self.set_round_firstmin(firstmin)
 
     def set_round_firstmin(self, fm: "DeviceFirstMin | None"):
         """Cycles decoded by FirstMinBPDecoder (``qldpc_circ_set_round_firstmin``); None: back to dec1."""
-        _native.check(_native.lib().qldpc_circ_set_round_firstmin(self.handle, fm.handle if fm is not None else None),
+        _native.check(_native.lib().qldpc_circ_set_round_firstmin(self.handle, _handle(fm)),
                       "qldpc_circ_set_round_firstmin")
         self._fm1 = fm  # keep the handle alive

@@ -198,7 +198,81 @@ def gf2_rows(csr, X):
     return (P.toarray() & 1).astype(np.uint8)
 
 
-class CodeSimulator_DataError:
+def _sector_failure(eval_logical_type, X_failure, Z_failure):
+    """The failure flag ``eval_logical_type`` asks for, of the two sectors' flags (0/1 ints, or bool
+    arrays with one entry per shot)."""
+    assert eval_logical_type in ["X", "Z", "Total"]
+    if eval_logical_type == "X":
+        return X_failure
+    if eval_logical_type == "Z":
+        return Z_failure
+    return X_failure | Z_failure
+
+
+def _css_failures(code, residual_x, residual_z):
+    """``(X_failure, Z_failure)`` of a sample from its residual errors: a sector fails when its
+    residual leaves a syndrome or flips a logical operator."""
+    X_failure = int(((code.hz @ residual_x) % 2).any() or ((code.lz @ residual_x) % 2).any())
+    Z_failure = int(((code.hx @ residual_z) % 2).any() or ((code.lx @ residual_z) % 2).any())
+    return X_failure, Z_failure
+
+
+def _adaptive_failures(batch_failures, target_failures, batch_size, max_batches):
+    """The adaptive sampling loop (``src/Simulators_SpaceTime.py:1051-1077``): batches of
+    ``batch_size`` samples, each counted by ``batch_failures(batch_size)``, until ``target_failures``
+    failures or ``max_batches`` batches; returns ``(fails, total)``.  Each batch's count is
+    all-reduced, so every rank stops at the same batch."""
+    total, fails = 0, 0
+    for _ in range(int(max_batches)):
+        fails += batch_failures(batch_size)
+        total += int(batch_size)
+        if fails >= target_failures:
+            break
+    return fails, total
+
+
+class _ShotStream:
+    """The shot accounting every simulator's device path shares.  A simulator draws its samples from
+    one global stream keyed by ``(seed, shot index)``: ``seed`` is fixed lazily (64 bits of Python's
+    ``random``), ``_shot_offset`` is the next unused index, and each run takes this rank's shard of
+    the next ``count`` indices and advances the offset by the global ``count``."""
+
+    def __init__(self, seed):
+        self.seed = int(seed) if seed is not None else None
+        self._shot_offset = 0
+        self.last_result = None
+
+    def _lazy_seed(self):
+        if self.seed is None:
+            self.seed = random.getrandbits(64)
+
+    def _next_shard(self, count):
+        """This rank's ``(begin, count)`` of the next ``count`` global shots; advances the offset."""
+        rank, ws = parallel.world()
+        b, c = parallel.shard_range(count, rank, ws, begin=self._shot_offset)
+        self._shot_offset += int(count)
+        return b, c
+
+    def _fused_run(self, device_loop, count, launch):
+        """``count`` global shots through one fused device loop: seed, build or fetch the loop
+        (``device_loop()``), shard, fresh counters, ``launch(loop, begin, count, counters)`` on this
+        rank's shard, one counter all-reduce, synchronise.  Returns the all-reduced
+        :class:`~.engine.MCResult`, also kept in ``last_result``."""
+        from . import engine
+
+        torch = engine._torch()
+        self._lazy_seed()
+        loop = device_loop()
+        b, c = self._next_shard(count)
+        cnt = loop.new_counters()
+        launch(loop, b, c, cnt)
+        parallel.allreduce_counters(cnt)
+        torch.cuda.synchronize(cnt.device)
+        self.last_result = engine.MCResult.from_words(cnt.cpu().numpy())
+        return self.last_result
+
+
+class CodeSimulator_DataError(_ShotStream):
     """Data-error simulator (``src/Simulators.py:75-188``).
 
     Extra keyword arguments (not in the reference): ``seed`` for the fused
@@ -216,11 +290,9 @@ class CodeSimulator_DataError:
         self.error_z = np.zeros(self.N).astype(int)
         self.min_logical_weight = self.N
         self.eval_logical_type = eval_logical_type
-        self.seed = int(seed) if seed is not None else None
-        self._shot_offset = 0
+        super().__init__(seed)
         self._mc = None
         self._mc_staged = None  # FailureSpectrum's own staged handle
-        self.last_result = None
         self.last_spectrum = None
 
     # -- reference per-shot API (plugin path) --------------------------------
@@ -238,17 +310,11 @@ class CodeSimulator_DataError:
         decoded_x = self.decoder_x.decode(synd_x)
         residual_x = (self.error_x + decoded_x) % 2
         residual_z = (self.error_z + decoded_z) % 2
-        X_failure = int(((code.hz @ residual_x) % 2).any() or ((code.lz @ residual_x) % 2).any())
-        Z_failure = int(((code.hx @ residual_z) % 2).any() or ((code.lx @ residual_z) % 2).any())
+        X_failure, Z_failure = _css_failures(code, residual_x, residual_z)
         for fail, r, L in ((X_failure, residual_x, code.lz), (Z_failure, residual_z, code.lx)):
             if fail and ((L @ r) % 2).any():
                 self.min_logical_weight = min(self.min_logical_weight, int(np.sum(r)))
-        assert self.eval_logical_type in ["X", "Z", "Total"]
-        if self.eval_logical_type == "X":
-            return X_failure
-        if self.eval_logical_type == "Z":
-            return Z_failure
-        return X_failure or Z_failure
+        return _sector_failure(self.eval_logical_type, X_failure, Z_failure)
 
     # -- fused engine path ----------------------------------------------------
     def _engine_ready(self):
@@ -270,23 +336,9 @@ class CodeSimulator_DataError:
         ok, bx, bz = self._engine_ready()
         if not ok:
             raise TypeError("fused path needs engine BPDecoder instances for the sectors eval_logical_type uses")
-        from .engine import MCResult, _torch
-
-        torch = _torch()
-        if self.seed is None:
-            self.seed = random.getrandbits(64)
-        mc = self._device_mc(bx, bz)
-        rank, ws = parallel.world()
-        b, c = parallel.shard_range(num_run, rank, ws, begin=self._shot_offset)
-        self._shot_offset += int(num_run)
         px, py, pz = self.channel_probs
-        cnt = mc.new_counters()
-        mc.launch(px, py, pz, self.seed, b, c, self.eval_logical_type, cnt)
-        parallel.allreduce_counters(cnt)
-        torch.cuda.synchronize(cnt.device)
-        res = MCResult.from_words(cnt.cpu().numpy())
-        self.last_result = res
-        return res
+        return self._fused_run(lambda: self._device_mc(bx, bz), num_run, lambda mc, b, c, cnt: mc.launch(
+            px, py, pz, self.seed, b, c, self.eval_logical_type, cnt))
 
     # -- weight-stratified estimate -------------------------------------------------
     def FailureSpectrum(self, weights, shots_per_weight: int):
@@ -308,20 +360,17 @@ class CodeSimulator_DataError:
         from .engine import DeviceMC, _torch
 
         torch = _torch()
-        if self.seed is None:
-            self.seed = random.getrandbits(64)
+        self._lazy_seed()
         if getattr(self, "_mc_staged", None) is None:
             self._mc_staged = DeviceMC(self.code, bx, bz, staged=True)
         mc = self._mc_staged
         weights = [int(w) for w in weights]
         S = int(shots_per_weight)
-        rank, ws = parallel.world()
         px, py, pz = self.channel_probs
         cnt = torch.zeros((max(1, len(weights)), _native.COUNTER_WORDS), dtype=torch.int64,
                           device=torch.device("cuda", mc.device))
         for i, w in enumerate(weights):
-            b, c = parallel.shard_range(S, rank, ws, begin=self._shot_offset)
-            self._shot_offset += S
+            b, c = self._next_shard(S)
             mc.launch_weight(w, px, py, pz, self.seed, b, c, self.eval_logical_type, cnt[i])
         parallel.allreduce_counters(cnt)
         torch.cuda.synchronize(cnt.device)
@@ -402,35 +451,30 @@ class CodeSimulator_DataError:
         return self._bposd_dev or None
 
     def _bposd_counts_device(self, num_run, batch, keep_shots, need_x, need_z):
-        from .engine import MCResult, _torch
+        from .engine import _torch
 
         torch = _torch()
-        if self.seed is None:
-            self.seed = random.getrandbits(64)
-        mc = self._bposd_dev
-        rank, ws = parallel.world()
-        b, c = parallel.shard_range(num_run, rank, ws, begin=self._shot_offset)
-        self._shot_offset += int(num_run)
         px, py, pz = self.channel_probs
-        dev = torch.device("cuda", mc.device)
-        cnt = mc.new_counters()
-        kept_e, kept_f = [], []
-        for s0 in range(b, b + c, int(batch)):
-            S = min(int(batch), b + c - s0)
-            f_d = e_d = None
+
+        def launch(mc, b, c, cnt):
+            dev = torch.device("cuda", mc.device)
+            kept_e, kept_f = [], []
+            for s0 in range(b, b + c, int(batch)):
+                S = min(int(batch), b + c - s0)
+                f_d = e_d = None
+                if keep_shots:
+                    f_d = torch.zeros(S, dtype=torch.uint8, device=dev)
+                    e_d = torch.zeros((S, self.N), dtype=torch.uint8, device=dev)
+                mc.launch(px, py, pz, self.seed, s0, S, self.eval_logical_type, cnt, None, f_d, e_d)
+                if keep_shots:
+                    f = f_d.cpu().numpy()
+                    kept_e.append(e_d.cpu().numpy())
+                    kept_f.append(np.stack([(f & 1) != 0, (f & 2) != 0], axis=1))
             if keep_shots:
-                f_d = torch.zeros(S, dtype=torch.uint8, device=dev)
-                e_d = torch.zeros((S, self.N), dtype=torch.uint8, device=dev)
-            mc.launch(px, py, pz, self.seed, s0, S, self.eval_logical_type, cnt, None, f_d, e_d)
-            if keep_shots:
-                f = f_d.cpu().numpy()
-                kept_e.append(e_d.cpu().numpy())
-                kept_f.append(np.stack([(f & 1) != 0, (f & 2) != 0], axis=1))
-        if keep_shots:
-            self.last_shots = (np.concatenate(kept_e) if kept_e else None, np.concatenate(kept_f) if kept_f else None)
-        parallel.allreduce_counters(cnt)
-        res = MCResult.from_words(cnt.cpu().numpy())
-        self.last_result = res
+                self.last_shots = (np.concatenate(kept_e) if kept_e else None,
+                                   np.concatenate(kept_f) if kept_f else None)
+
+        res = self._fused_run(lambda: self._bposd_dev, num_run, launch)
         return res.failures, res.shots, int(sum(res.sector_nonconv))
 
     def _bposd_counts_host(self, num_run: int, batch: int = 16384, keep_shots: bool = False):
@@ -438,17 +482,14 @@ class CodeSimulator_DataError:
         from .engine import DeviceMC, _torch
 
         torch = _torch()
-        if self.seed is None:
-            self.seed = random.getrandbits(64)
+        self._lazy_seed()
         need_x = self.eval_logical_type != "Z"
         need_z = self.eval_logical_type != "X"
         if getattr(self, "_bposd_mc", None) is None:
             self._bposd_mc = DeviceMC(self.code, self.decoder_x.decoder if need_x else None,
                                       self.decoder_z.decoder if need_z else None)
         mc = self._bposd_mc
-        rank, ws = parallel.world()
-        b, c = parallel.shard_range(num_run, rank, ws, begin=self._shot_offset)
-        self._shot_offset += int(num_run)
+        b, c = self._next_shard(num_run)
         px, py, pz = self.channel_probs
         code = self.code
         sectors = [(0, need_x, self.decoder_x, code.csr("hz"), code.csr("lz")),
@@ -483,19 +524,13 @@ class CodeSimulator_DataError:
                         f[ci[bad]] = gf2_rows(H, r).any(1) | gf2_rows(L, r).any(1)
                         osd_n += int(bad.size)
                 sf[:, q] = f
-            if self.eval_logical_type == "X":
-                fails += int(sf[:, 0].sum())
-            elif self.eval_logical_type == "Z":
-                fails += int(sf[:, 1].sum())
-            else:
-                fails += int((sf[:, 0] | sf[:, 1]).sum())
+            fails += int(_sector_failure(self.eval_logical_type, sf[:, 0], sf[:, 1]).sum())
             if keep_shots:
                 kept_e.append(e_d.cpu().numpy())
                 kept_f.append(sf)
         if keep_shots:
             self.last_shots = (np.concatenate(kept_e) if kept_e else None, np.concatenate(kept_f) if kept_f else None)
-        cnt = torch.tensor([fails, c, osd_n], dtype=torch.int64,
-                           device=torch.device("cuda", mc.device))
+        cnt = torch.tensor([fails, c, osd_n], dtype=torch.int64, device=dev)
         parallel.allreduce_counters(cnt)
         out = cnt.cpu().numpy()
         return int(out[0]), int(out[1]), int(out[2])
@@ -516,26 +551,100 @@ class CodeSimulator_DataError:
         src/Simulators_SpaceTime.py:1051-1077): batches of ``batch_size`` shots until
         ``target_failures`` failures or ``max_batches``; returns ``(wer, total_samples)``.
         Each batch's count is all-reduced, so every rank stops at the same batch."""
-        total, fails = 0, 0
-        for _ in range(int(max_batches)):
-            fails += self._batch_failures(batch_size)
-            total += int(batch_size)
-            if fails >= target_failures:
-                break
+        fails, total = _adaptive_failures(self._batch_failures, target_failures, batch_size, max_batches)
         return word_error_rate(fails, total, self.K)[0], total
 
 
 def word_error_rate_phenl(error_count: int, num_samples: int, K: int, num_rounds: int):
-    """``CodeSimulator_Phenon.WordErrorRate`` arithmetic (``src/Simulators.py:329-358``)."""
-    assert int(num_rounds) % 2 == 1
-    ler = error_count / num_samples
-    ler_q = 1.0 - (1 - ler) ** (1 / K)
-    if ler_q <= 0.5:
-        return (1.0 - (1 - 2 * ler_q) ** (1 / num_rounds)) / 2
-    return (1.0 + (-1 + 2 * ler_q) ** (1 / num_rounds)) / 2
+    """``CodeSimulator_Phenon.WordErrorRate`` arithmetic (``src/Simulators.py:329-358``): the per-cycle
+    formula over the ``num_rounds`` rounds."""
+    return word_error_rate_per_cycle(error_count, num_samples, K, num_rounds)
 
 
-class CodeSimulator_Phenon:
+class _PhenonBase(_ShotStream):
+    """What the two phenomenological simulators share: the constructor state, the error draw, the
+    perfect final round and the device path (``qldpc_phenl_launch``).  A subclass owns
+    ``_single_run``'s round loop, ``_engine_parts`` (which decoders the device loop takes), the
+    ``_fused_needs`` text and its WER formulas; ``num_rep`` is 1 unless it sets another."""
+
+    num_rep = 1
+    _fused_needs = None  # the TypeError text of fused_counts without engine decoders
+
+    def __init__(self, code, decoder1_x, decoder1_z, decoder2_x, decoder2_z, pauli_error_probs, q,
+                 eval_logical_type, seed, max_batch):
+        self.code = code
+        self.hx_ext = np.hstack([code.hx, np.identity(np.shape(code.hx)[0])])
+        self.hz_ext = np.hstack([code.hz, np.identity(np.shape(code.hz)[0])])
+        self.decoder1_z, self.decoder1_x = decoder1_z, decoder1_x
+        self.decoder2_z, self.decoder2_x = decoder2_z, decoder2_x
+        self.N = code.N
+        self.K = code.K
+        self.channel_probs = list(pauli_error_probs)
+        self.synd_prob = q
+        self.min_logical_weight = self.N
+        self.eval_logical_type = eval_logical_type
+        super().__init__(seed)
+        self.max_batch = int(max_batch)
+        self._ph = None
+
+    # -- reference per-sample API (plugin path) --------------------------------
+    def _generate_error(self):
+        """``src/Simulators.py:211-250`` / ``src/Simulators_SpaceTime.py:405-442``: data error (3-way
+        split), then hx-row and hz-row syndrome flips."""
+        N = self.N
+        u = np.array([random.random() for _ in range(N)])
+        ex, ez = pauli_split(u, self.channel_probs)
+        sz = np.array([random.random() < self.synd_prob for _ in range(self.hx_ext.shape[1] - N)], dtype=int)
+        sx = np.array([random.random() < self.synd_prob for _ in range(self.hz_ext.shape[1] - N)], dtype=int)
+        self.error_x_ext = np.concatenate([ex, sx])
+        self.error_z_ext = np.concatenate([ez, sz])
+        return self.error_x_ext, self.error_z_ext
+
+    def _final_round(self, cur_x, cur_z):
+        """The perfect last round: decoder2 on the data errors ``cur_x`` / ``cur_z``, then the failure
+        check of the residuals (the tail of both references' ``_single_run``)."""
+        code = self.code
+        dz = self.decoder2_z.decode(code.hx @ cur_z % 2)
+        dx = self.decoder2_x.decode(code.hz @ cur_x % 2)
+        return _sector_failure(self.eval_logical_type, *_css_failures(code, (cur_x + dx) % 2, (cur_z + dz) % 2))
+
+    # -- fused engine path ----------------------------------------------------
+    def _firstmin1(self):
+        """The noisy rounds' decoders as device first-min handles, or None (BP decodes them)."""
+        return None
+
+    def _final_osd(self):
+        return tuple(getattr(d, "gpu_osd", None) for d in (self.decoder2_x, self.decoder2_z))
+
+    def _device_phenl(self, parts):
+        from .engine import DevicePhenl
+
+        if self._ph is None:
+            self._ph = DevicePhenl(self.code, *parts, num_rep=self.num_rep, max_batch=self.max_batch)
+            ox, oz = self._final_osd()
+            if ox is not None or oz is not None:
+                self._ph.set_final_osd(ox, oz)
+            fm = self._firstmin1()
+            if fm is not None:
+                self._ph.set_round_firstmin(fm[0]._fm, fm[1]._fm)
+        return self._ph
+
+    def fused_counts(self, num_rounds: int, num_samples: int):
+        """Run ``num_samples`` samples on the GPU; returns the all-reduced :class:`~.engine.MCResult`."""
+        parts = self._engine_parts()
+        if parts is None:
+            raise TypeError(self._fused_needs)
+        px, py, pz = self.channel_probs
+        return self._fused_run(lambda: self._device_phenl(parts), num_samples, lambda ph, b, c, cnt: ph.launch(
+            px, py, pz, self.synd_prob, self.seed, b, c, num_rounds, self.eval_logical_type, cnt))
+
+    def _batch_failures(self, num_rounds: int, n: int) -> int:
+        if self._engine_parts() is not None:
+            return self.fused_counts(num_rounds, n).failures
+        return int(np.sum([self._single_run(num_rounds) for _ in range(n)]))
+
+
+class CodeSimulator_Phenon(_PhenonBase):
     """Single-shot phenomenological simulator (``src/Simulators.py:189-381``).
 
     Each noisy round decodes the extended syndrome ``[h | I]·[e | s_err]`` with
@@ -550,35 +659,12 @@ class CodeSimulator_Phenon:
 
     def __init__(self, code=None, decoder1_x=None, decoder1_z=None, decoder2_x=None, decoder2_z=None,
                  pauli_error_probs=(0.01, 0.01, 0.01), q=0, eval_logical_type="Total", seed=None, max_batch=0):
-        self.code = code
-        self.hx_ext = np.hstack([code.hx, np.identity(np.shape(code.hx)[0])])
-        self.hz_ext = np.hstack([code.hz, np.identity(np.shape(code.hz)[0])])
-        self.decoder1_z, self.decoder1_x = decoder1_z, decoder1_x
-        self.decoder2_z, self.decoder2_x = decoder2_z, decoder2_x
-        self.N = code.N
-        self.K = code.K
-        self.channel_probs = list(pauli_error_probs)
-        self.synd_prob = q
+        super().__init__(code, decoder1_x, decoder1_z, decoder2_x, decoder2_z, pauli_error_probs, q,
+                         eval_logical_type, seed, max_batch)
         self.error_x = np.zeros(self.N).astype(int)
         self.error_z = np.zeros(self.N).astype(int)
-        self.min_logical_weight = self.N
-        self.eval_logical_type = eval_logical_type
-        self.seed = int(seed) if seed is not None else None
-        self.max_batch = int(max_batch)
-        self._shot_offset = 0
-        self._ph = None
-        self.last_result = None
 
-    def _generate_error(self):
-        """``:211-250``: data error (3-way split), then hx-row and hz-row syndrome flips."""
-        N = self.N
-        u = np.array([random.random() for _ in range(N)])
-        ex, ez = pauli_split(u, self.channel_probs)
-        sz = np.array([random.random() < self.synd_prob for _ in range(self.hx_ext.shape[1] - N)], dtype=int)
-        sx = np.array([random.random() < self.synd_prob for _ in range(self.hz_ext.shape[1] - N)], dtype=int)
-        self.error_x_ext = np.concatenate([ex, sx])
-        self.error_z_ext = np.concatenate([ez, sz])
-        return self.error_x_ext, self.error_z_ext
+    _fused_needs = "fused path needs engine BPDecoder instances (decoder1 on [h | I], decoder2 on h)"
 
     def _single_run(self, num_rounds):
         """``:252-327``."""
@@ -596,19 +682,7 @@ class CodeSimulator_Phenon:
             cx = (cx + dx.astype(int)) % 2
             cz = (cz + dz.astype(int)) % 2
         ex_ext, ez_ext = self._generate_error()
-        cur_x = ((cx + ex_ext) % 2)[:N]
-        cur_z = ((cz + ez_ext) % 2)[:N]
-        dz = self.decoder2_z.decode(code.hx @ cur_z % 2)
-        dx = self.decoder2_x.decode(code.hz @ cur_x % 2)
-        rx, rz = (cur_x + dx) % 2, (cur_z + dz) % 2
-        X_failure = int(((code.hz @ rx) % 2).any() or ((code.lz @ rx) % 2).any())
-        Z_failure = int(((code.hx @ rz) % 2).any() or ((code.lx @ rz) % 2).any())
-        assert self.eval_logical_type in ["X", "Z", "Total"]
-        if self.eval_logical_type == "X":
-            return X_failure
-        if self.eval_logical_type == "Z":
-            return Z_failure
-        return X_failure or Z_failure
+        return self._final_round(((cx + ex_ext) % 2)[:N], ((cz + ez_ext) % 2)[:N])
 
     def _engine_parts(self):
         from .decoders import BPDecoder
@@ -639,53 +713,16 @@ class CodeSimulator_Phenon:
             return None
         return d1
 
-    def _final_osd(self):
-        return tuple(getattr(d, "gpu_osd", None) for d in (self.decoder2_x, self.decoder2_z))
-
-    def fused_counts(self, num_rounds: int, num_samples: int):
-        parts = self._engine_parts()
-        if parts is None:
-            raise TypeError("fused path needs engine BPDecoder instances (decoder1 on [h | I], decoder2 on h)")
-        from .engine import DevicePhenl, MCResult, _torch
-
-        torch = _torch()
-        if self.seed is None:
-            self.seed = random.getrandbits(64)
-        if self._ph is None:
-            self._ph = DevicePhenl(self.code, *parts, num_rep=1, max_batch=self.max_batch)
-            ox, oz = self._final_osd()
-            if ox is not None or oz is not None:
-                self._ph.set_final_osd(ox, oz)
-            fm = self._firstmin1()
-            if fm is not None:
-                self._ph.set_round_firstmin(fm[0]._fm, fm[1]._fm)
-        rank, ws = parallel.world()
-        b, c = parallel.shard_range(num_samples, rank, ws, begin=self._shot_offset)
-        self._shot_offset += int(num_samples)
-        px, py, pz = self.channel_probs
-        cnt = self._ph.new_counters()
-        self._ph.launch(px, py, pz, self.synd_prob, self.seed, b, c, num_rounds, self.eval_logical_type, cnt)
-        parallel.allreduce_counters(cnt)
-        torch.cuda.synchronize(cnt.device)
-        res = MCResult.from_words(cnt.cpu().numpy())
-        self.last_result = res
-        return res
-
-    def _count(self, num_rounds, num_samples):
-        if self._engine_parts() is not None:
-            return self.fused_counts(num_rounds, num_samples).failures
-        return int(np.sum([self._single_run(num_rounds) for _ in range(num_samples)]))
-
     def WordErrorRate(self, num_rounds: int, num_samples: int):
-        error_count = self._count(num_rounds, num_samples)
+        error_count = self._batch_failures(num_rounds, num_samples)
         return word_error_rate_phenl(error_count, num_samples, self.K, num_rounds), None
 
     def WordErrorProbability(self, num_rounds: int, num_samples: int):
         """``:360-381`` (the A8 formulas on the end-of-run failure count)."""
-        return word_error_rate(self._count(num_rounds, num_samples), num_samples, self.K)
+        return word_error_rate(self._batch_failures(num_rounds, num_samples), num_samples, self.K)
 
 
-class CodeSimulator_Phenon_SpaceTime:
+class CodeSimulator_Phenon_SpaceTime(_PhenonBase):
     """Phenomenological space-time simulator (``src/Simulators_SpaceTime.py:382-548``).
 
     ``WordErrorRate(num_cycles, num_samples)`` returns ``(wer, None)`` with the
@@ -701,35 +738,11 @@ class CodeSimulator_Phenon_SpaceTime:
     def __init__(self, code=None, decoder1_x=None, decoder1_z=None, decoder2_x=None, decoder2_z=None,
                  pauli_error_probs=(0.01, 0.01, 0.01), q=0, eval_logical_type="Total", num_rep=1, seed=None,
                  max_batch=0):
-        self.code = code
-        self.hx_ext = np.hstack([code.hx, np.identity(np.shape(code.hx)[0])])
-        self.hz_ext = np.hstack([code.hz, np.identity(np.shape(code.hz)[0])])
-        self.decoder1_z, self.decoder1_x = decoder1_z, decoder1_x
-        self.decoder2_z, self.decoder2_x = decoder2_z, decoder2_x
-        self.N = code.N
-        self.K = code.K
-        self.channel_probs = list(pauli_error_probs)
-        self.synd_prob = q
-        self.min_logical_weight = self.N
-        self.eval_logical_type = eval_logical_type
+        super().__init__(code, decoder1_x, decoder1_z, decoder2_x, decoder2_z, pauli_error_probs, q,
+                         eval_logical_type, seed, max_batch)
         self.num_rep = num_rep
-        self.seed = int(seed) if seed is not None else None
-        self.max_batch = int(max_batch)
-        self._shot_offset = 0
-        self._ph = None
-        self.last_result = None
 
-    # -- reference per-sample API (plugin path) --------------------------------
-    def _generate_error(self):
-        """``:405-442``: data error (3-way split), then hx-row and hz-row syndrome flips."""
-        N = self.N
-        u = np.array([random.random() for _ in range(N)])
-        ex, ez = pauli_split(u, self.channel_probs)
-        sz = np.array([random.random() < self.synd_prob for _ in range(self.hx_ext.shape[1] - N)], dtype=int)
-        sx = np.array([random.random() < self.synd_prob for _ in range(self.hz_ext.shape[1] - N)], dtype=int)
-        self.error_x_ext = np.concatenate([ex, sx])
-        self.error_z_ext = np.concatenate([ez, sz])
-        return self.error_x_ext, self.error_z_ext
+    _fused_needs = "fused path needs engine ST_BP_Decoder_syndrome (decoder1) and BPDecoder (decoder2)"
 
     def _single_run(self, num_rounds):
         """``:444-529`` (Z detectors differenced, X raw: quirk Q3)."""
@@ -752,21 +765,8 @@ class CodeSimulator_Phenon_SpaceTime:
             cur_z = (cur_z + self.decoder1_z.decode(det_z)) % 2
             cur_x = (cur_x + self.decoder1_x.decode(hist_x)) % 2
         ex_ext, ez_ext = self._generate_error()
-        cur_x = (cur_x + ex_ext[:self.N]) % 2
-        cur_z = (cur_z + ez_ext[:self.N]) % 2
-        dz = self.decoder2_z.decode(code.hx @ cur_z % 2)
-        dx = self.decoder2_x.decode(code.hz @ cur_x % 2)
-        rx, rz = (cur_x + dx) % 2, (cur_z + dz) % 2
-        X_failure = int(((code.hz @ rx) % 2).any() or ((code.lz @ rx) % 2).any())
-        Z_failure = int(((code.hx @ rz) % 2).any() or ((code.lx @ rz) % 2).any())
-        assert self.eval_logical_type in ["X", "Z", "Total"]
-        if self.eval_logical_type == "X":
-            return X_failure
-        if self.eval_logical_type == "Z":
-            return Z_failure
-        return X_failure or Z_failure
+        return self._final_round((cur_x + ex_ext[:self.N]) % 2, (cur_z + ez_ext[:self.N]) % 2)
 
-    # -- fused engine path ----------------------------------------------------
     def _engine_parts(self):
         from .decoders import ST_BP_Decoder_syndrome
 
@@ -778,41 +778,6 @@ class CodeSimulator_Phenon_SpaceTime:
             return None
         return d1[0].space_decoder, d1[1].space_decoder, b2[0], b2[1]
 
-    def _final_osd(self):
-        return tuple(getattr(d, "gpu_osd", None) for d in (self.decoder2_x, self.decoder2_z))
-
-    def fused_counts(self, num_rounds: int, num_samples: int):
-        """Run ``num_samples`` samples on the GPU; returns the all-reduced :class:`~.engine.MCResult`."""
-        parts = self._engine_parts()
-        if parts is None:
-            raise TypeError("fused path needs engine ST_BP_Decoder_syndrome (decoder1) and BPDecoder (decoder2)")
-        from .engine import DevicePhenl, MCResult, _torch
-
-        torch = _torch()
-        if self.seed is None:
-            self.seed = random.getrandbits(64)
-        if self._ph is None:
-            self._ph = DevicePhenl(self.code, *parts, num_rep=self.num_rep, max_batch=self.max_batch)
-            ox, oz = self._final_osd()
-            if ox is not None or oz is not None:
-                self._ph.set_final_osd(ox, oz)
-        rank, ws = parallel.world()
-        b, c = parallel.shard_range(num_samples, rank, ws, begin=self._shot_offset)
-        self._shot_offset += int(num_samples)
-        px, py, pz = self.channel_probs
-        cnt = self._ph.new_counters()
-        self._ph.launch(px, py, pz, self.synd_prob, self.seed, b, c, num_rounds, self.eval_logical_type, cnt)
-        parallel.allreduce_counters(cnt)
-        torch.cuda.synchronize(cnt.device)
-        res = MCResult.from_words(cnt.cpu().numpy())
-        self.last_result = res
-        return res
-
-    def _batch_failures(self, num_rounds: int, n: int) -> int:
-        if self._engine_parts() is not None:
-            return self.fused_counts(num_rounds, n).failures
-        return int(np.sum([self._single_run(num_rounds) for _ in range(n)]))
-
     def WordErrorRate(self, num_cycles: int, num_samples: int):
         num_rounds = int((num_cycles - 1) / self.num_rep + 1)
         error_count = self._batch_failures(num_rounds, num_samples)
@@ -823,17 +788,90 @@ class CodeSimulator_Phenon_SpaceTime:
         """Adaptive sampling (src/Simulators_SpaceTime.py:1051-1077) on this simulator:
         batches until ``target_failures`` or ``max_batches``; returns ``(wer, total_samples)``."""
         num_rounds = int((num_cycles - 1) / self.num_rep + 1)
-        total, fails = 0, 0
-        for _ in range(int(max_batches)):
-            fails += self._batch_failures(num_rounds, batch_size)
-            total += int(batch_size)
-            if fails >= target_failures:
-                break
+        fails, total = _adaptive_failures(lambda n: self._batch_failures(num_rounds, n), target_failures, batch_size,
+                                          max_batches)
         total_num_cycles = (num_rounds - 1) * self.num_rep + 1
         return word_error_rate_per_cycle(fails, total, self.K, total_num_cycles), total
 
 
-class CodeSimulator_Circuit_SpaceTime:
+class _CircuitBase(_ShotStream):
+    """What the two circuit-level simulators share: the constructor state of the evaluated sector
+    (each subclass swaps the sectors for ``eval_logical_type='X'`` in its own way first), the
+    per-sample path on GPU-sampled detectors, the device path and the cache of its loop
+    (``_dev``, keyed by the decoders' identities in ``_dev_key``).  A subclass owns its circuits and
+    graphs, ``_decoding_samples``, ``_engine_parts``, ``_build_device`` (the device loop of those
+    parts), the ``_fused_needs`` text and ``WordErrorRate``."""
+
+    _fused_needs = None  # the TypeError text of fused_counts without engine decoders
+
+    def __init__(self, code, decoder1_z, decoder2_z, p, num_cycles, error_params, circuit_type, seed, max_batch,
+                 sampler):
+        from . import circuit as _circ
+
+        self.eval_code = code
+        self.hx_ext = np.hstack([code.hx, np.identity(np.shape(code.hx)[0])])
+        self.hz_ext = np.hstack([code.hz, np.identity(np.shape(code.hz)[0])])
+        self.decoder1_z = decoder1_z
+        self.decoder2_z = decoder2_z
+        self.N = code.N
+        self.K = code.K
+        self.pz = p
+        self.synd_prob = p
+        self.min_logical_weight = self.N
+        self.num_cycles = num_cycles
+        self.circuit = _circ.StimCircuit()
+        self.error_params = error_params
+        self.max_stab_weight_x = int(np.max(np.sum(code.hx, axis=1)))
+        self.max_stab_weight_z = int(np.max(np.sum(code.hz, axis=1)))
+        if circuit_type == "random":
+            self.scheduling_X = _circ.RandomCircuit(code.hx)
+            self.scheduling_Z = _circ.RandomCircuit(code.hz)
+        elif circuit_type == "coloration":
+            self.scheduling_X = _circ.ColorationCircuit(code.hx)
+            self.scheduling_Z = _circ.ColorationCircuit(code.hz)
+        self.dem = None
+        self.detector_sampler = None
+        super().__init__(seed)
+        self.sampler = sampler  # DEM sampler of the device loop: "skip" (geometric gaps) or "keyed"
+        self.max_batch = int(max_batch)
+        self._dev = None
+        self._dev_key = None
+
+    # -- reference per-sample path (plugin decoders) -------------------------------
+    def _single_run(self):
+        samples = self.detector_sampler.sample(shots=1, append_observables=True)
+        return self._decoding_samples(samples)[0]
+
+    # -- fused engine path ---------------------------------------------------------
+    def _sampler_device(self):
+        """A device loop that only samples the DEM (no decoders): the detector sampler's."""
+        from .engine import DeviceCircuit
+
+        return DeviceCircuit(self.dem, max_batch=self.max_batch, sampler=self.sampler)
+
+    def _device(self):
+        parts = self._engine_parts()
+        key = None if parts is None else tuple(id(x) for x in parts)
+        if self._dev is None or self._dev_key != key:
+            self._dev = self._build_device(parts)
+            self._dev_key = key
+        return self._dev
+
+    def fused_counts(self, num_samples: int):
+        """``num_samples`` samples on the GPU (sharded over the torch.distributed ranks); the
+        all-reduced :class:`~.engine.MCResult`."""
+        if self._engine_parts() is None:
+            raise TypeError(self._fused_needs)
+        return self._fused_run(self._device, num_samples, lambda dev, b, c, cnt: dev.launch(self.seed, b, c, cnt))
+
+    def _batch_failures(self, n: int) -> int:
+        if self._engine_parts() is not None:
+            return self.fused_counts(n).failures
+        samples = self.detector_sampler.sample(shots=n, append_observables=True)
+        return int(np.sum(self._decoding_samples(samples)))
+
+
+class CodeSimulator_Circuit_SpaceTime(_CircuitBase):
     """Circuit-level space-time simulator (``src/Simulators_SpaceTime.py:672-1077``).
 
     ``_generate_circuit`` builds the reference's syndrome-extraction circuits (:mod:`.circuit`:
@@ -862,45 +900,17 @@ class CodeSimulator_Circuit_SpaceTime:
             code.hx, code.hz = code.hz, code.hx
             code.lx, code.lz = code.lz, code.lx
             decoder1_z, decoder2_z = decoder1_x, decoder2_x
-        self.eval_code = code
-        self.hx_ext = np.hstack([code.hx, np.identity(np.shape(code.hx)[0])])
-        self.hz_ext = np.hstack([code.hz, np.identity(np.shape(code.hz)[0])])
-        self.decoder1_z = decoder1_z
-        self.decoder2_z = decoder2_z
-        self.N = code.N
-        self.K = code.K
-        self.pz = p
-        self.synd_prob = p
-        self.min_logical_weight = self.N
-        self.num_cycles = num_cycles
         self.num_rep = num_rep
-        self.num_rounds = int((self.num_cycles - 1) / self.num_rep)
-        assert np.abs((self.num_cycles - 1) / self.num_rep - self.num_rounds) <= 1e-2
-        self.circuit = _circ.StimCircuit()
+        self.num_rounds = int((num_cycles - 1) / self.num_rep)
+        assert np.abs((num_cycles - 1) / self.num_rep - self.num_rounds) <= 1e-2
+        super().__init__(code, decoder1_z, decoder2_z, p, num_cycles, error_params, circuit_type, seed, max_batch,
+                         sampler)
         self.fault_circuit = _circ.StimCircuit()
-        self.error_params = error_params
-        self.max_stab_weight_x = int(np.max(np.sum(code.hx, axis=1)))
-        self.max_stab_weight_z = int(np.max(np.sum(code.hz, axis=1)))
-        if circuit_type == "random":
-            self.scheduling_X = _circ.RandomCircuit(code.hx)
-            self.scheduling_Z = _circ.RandomCircuit(code.hz)
-        elif circuit_type == "coloration":
-            self.scheduling_X = _circ.ColorationCircuit(code.hx)
-            self.scheduling_Z = _circ.ColorationCircuit(code.hz)
         self.num_logicals = self.eval_code.lx.shape[0]
         self.num_checks = self.eval_code.hx.shape[0]
-        self.detector_sampler = None
         self.circuit_graph = None
         self.h1_space_cor = None
-        self.dem = None
         self.fault_dem = None
-        self.seed = int(seed) if seed is not None else None
-        self.sampler = sampler  # DEM sampler of the device loop: "skip" (geometric gaps) or "keyed"
-        self.max_batch = int(max_batch)
-        self._shot_offset = 0
-        self._dev = None
-        self._dev_key = None
-        self.last_result = None
         # True: the hypergraphs are built from the fault DEM rendered as stim's text and parsed with the
         # reference's regex (circuit.DetectorErrorModel.from_text): stim's mechanism order, 6-digit
         # probabilities, and mantissa-only reads of probabilities printed in exponent notation
@@ -963,11 +973,9 @@ class CodeSimulator_Circuit_SpaceTime:
             out.append(1 if (res_syn.any() or res_log.any()) else 0)
         return out
 
-    def _single_run(self):
-        samples = self.detector_sampler.sample(shots=1, append_observables=True)
-        return self._decoding_samples(samples)[0]
-
     # -- fused engine path ---------------------------------------------------------
+    _fused_needs = "fused path needs engine decoders (ST_BP_Decoder_Circuit / BPDecoder / BPOSD_Decoder)"
+
     def _engine_parts(self):
         """(decoder1's DeviceBP, decoder2's DeviceBP, decoder2's OSD or None), or None."""
         b1 = _engine_bp(self.decoder1_z)
@@ -980,51 +988,17 @@ class CodeSimulator_Circuit_SpaceTime:
         b2 = _engine_bp(d2)
         return None if b2 is None else (b1, b2, None)
 
-    def _device(self):
+    def _build_device(self, parts):
         from .engine import DeviceCircuit
 
-        parts = self._engine_parts()
-        key = None if parts is None else tuple(id(x) for x in parts)
-        if self._dev is None or self._dev_key != key:
-            if self.circuit_graph is None:
-                raise RuntimeError("call _generate_circuit() and _generate_circuit_graph() first")
-            cg = self.circuit_graph
-            if parts is None:
-                self._dev = DeviceCircuit(self.dem, max_batch=self.max_batch, sampler=self.sampler)
-            else:
-                b1, b2, osd = parts
-                self._dev = DeviceCircuit(self.dem, b1, self.h1_space_cor, cg["L1"], b2, cg["L2"], self.num_rounds,
-                                          self.num_rep, osd=osd, max_batch=self.max_batch, sampler=self.sampler)
-            self._dev_key = key
-        return self._dev
-
-    def fused_counts(self, num_samples: int):
-        """``num_samples`` samples on the GPU (sharded over the torch.distributed ranks); the
-        all-reduced :class:`~.engine.MCResult`."""
-        from .engine import MCResult, _torch
-
-        if self._engine_parts() is None:
-            raise TypeError("fused path needs engine decoders (ST_BP_Decoder_Circuit / BPDecoder / BPOSD_Decoder)")
-        torch = _torch()
-        if self.seed is None:
-            self.seed = random.getrandbits(64)
-        dev = self._device()
-        rank, ws = parallel.world()
-        b, c = parallel.shard_range(num_samples, rank, ws, begin=self._shot_offset)
-        self._shot_offset += int(num_samples)
-        cnt = dev.new_counters()
-        dev.launch(self.seed, b, c, cnt)
-        parallel.allreduce_counters(cnt)
-        torch.cuda.synchronize(cnt.device)
-        res = MCResult.from_words(cnt.cpu().numpy())
-        self.last_result = res
-        return res
-
-    def _batch_failures(self, n: int) -> int:
-        if self._engine_parts() is not None:
-            return self.fused_counts(n).failures
-        samples = self.detector_sampler.sample(shots=n, append_observables=True)
-        return int(np.sum(self._decoding_samples(samples)))
+        if self.circuit_graph is None:
+            raise RuntimeError("call _generate_circuit() and _generate_circuit_graph() first")
+        if parts is None:
+            return self._sampler_device()
+        cg = self.circuit_graph
+        b1, b2, osd = parts
+        return DeviceCircuit(self.dem, b1, self.h1_space_cor, cg["L1"], b2, cg["L2"], self.num_rounds, self.num_rep,
+                             osd=osd, max_batch=self.max_batch, sampler=self.sampler)
 
     def WordErrorRate(self, num_samples: int):
         """``:1028-1049``: ``(wer per qubit per cycle, None)``; num_cycles must be odd."""
@@ -1034,17 +1008,12 @@ class CodeSimulator_Circuit_SpaceTime:
     def WordErrorRate_TargetFailure(self, target_failures, batch_size, max_batches):
         """``:1051-1077``: batches until ``target_failures``; ``(wer, total_samples)``."""
         assert int(self.num_cycles) % 2 == 1
-        total, fails = 0, 0
-        for _ in range(int(max_batches)):
-            fails += self._batch_failures(batch_size)
-            total += int(batch_size)
-            if fails >= target_failures:
-                break
+        fails, total = _adaptive_failures(self._batch_failures, target_failures, batch_size, max_batches)
         print("failures:", fails)
         return word_error_rate_per_cycle(fails, total, self.K, self.num_cycles), total
 
 
-class CodeSimulator_Circuit:
+class CodeSimulator_Circuit(_CircuitBase):
     """Single-shot circuit-level simulator (``src/Simulators.py:386-671``).
 
     ``_generate_circuit`` builds the reference's single-shot circuit (:func:`.circuit.single_shot_circuit`:
@@ -1072,46 +1041,16 @@ class CodeSimulator_Circuit:
     def __init__(self, code=None, decoder1_z=None, decoder1_x=None, decoder2_z=None, decoder2_x=None, p=0,
                  num_cycles=1, error_params=None, eval_logical_type="Z", circuit_type="coloration",
                  rand_scheduling_seed=0, seed=None, max_batch=0, sampler="skip"):
-        from . import circuit as _circ
-
         if eval_logical_type == "X":  # :390-402, in place
             code.hx, code.hz = code.hz, code.hx
             code.lx, code.lz = code.lz, code.lx
             if isinstance(getattr(code, "_csr", None), dict):
                 code._csr.clear()
             decoder1_z, decoder2_z = decoder1_x, decoder2_x
-        self.eval_code = code
-        self.hx_ext = np.hstack([code.hx, np.identity(np.shape(code.hx)[0])])
-        self.hz_ext = np.hstack([code.hz, np.identity(np.shape(code.hz)[0])])
-        self.decoder1_z = decoder1_z
-        self.decoder2_z = decoder2_z
-        self.N = code.N
-        self.K = code.K
-        self.pz = p
-        self.synd_prob = p
+        super().__init__(code, decoder1_z, decoder2_z, p, num_cycles, error_params, circuit_type, seed, max_batch,
+                         sampler)
         self.error_x = np.zeros(self.N).astype(int)
         self.error_z = np.zeros(self.N).astype(int)
-        self.min_logical_weight = self.N
-        self.num_cycles = num_cycles
-        self.circuit = _circ.StimCircuit()
-        self.error_params = error_params
-        self.max_stab_weight_x = int(np.max(np.sum(code.hx, axis=1)))
-        self.max_stab_weight_z = int(np.max(np.sum(code.hz, axis=1)))
-        if circuit_type == "random":
-            self.scheduling_X = _circ.RandomCircuit(code.hx)
-            self.scheduling_Z = _circ.RandomCircuit(code.hz)
-        elif circuit_type == "coloration":
-            self.scheduling_X = _circ.ColorationCircuit(code.hx)
-            self.scheduling_Z = _circ.ColorationCircuit(code.hz)
-        self.dem = None
-        self.detector_sampler = None
-        self.seed = int(seed) if seed is not None else None
-        self.sampler = sampler  # DEM sampler of the device loop: "skip" (geometric gaps) or "keyed"
-        self.max_batch = int(max_batch)
-        self._shot_offset = 0
-        self._dev = None
-        self._dev_key = None
-        self.last_result = None
 
     def _generate_circuit(self):
         """``:438-609``; the circuit's DEM is the sampler."""
@@ -1148,11 +1087,10 @@ class CodeSimulator_Circuit:
             out.append(1 if (res_syn.any() or res_log.any()) else 0)
         return out
 
-    def _single_run(self):
-        samples = self.detector_sampler.sample(shots=1, append_observables=True)
-        return self._decoding_samples(samples)[0]
-
     # -- fused engine path ---------------------------------------------------------
+    _fused_needs = ("fused path needs engine decoders (BPDecoder / FirstMinBPDecoder on [hx | I], "
+                    "BPDecoder / BPOSD_Decoder on hx)")
+
     def _engine_parts(self):
         """(decoder1's DeviceBP or None, its DeviceFirstMin or None, decoder2's DeviceBP, decoder2's
         OSD or None) when both decoders are this engine's, else None."""
@@ -1174,52 +1112,16 @@ class CodeSimulator_Circuit:
             return b1, fm, d2.decoder, None
         return None
 
-    def _device(self):
-        from .engine import DeviceCircuit, DeviceCircuitSingleShot
+    def _build_device(self, parts):
+        from .engine import DeviceCircuitSingleShot
 
-        parts = self._engine_parts()
-        key = None if parts is None else tuple(id(x) for x in parts)
-        if self._dev is None or self._dev_key != key:
-            if self.dem is None:
-                raise RuntimeError("call _generate_circuit() first")
-            if parts is None:
-                self._dev = DeviceCircuit(self.dem, max_batch=self.max_batch, sampler=self.sampler)
-            else:
-                b1, fm, b2, osd = parts
-                self._dev = DeviceCircuitSingleShot(self.dem, b1, self.eval_code.hx, self.eval_code.lx, b2,
-                                                    self.num_cycles, osd=osd, firstmin=fm, max_batch=self.max_batch,
-                                                    sampler=self.sampler)
-            self._dev_key = key
-        return self._dev
-
-    def fused_counts(self, num_samples: int):
-        """``num_samples`` samples on the GPU (sharded over the torch.distributed ranks); the
-        all-reduced :class:`~.engine.MCResult`."""
-        from .engine import MCResult, _torch
-
-        if self._engine_parts() is None:
-            raise TypeError("fused path needs engine decoders (BPDecoder / FirstMinBPDecoder on [hx | I], "
-                            "BPDecoder / BPOSD_Decoder on hx)")
-        torch = _torch()
-        if self.seed is None:
-            self.seed = random.getrandbits(64)
-        dev = self._device()
-        rank, ws = parallel.world()
-        b, c = parallel.shard_range(num_samples, rank, ws, begin=self._shot_offset)
-        self._shot_offset += int(num_samples)
-        cnt = dev.new_counters()
-        dev.launch(self.seed, b, c, cnt)
-        parallel.allreduce_counters(cnt)
-        torch.cuda.synchronize(cnt.device)
-        res = MCResult.from_words(cnt.cpu().numpy())
-        self.last_result = res
-        return res
-
-    def _batch_failures(self, n: int) -> int:
-        if self._engine_parts() is not None:
-            return self.fused_counts(n).failures
-        samples = self.detector_sampler.sample(shots=n, append_observables=True)
-        return int(np.sum(self._decoding_samples(samples)))
+        if self.dem is None:
+            raise RuntimeError("call _generate_circuit() first")
+        if parts is None:
+            return self._sampler_device()
+        b1, fm, b2, osd = parts
+        return DeviceCircuitSingleShot(self.dem, b1, self.eval_code.hx, self.eval_code.lx, b2, self.num_cycles,
+                                       osd=osd, firstmin=fm, max_batch=self.max_batch, sampler=self.sampler)
 
     def WordErrorRate(self, num_samples: int):
         """``:653-671``: ``(wer per qubit per cycle, None)``; num_cycles must be odd."""
@@ -1237,14 +1139,10 @@ class _DetectorSampler:
 
     def sample(self, shots: int, append_observables: bool = True):
         sim = self.sim
-        if sim.seed is None:
-            sim.seed = random.getrandbits(64)
-        from .engine import DeviceCircuit
-
-        dev = sim._dev if sim._dev is not None else DeviceCircuit(sim.dem, max_batch=sim.max_batch, sampler=sim.sampler)
+        sim._lazy_seed()
         if sim._dev is None:
-            sim._dev, sim._dev_key = dev, None
-        out = dev.sample(sim.seed, sim._shot_offset, int(shots))
+            sim._dev, sim._dev_key = sim._sampler_device(), None
+        out = sim._dev.sample(sim.seed, sim._shot_offset, int(shots))
         sim._shot_offset += int(shots)
         return out if append_observables else out[:, :sim.dem.num_detectors]
 
@@ -1252,19 +1150,91 @@ class _DetectorSampler:
 # -------------------------------------------------------------- code family
 
 
-class CodeFamily:
-    """``src/Simulators.py:746-963``: the ``'data'``, ``'phenl'`` and ``'circuit'`` noise models
-    (``'circuit'``: :class:`CodeSimulator_Circuit` on this package's own circuits and DEMs)."""
+def _check_eval_args(noise_model=None, eval_logical_type=None, eval_method=None):
+    """The argument asserts of the families' ``Eval*`` methods, for the arguments given."""
+    assert noise_model is None or noise_model in ["data", "phenl", "circuit"], \
+        "noise_model should be one of [data, phenl, circuit]"
+    assert eval_logical_type is None or eval_logical_type in ["X", "Z", "Total"], \
+        "eval_type should be one of [X, Y, Total]"
+    assert eval_method is None or eval_method in ["extrapolation"], "eval_method should be one of [extrapolation]"
+
+
+def _depolarizing_probs(eval_p):
+    """``[px, py, pz]`` of the ``'data'`` and ``'phenl'`` points (``src/Simulators.py:763-764``)."""
+    p = eval_p * 3 / 2
+    return [p / 3, p / 3, p / 3]
+
+
+def _threshold_p_list(est_threshold):
+    """The 6 log-spaced p in [0.4 p_th, 0.8 p_th] of ``EvalThreshold``."""
+    return 10 ** (np.linspace(np.log10(est_threshold * 0.4), np.log10(est_threshold * 0.8), 6))
+
+
+def _distance_p_list(est_threshold):
+    """The 5 log-spaced p in [p_th / 6, p_th / 4] of ``EvalEffectiveDistances``."""
+    return 10 ** (np.linspace(np.log10(est_threshold / 6), np.log10(est_threshold / 4), 5))
+
+
+def _circuit_error_params(circuit_error_params, p):
+    """The circuit noise rates at ``p``: every rate of ``circuit_error_params`` times ``p``."""
+    return {k: circuit_error_params[k] * p for k in ("p_i", "p_state_p", "p_m", "p_CX", "p_idling_gate")}
+
+
+class _CodeFamilyBase:
+    """What ``CodeFamily`` and ``CodeFamily_SpaceTime`` share: the constructor, the ``'data'`` point
+    and the sustainable-threshold sweep.  ``EvalWER``, ``EvalThreshold`` and
+    ``EvalEffectiveDistances`` stay per class (their return shapes and quirks differ)."""
 
     def __init__(self, code_list: list, decoder1_class, decoder2_class):
         self.code_list = code_list
         self.decoder1_class = decoder1_class
         self.decoder2_class = decoder2_class
 
+    def _data_simulator(self, eval_code, eval_p, eval_logical_type):
+        """The ``'data'`` point: decoder2 on hz / hx with ``p_data = eval_p`` and the
+        :class:`CodeSimulator_DataError` of the depolarizing channel at ``3/2 eval_p``."""
+        decoder_x = self.decoder2_class.GetDecoder({"h": eval_code.hz, "p_data": eval_p})
+        decoder_z = self.decoder2_class.GetDecoder({"h": eval_code.hx, "p_data": eval_p})
+        return CodeSimulator_DataError(code=eval_code, decoder_x=decoder_x, decoder_z=decoder_z,
+                                       pauli_error_probs=_depolarizing_probs(eval_p),
+                                       eval_logical_type=eval_logical_type)
+
+    def EvalSustainableThreshold(self, noise_model: str, eval_logical_type: str, eval_method: str,
+                                 est_threshold: float, num_samples_per_cycle: int, num_cycles_list: list,
+                                 data_synd_noise_ratio=1, circuit_type="coloration", circuit_error_params=None,
+                                 if_plot=False):
+        """``src/Simulators.py:927-948`` / ``src/Simulators_SpaceTime.py:1326-1347``: the threshold at
+        each cycle count (``num_samples_per_cycle / num_cycles`` samples each), then
+        ``FitSusThreshold`` -> the sustainable threshold p_sus."""
+        from scipy.optimize import curve_fit
+
+        sweep = [self.EvalThreshold(noise_model=noise_model, eval_logical_type=eval_logical_type,
+                                    eval_method=eval_method, est_threshold=est_threshold,
+                                    num_samples=int(num_samples_per_cycle / c), num_cycles=c,
+                                    data_synd_noise_ratio=data_synd_noise_ratio, circuit_type=circuit_type,
+                                    circuit_error_params=circuit_error_params, if_plot=if_plot)
+                 for c in num_cycles_list]
+        popt, _ = curve_fit(FitSusThreshold, np.array(num_cycles_list), np.array(sweep), p0=(0.01, 0.05, 0.05))
+        if if_plot:
+            try:
+                import matplotlib.pyplot as plt
+
+                plt.figure()
+                plt.plot(num_cycles_list, sweep, "D")
+                plt.plot(num_cycles_list, FitSusThreshold(np.array(num_cycles_list), *popt), "-")
+                plt.close()
+            except ImportError:
+                pass
+        return popt[0]
+
+
+class CodeFamily(_CodeFamilyBase):
+    """``src/Simulators.py:746-963``: the ``'data'``, ``'phenl'`` and ``'circuit'`` noise models
+    (``'circuit'``: :class:`CodeSimulator_Circuit` on this package's own circuits and DEMs)."""
+
     def EvalWER(self, noise_model: str, eval_logical_type: str, eval_p_list: list, num_samples: int, num_cycles=1,
                 data_synd_noise_ratio=1, circuit_type="coloration", circuit_error_params=None, if_plot=True):
-        assert noise_model in ["data", "phenl", "circuit"], "noise_model should be one of [data, phenl, circuit]"
-        assert eval_logical_type in ["X", "Z", "Total"], "eval_type should be one of [X, Y, Total]"
+        _check_eval_args(noise_model, eval_logical_type)
         eval_wer_list = []
         for eval_code in self.code_list:
             for eval_p in eval_p_list:
@@ -1273,9 +1243,8 @@ class CodeFamily:
                                                            num_cycles, data_synd_noise_ratio, circuit_type,
                                                            circuit_error_params))
                     continue
-                p = eval_p * 3 / 2
-                pauli_error_probs = [p / 3, p / 3, p / 3]  # src/Simulators.py:763-764
                 if noise_model == "phenl":  # src/Simulators.py:779-809
+                    p = eval_p * 3 / 2
                     q = eval_p
                     p_data, p_synd = p * 2 / 3, q
                     hx_ext = np.hstack([eval_code.hx, np.identity(np.shape(eval_code.hx)[0])])
@@ -1285,15 +1254,11 @@ class CodeFamily:
                     d2x = self.decoder2_class.GetDecoder({"h": eval_code.hz, "p_data": p_data})
                     d2z = self.decoder2_class.GetDecoder({"h": eval_code.hx, "p_data": p_data})
                     sim = CodeSimulator_Phenon(code=eval_code, decoder1_x=d1x, decoder1_z=d1z, decoder2_x=d2x,
-                                               decoder2_z=d2z, pauli_error_probs=pauli_error_probs, q=q,
+                                               decoder2_z=d2z, pauli_error_probs=_depolarizing_probs(eval_p), q=q,
                                                eval_logical_type=eval_logical_type)
                     eval_wer_list.append(sim.WordErrorRate(num_rounds=num_cycles, num_samples=num_samples)[0])
                     continue
-                decoder_x = self.decoder2_class.GetDecoder({"h": eval_code.hz, "p_data": eval_p})
-                decoder_z = self.decoder2_class.GetDecoder({"h": eval_code.hx, "p_data": eval_p})
-                sim = CodeSimulator_DataError(code=eval_code, decoder_x=decoder_x, decoder_z=decoder_z,
-                                              pauli_error_probs=pauli_error_probs,
-                                              eval_logical_type=eval_logical_type)
+                sim = self._data_simulator(eval_code, eval_p, eval_logical_type)
                 eval_wer_list.append(sim.WordErrorRate(num_samples)[0])
         eval_wer_array = np.reshape(np.array(eval_wer_list), [len(self.code_list), len(eval_p_list)])
         if if_plot:
@@ -1305,17 +1270,11 @@ class CodeFamily:
         :meth:`CodeSimulator_DataError.WordErrorRate_Stratified`: the same ``p = 3/2 eval_p``
         convention and decoder construction, the same ``[codes, points]`` array; every point measures
         its own spectrum with decoders built for that point."""
-        assert eval_logical_type in ["X", "Z", "Total"], "eval_type should be one of [X, Y, Total]"
+        _check_eval_args(eval_logical_type=eval_logical_type)
         eval_wer_list = []
         for eval_code in self.code_list:
             for eval_p in eval_p_list:
-                p = eval_p * 3 / 2
-                pauli_error_probs = [p / 3, p / 3, p / 3]
-                decoder_x = self.decoder2_class.GetDecoder({"h": eval_code.hz, "p_data": eval_p})
-                decoder_z = self.decoder2_class.GetDecoder({"h": eval_code.hx, "p_data": eval_p})
-                sim = CodeSimulator_DataError(code=eval_code, decoder_x=decoder_x, decoder_z=decoder_z,
-                                              pauli_error_probs=pauli_error_probs,
-                                              eval_logical_type=eval_logical_type)
+                sim = self._data_simulator(eval_code, eval_p, eval_logical_type)
                 eval_wer_list.append(sim.WordErrorRate_Stratified(shots_per_weight, tail)[0])
         return np.reshape(np.array(eval_wer_list), [len(self.code_list), len(eval_p_list)])
 
@@ -1326,7 +1285,7 @@ class CodeFamily:
         ``'Total'`` = the Z run + the X run.  The X run swaps the sectors of ``eval_code`` in place
         (quirk Q8), so the decoders are built from the code as the previous point left it."""
         p = eval_p
-        error_params = {k: circuit_error_params[k] * p for k in ("p_i", "p_state_p", "p_m", "p_CX", "p_idling_gate")}
+        error_params = _circuit_error_params(circuit_error_params, p)
         p_data, p_synd = data_synd_noise_ratio * p, 1 * p
         hx_ext = np.hstack([eval_code.hx, np.identity(np.shape(eval_code.hx)[0])])
         hz_ext = np.hstack([eval_code.hz, np.identity(np.shape(eval_code.hz)[0])])
@@ -1347,30 +1306,18 @@ class CodeFamily:
                       num_samples: int, num_cycles=1, data_synd_noise_ratio=1, circuit_type="coloration",
                       circuit_error_params=None, if_plot=False):
         """``src/Simulators.py:912-924``."""
-        assert eval_method in ["extrapolation"], "eval_method should be one of [extrapolation]"
-        eval_p_list = 10 ** (np.linspace(np.log10(est_threshold * 0.4), np.log10(est_threshold * 0.8), 6))
+        _check_eval_args(eval_method=eval_method)
+        eval_p_list = _threshold_p_list(est_threshold)
         eval_wer_array = self.EvalWER(noise_model, eval_logical_type, eval_p_list, num_samples, num_cycles,
                                       data_synd_noise_ratio, circuit_type, circuit_error_params, if_plot=False)
         return ThresholdEst_extrapolation(eval_p_list, eval_wer_array, if_plot)
-
-    def EvalSustainableThreshold(self, noise_model: str, eval_logical_type: str, eval_method: str,
-                                 est_threshold: float, num_samples_per_cycle: int, num_cycles_list: list,
-                                 data_synd_noise_ratio=1, circuit_type="coloration", circuit_error_params=None,
-                                 if_plot=False):
-        """``src/Simulators.py:927-948``: the threshold at each cycle count (``num_samples_per_cycle /
-        num_cycles`` samples each), then ``FitSusThreshold`` -> the sustainable threshold p_sus."""
-        return _sustainable_threshold(self, noise_model, eval_logical_type, eval_method, est_threshold,
-                                      num_samples_per_cycle, num_cycles_list, data_synd_noise_ratio, circuit_type,
-                                      circuit_error_params, if_plot)
 
     def EvalEffectiveDistances(self, noise_model: str, eval_logical_type: str, eval_method: str, est_threshold: float,
                                num_samples: int, num_cycles=1, data_synd_noise_ratio=1, circuit_type="coloration",
                                if_plot=False):
         """``src/Simulators.py:951-963``: 5 log-spaced p in [p_th/6, p_th/4], then :func:`DistanceEst`."""
-        assert noise_model in ["data", "phenl", "circuit"], "noise_model should be one of [data, phenl, circuit]"
-        assert eval_logical_type in ["X", "Z", "Total"], "eval_type should be one of [X, Y, Total]"
-        assert eval_method in ["extrapolation"], "eval_method should be one of [extrapolation]"
-        eval_p_list = 10 ** (np.linspace(np.log10(est_threshold / 6), np.log10(est_threshold / 4), 5))
+        _check_eval_args(noise_model, eval_logical_type, eval_method)
+        eval_p_list = _distance_p_list(est_threshold)
         eval_wer_array = self.EvalWER(noise_model, eval_logical_type, eval_p_list, num_samples, num_cycles,
                                       data_synd_noise_ratio, circuit_type, if_plot=False)
         return DistanceEst(eval_p_list, eval_wer_array, if_plot)
@@ -1381,29 +1328,7 @@ def FitSusThreshold(N, p_sus, p_0, gamma):
     return p_sus * (1 - (1 - p_0 / p_sus) * np.exp(-gamma * N))
 
 
-def _sustainable_threshold(fam, noise_model, eval_logical_type, eval_method, est_threshold, num_samples_per_cycle,
-                           num_cycles_list, data_synd_noise_ratio, circuit_type, circuit_error_params, if_plot):
-    from scipy.optimize import curve_fit
-
-    sweep = [fam.EvalThreshold(noise_model=noise_model, eval_logical_type=eval_logical_type, eval_method=eval_method,
-                               est_threshold=est_threshold, num_samples=int(num_samples_per_cycle / c), num_cycles=c,
-                               data_synd_noise_ratio=data_synd_noise_ratio, circuit_type=circuit_type,
-                               circuit_error_params=circuit_error_params, if_plot=if_plot) for c in num_cycles_list]
-    popt, _ = curve_fit(FitSusThreshold, np.array(num_cycles_list), np.array(sweep), p0=(0.01, 0.05, 0.05))
-    if if_plot:
-        try:
-            import matplotlib.pyplot as plt
-
-            plt.figure()
-            plt.plot(num_cycles_list, sweep, "D")
-            plt.plot(num_cycles_list, FitSusThreshold(np.array(num_cycles_list), *popt), "-")
-            plt.close()
-        except ImportError:
-            pass
-    return popt[0]
-
-
-class CodeFamily_SpaceTime:
+class CodeFamily_SpaceTime(_CodeFamilyBase):
     """``src/Simulators_SpaceTime.py:1152-1309`` for the ``'data'`` and ``'phenl'`` noise models.
 
     ``'phenl'`` builds decoder1 (space-time, ``num_rep``) and decoder2 exactly
@@ -1421,16 +1346,10 @@ class CodeFamily_SpaceTime:
     in :mod:`.circuit`) and returns ``(eval_wer_list, eval_p_adapt_list)`` like the reference.
     """
 
-    def __init__(self, code_list: list, decoder1_class, decoder2_class):
-        self.code_list = code_list
-        self.decoder1_class = decoder1_class
-        self.decoder2_class = decoder2_class
-
     def EvalWER(self, noise_model: str, eval_logical_type: str, eval_p_list: list, num_samples: int, num_cycles=1,
                 num_rep=1, circuit_type="coloration", circuit_error_params=None, if_plot=True, if_adaptive=False,
                 adaptive_params=None):
-        assert noise_model in ["data", "phenl", "circuit"], "noise_model should be one of [data, phenl, circuit]"
-        assert eval_logical_type in ["X", "Z", "Total"], "eval_type should be one of [X, Y, Total]"
+        _check_eval_args(noise_model, eval_logical_type)
         if noise_model == "circuit":
             return self._eval_wer_circuit(eval_logical_type, eval_p_list, num_samples, num_cycles, num_rep,
                                           circuit_type, circuit_error_params, if_adaptive, adaptive_params)
@@ -1438,16 +1357,11 @@ class CodeFamily_SpaceTime:
         for eval_code in self.code_list:
             per_code = []
             for eval_p in eval_p_list:
-                p = eval_p * 3 / 2
-                pauli_error_probs = [p / 3, p / 3, p / 3]
                 if noise_model == "data":
-                    dx = self.decoder2_class.GetDecoder({"h": eval_code.hz, "p_data": eval_p})
-                    dz = self.decoder2_class.GetDecoder({"h": eval_code.hx, "p_data": eval_p})
-                    sim = CodeSimulator_DataError(code=eval_code, decoder_x=dx, decoder_z=dz,
-                                                  pauli_error_probs=pauli_error_probs,
-                                                  eval_logical_type=eval_logical_type)
+                    sim = self._data_simulator(eval_code, eval_p, eval_logical_type)
                     per_code.append(sim.WordErrorRate(num_samples)[0])
                 else:
+                    p = eval_p * 3 / 2
                     q = eval_p
                     p_data, p_synd = p * 2 / 3, q
                     d1x = self.decoder1_class.GetDecoder({"h": eval_code.hz, "p_data": p_data, "p_syndrome": p_synd,
@@ -1458,7 +1372,7 @@ class CodeFamily_SpaceTime:
                     d2z = self.decoder2_class.GetDecoder({"h": eval_code.hx, "p_data": p_data})
                     sim = CodeSimulator_Phenon_SpaceTime(code=eval_code, decoder1_x=d1x, decoder1_z=d1z,
                                                          decoder2_x=d2x, decoder2_z=d2z,
-                                                         pauli_error_probs=pauli_error_probs, q=q,
+                                                         pauli_error_probs=_depolarizing_probs(eval_p), q=q,
                                                          eval_logical_type=eval_logical_type, num_rep=num_rep)
                     per_code.append(sim.WordErrorRate(num_cycles=num_cycles, num_samples=num_samples)[0])
             eval_wer_list.append(np.array(per_code))
@@ -1482,8 +1396,7 @@ class CodeFamily_SpaceTime:
             per_code = []
             for eval_p in plist:
                 p = eval_p
-                cep = circuit_error_params
-                error_params = {k: cep[k] * p for k in ("p_i", "p_state_p", "p_m", "p_CX", "p_idling_gate")}
+                error_params = _circuit_error_params(circuit_error_params, p)
                 sim = CodeSimulator_Circuit_SpaceTime(code=eval_code, decoder1_z=None, decoder1_x=None,
                                                       decoder2_z=None, decoder2_x=None, p=p, num_cycles=num_cycles,
                                                       num_rep=num_rep, error_params=error_params,
@@ -1507,32 +1420,19 @@ class CodeFamily_SpaceTime:
         """``src/Simulators_SpaceTime.py:1311-1324``.  As in the reference, ``data_synd_noise_ratio`` is
         passed positionally into EvalWER's ``num_rep`` slot (quirk Q7); the WER list (first element of
         EvalWER's pair; the reference hands the pair itself to the fit, which cannot work) is fitted."""
-        assert noise_model in ["data", "phenl", "circuit"], "noise_model should be one of [data, phenl, circuit]"
-        assert eval_logical_type in ["X", "Z", "Total"], "eval_type should be one of [X, Y, Total]"
-        assert eval_method in ["extrapolation"], "eval_method should be one of [extrapolation]"
-        eval_p_list = 10 ** (np.linspace(np.log10(est_threshold * 0.4), np.log10(est_threshold * 0.8), 6))
+        _check_eval_args(noise_model, eval_logical_type, eval_method)
+        eval_p_list = _threshold_p_list(est_threshold)
         res = self.EvalWER(noise_model, eval_logical_type, eval_p_list, num_samples, num_cycles, data_synd_noise_ratio,
                            circuit_type, circuit_error_params, if_plot=False)
         wer = res[0] if isinstance(res, tuple) else res
         return ThresholdEst_extrapolation(eval_p_list, np.array(wer), if_plot)
 
-    def EvalSustainableThreshold(self, noise_model: str, eval_logical_type: str, eval_method: str,
-                                 est_threshold: float, num_samples_per_cycle: int, num_cycles_list: list,
-                                 data_synd_noise_ratio=1, circuit_type="coloration", circuit_error_params=None,
-                                 if_plot=False):
-        """``src/Simulators_SpaceTime.py:1326-1347`` (same as CodeFamily's)."""
-        return _sustainable_threshold(self, noise_model, eval_logical_type, eval_method, est_threshold,
-                                      num_samples_per_cycle, num_cycles_list, data_synd_noise_ratio, circuit_type,
-                                      circuit_error_params, if_plot)
-
     def EvalEffectiveDistances(self, noise_model: str, eval_logical_type: str, eval_method: str, est_threshold: float,
                                num_samples: int, num_cycles=1, data_synd_noise_ratio=1, circuit_type="coloration",
                                if_plot=False):
         """``src/Simulators_SpaceTime.py:1350-1362`` (``data_synd_noise_ratio`` lands in ``num_rep``, Q7)."""
-        assert noise_model in ["data", "phenl", "circuit"], "noise_model should be one of [data, phenl, circuit]"
-        assert eval_logical_type in ["X", "Z", "Total"], "eval_type should be one of [X, Y, Total]"
-        assert eval_method in ["extrapolation"], "eval_method should be one of [extrapolation]"
-        eval_p_list = 10 ** (np.linspace(np.log10(est_threshold / 6), np.log10(est_threshold / 4), 5))
+        _check_eval_args(noise_model, eval_logical_type, eval_method)
+        eval_p_list = _distance_p_list(est_threshold)
         res = self.EvalWER(noise_model, eval_logical_type, eval_p_list, num_samples, num_cycles, data_synd_noise_ratio,
                            circuit_type, if_plot=False)
         wer = res[0] if isinstance(res, tuple) else res
