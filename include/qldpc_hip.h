@@ -304,7 +304,8 @@ int qldpc_bp_geometry(const qldpc_bp *bp, int32_t *threads, int32_t *vars_per_th
  * when the graph fits: column degree <= 4, <= 8 variables per thread, image
  * < 64 KiB), 2 = streamed variables, 1 = LDS-atomic check state, 4 = engine 3
  * with c2v computed by the check phase, 5 = product-sum (bp_method 0), 6 = HBM-resident
- * messages (qldpc_bp_create_hbm; automatic for images over 160 KiB).
+ * messages (qldpc_bp_create_hbm; automatic for images over 160 KiB), 7 = Relay-BP
+ * (qldpc_bp_create_relay).
  * QLDPC_ENGINE in the environment selects 1, 2 or 4 explicitly. */
 int qldpc_bp_engine(const qldpc_bp *bp, int32_t *engine);
 
@@ -339,6 +340,51 @@ int qldpc_bp_degree3_slots(const qldpc_bp *bp, int32_t *d3k);
  * bp_decoder replacement, src/Decoders.py:80-84); min-sum only. */
 int qldpc_bp_create_hbm(qldpc_graph *g, const double *channel_probs, int32_t max_iter, double ms_scaling_factor,
                         int32_t precision, qldpc_bp **out);
+
+/*
+ * Relay-BP (Mueller et al. 2025) on engine 7 (relay.hip): min-sum BP with a per-variable memory term,
+ * run as a chain of legs that collects up to stop_nconv syndrome-consistent solutions and keeps the
+ * lightest.  No reference counterpart: the decoder for the slot after plain BP, with no elimination.
+ * THE LAW, T = double (precision 64) or float (32), every operation in T in ldpc's min-sum order:
+ *   L0_j = (T) log((1 - p_j) / p_j) (double, libm);  wq_j = (int64) floor(L0_j(double) 2^32 + 0.5);
+ *   gam[0][j] = (T) pre_gamma;  gam[r][j] = (T)(gamma_lo + (gamma_hi - gamma_lo) u) in double, r = 1 ..
+ *     num_legs, u = ((o0 >> 5) 2^26 + (o1 >> 6)) / 2^53, (o0..o3) = Philox4x32-10(key = (seed_lo, seed_hi),
+ *     ctr = (j, r, 0, 0x51D50007));
+ *   M_j <- L0_j, nsol <- 0, bestW <- +inf, iters <- 0;  for leg r = 0 .. num_legs (pre_iter iterations
+ *   for r = 0, else leg_iter):  bias_j = ((T)1 - gam[r][j]) L0_j + gam[r][j] M_j (two rounded products
+ *   and one rounded sum, never an FMA); every bit-to-check message of column j <- bias_j; each iteration
+ *   t = 1 .. : ldpc's min-sum check pass (alpha = ms_scaling_factor, or 1 - 2^-t when that is 0), its
+ *   variable pass with bias_j (from the current M_j) in place of the prior, M_j <- the column's final
+ *   sum, dec_j = (M_j <= 0), iters += 1; the leg ends when H dec == s.  A leg that ended so is a solution:
+ *   nsol += 1, W = sum of wq_j over dec_j = 1, best <- dec when W < bestW (strict); the chain stops at
+ *   nsol == stop_nconv.  M carries into the next leg; the messages restart from the new bias.
+ *   corr = best if nsol > 0 else the last dec; conv = (nsol > 0); iters <= pre_iter + num_legs leg_iter.
+ * num_legs = 0 and pre_gamma = 0 is plain min-sum BP, bit for bit.
+ *
+ * qldpc_bp_create_relay returns an ordinary qldpc_bp (qldpc_bp_engine: 7; max_iter = pre_iter +
+ * num_legs leg_iter) for qldpc_bp_decode_batch and every loop that decodes through it: the staged
+ * data-error pipeline (qldpc_mc_create sends it there), qldpc_mc_launch_weight, the phenomenological
+ * and circuit loops.  qldpc_bp_set_channel_probs rebuilds L0 and the weights.  No soft output
+ * (qldpc_bp_decode_batch_soft) and no qldpc_mc_set_osd: QLDPC_ENOTSUP.  One decode per 256-thread
+ * workgroup, the whole chain in the kernel; state in LDS when it fits 160 KiB, else the messages in an
+ * HBM workspace (QLDPC_RELAY_WS=1 forces that); the graph's index arrays are staged in LDS as 16-bit
+ * words when that costs no resident workgroup (QLDPC_RELAY_IDX=0: walked in global memory).  QLDPC_EINVAL: pre_iter < 1, num_legs < 0, leg_iter <
+ * 1 with num_legs > 0, stop_nconv < 1, gamma_lo > gamma_hi, a non-finite gamma, precision not 32 / 64.
+ * qldpc_relay_gammas: the gamma table alone, host only, widened to double, out [num_legs + 1][n].
+ * qldpc_relay_decode_host: the same law in plain C++ on host memory (no HIP call, any graph): synd
+ * [B][m], corr [B][n], iters / conv / nsol [B] (each may be NULL); threads <= 0 = OMP_NUM_THREADS if
+ * set, else all hardware threads.
+ */
+int qldpc_bp_create_relay(qldpc_graph *g, const double *channel_probs, int32_t pre_iter, double pre_gamma,
+                          int32_t num_legs, int32_t leg_iter, double gamma_lo, double gamma_hi, int32_t stop_nconv,
+                          uint64_t gamma_seed, double ms_scaling_factor, int32_t precision, qldpc_bp **out);
+int qldpc_relay_gammas(int32_t n, double pre_gamma, int32_t num_legs, double gamma_lo, double gamma_hi,
+                       uint64_t gamma_seed, int32_t precision, double *out);
+int qldpc_relay_decode_host(int32_t m, int32_t n, const int32_t *row_ptr, const int32_t *col_idx,
+                            const double *channel_probs, int32_t pre_iter, double pre_gamma, int32_t num_legs,
+                            int32_t leg_iter, double gamma_lo, double gamma_hi, int32_t stop_nconv,
+                            uint64_t gamma_seed, double ms_scaling_factor, int32_t precision, const uint8_t *synd,
+                            uint8_t *corr, int32_t *iters, uint8_t *conv, int32_t *nsol, int64_t B, int32_t threads);
 
 /* BP+OSD in the fused shot loop (bposd_decoder per sector, src/Decoders.py:26-41, inside
  * _single_run, src/Simulators.py:117-168): after qldpc_mc_set_osd, qldpc_mc_launch captures

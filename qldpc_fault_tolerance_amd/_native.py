@@ -34,6 +34,7 @@ EXPORTED = [
     "qldpc_dist_create", "qldpc_dist_run_host", "qldpc_dist_run", "qldpc_dist_geometry", "qldpc_dist_destroy",
     "qldpc_mc_create_staged", "qldpc_mc_launch_weight", "qldpc_sample_errors_weight",
     "qldpc_sample_errors_weight_host",
+    "qldpc_bp_create_relay", "qldpc_relay_gammas", "qldpc_relay_decode_host",
 ]
 BUILD_EXPERIMENTAL = 1  # qldpc_build_flags(): the measured-and-not-kept kernel families are compiled in
 COMM_ID_BYTES = 128
@@ -232,6 +233,15 @@ def _declare(L):
     L.qldpc_sample_errors_weight.argtypes = [_i32, _dbl, _dbl, _dbl, _u64, _u64, _i64, _i32, _vp, _vp]
     L.qldpc_sample_errors_weight_host.restype = ctypes.c_int
     L.qldpc_sample_errors_weight_host.argtypes = [_i32, _dbl, _dbl, _dbl, _u64, _u64, _i64, _i32, _vp]
+    # (pre_iter, pre_gamma, num_legs, leg_iter, gamma_lo, gamma_hi, stop_nconv, gamma_seed, ms_scaling_factor,
+    # precision): the relay parameter block of qldpc_bp_create_relay / qldpc_relay_decode_host
+    relay = [_i32, _dbl, _i32, _i32, _dbl, _dbl, _i32, _u64, _dbl, _i32]
+    L.qldpc_bp_create_relay.restype = ctypes.c_int
+    L.qldpc_bp_create_relay.argtypes = [_vp, _vp] + relay + [_pp]
+    L.qldpc_relay_gammas.restype = ctypes.c_int
+    L.qldpc_relay_gammas.argtypes = [_i32, _dbl, _i32, _dbl, _dbl, _u64, _i32, _vp]
+    L.qldpc_relay_decode_host.restype = ctypes.c_int
+    L.qldpc_relay_decode_host.argtypes = [_i32, _i32, _vp, _vp, _vp] + relay + [_vp, _vp, _vp, _vp, _vp, _i64, _i32]
 
 
 def lib():

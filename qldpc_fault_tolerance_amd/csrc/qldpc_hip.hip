@@ -360,6 +360,7 @@ int qldpc_graph_info(const qldpc_graph* g, int32_t* m, int32_t* n, int32_t* nnz,
 
 static int upload_llr(qldpc_bp* bp) {
   const int TB = bp->route.TB, VPL = bp->route.VPL, n = bp->g->n;
+  if (bp->route.engine == 7) return relay_upload_priors(bp);  // L0 and the integer solution weights
   if (bp->route.engine == 6) {  // HBM engine: log((1-p)/p) per variable, variable order
     std::vector<double> l64(n);
     for (int j = 0; j < n; ++j) l64[j] = std::log((1.0 - bp->probs[j]) / bp->probs[j]);  // glibc log, as Cython
@@ -995,6 +996,33 @@ static std::vector<int> label_checks(const qldpc_graph* g, const Route& r, const
   return lab;
 }
 
+// The plain CSR and CSC of bp's graph on the device (edge ids in row-major order, rows ascending per
+// column): what the row-ordered / column-ordered passes of engines 5 and 7 walk.
+static int upload_csr_csc(qldpc_bp* bp) {
+  const qldpc_graph* g = bp->g;
+  const int E = g->nnz;
+  std::vector<int32_t> cp(g->n + 1, 0), ce;
+  ce.reserve(E);
+  for (int j = 0; j < g->n; ++j) {
+    for (int i : g->col_rows[j]) {
+      const int* b = g->col_idx.data() + g->row_ptr[i];
+      const int* e = g->col_idx.data() + g->row_ptr[i + 1];
+      ce.push_back((int32_t)(std::lower_bound(b, e, j) - g->col_idx.data()));
+    }
+    cp[j + 1] = (int32_t)ce.size();
+  }
+  int rc;
+  if ((rc = bp->ps_rp.alloc((size_t)(g->m + 1) * 4)) || (rc = bp->ps_ci.alloc((size_t)std::max(1, E) * 4)) ||
+      (rc = bp->ps_cp.alloc((size_t)(g->n + 1) * 4)) || (rc = bp->ps_ce.alloc((size_t)std::max(1, E) * 4)))
+    return rc;
+  if (hipMemcpy(bp->ps_rp.p, g->row_ptr.data(), (size_t)(g->m + 1) * 4, hipMemcpyHostToDevice) != hipSuccess ||
+      (E && hipMemcpy(bp->ps_ci.p, g->col_idx.data(), (size_t)E * 4, hipMemcpyHostToDevice) != hipSuccess) ||
+      hipMemcpy(bp->ps_cp.p, cp.data(), cp.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
+      (E && hipMemcpy(bp->ps_ce.p, ce.data(), (size_t)E * 4, hipMemcpyHostToDevice) != hipSuccess))
+    return set_err(QLDPC_EHIP, "upload the graph's CSR / CSC");
+  return 0;
+}
+
 // Engine 5 (product-sum): the row-ordered / column-ordered products need the
 // plain CSR and CSC (edge ids in row-major order, rows ascending per column).
 static int create_ps(qldpc_graph* g, const double* channel_probs, int32_t max_iter, int32_t precision,
@@ -1015,26 +1043,8 @@ static int create_ps(qldpc_graph* g, const double* channel_probs, int32_t max_it
     return code;
   };
   const int E = g->nnz;
-  std::vector<int32_t> cp(g->n + 1, 0), ce;
-  ce.reserve(E);
-  for (int j = 0; j < g->n; ++j) {
-    for (int i : g->col_rows[j]) {
-      const int* b = g->col_idx.data() + g->row_ptr[i];
-      const int* e = g->col_idx.data() + g->row_ptr[i + 1];
-      ce.push_back((int32_t)(std::lower_bound(b, e, j) - g->col_idx.data()));
-    }
-    cp[j + 1] = (int32_t)ce.size();
-  }
   int rc;
-  if ((rc = bp->ps_rp.alloc((size_t)(g->m + 1) * 4)) || (rc = bp->ps_ci.alloc((size_t)std::max(1, E) * 4)) ||
-      (rc = bp->ps_cp.alloc((size_t)(g->n + 1) * 4)) || (rc = bp->ps_ce.alloc((size_t)std::max(1, E) * 4)) ||
-      (rc = bp->llr.alloc((size_t)g->n * (precision == 32 ? 4 : 8))))
-    return fail(rc);
-  if (hipMemcpy(bp->ps_rp.p, g->row_ptr.data(), (size_t)(g->m + 1) * 4, hipMemcpyHostToDevice) != hipSuccess ||
-      (E && hipMemcpy(bp->ps_ci.p, g->col_idx.data(), (size_t)E * 4, hipMemcpyHostToDevice) != hipSuccess) ||
-      hipMemcpy(bp->ps_cp.p, cp.data(), cp.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-      (E && hipMemcpy(bp->ps_ce.p, ce.data(), (size_t)E * 4, hipMemcpyHostToDevice) != hipSuccess))
-    return fail(set_err(QLDPC_EHIP, "upload product-sum graph"));
+  if ((rc = upload_csr_csc(bp)) || (rc = bp->llr.alloc((size_t)g->n * (precision == 32 ? 4 : 8)))) return fail(rc);
   if ((rc = upload_llr(bp))) return fail(rc);
   // messages in LDS when 2E values fit in 96 KiB (>= 1 workgroup per CU with room), else in HBM
   const bool lds_msgs = ps_lds_bytes(precision, g->m, g->n, E, true) <= 96 * 1024;
@@ -1064,7 +1074,8 @@ static void bp1_prepare(qldpc_bp* bp) {
     qldpc_firstmin_destroy(bp->bp1);
     bp->bp1 = nullptr;
   }
-  bp->bp1_off = !(bp->max_iter == 1 && bp->method == 1) || env_int("QLDPC_BP1", 1) == 0;
+  // (a relay decoder with one iteration in all still runs its own law: memory term, solution weights)
+  bp->bp1_off = !(bp->max_iter == 1 && bp->method == 1) || bp->route.engine == 7 || env_int("QLDPC_BP1", 1) == 0;
   if (bp->bp1_off) return;
   const std::string keep = qldpc_rt::g_err;  // an ENOTSUP here is not the caller's error
   if (qldpc_firstmin_create(bp->g, bp->probs.data(), 0, bp->alpha, bp->route.precision, &bp->bp1) != 0) {
@@ -1689,9 +1700,79 @@ int qldpc_bp_destroy(qldpc_bp* bp) {
   if (!bp) return 0;
   if (bp->bp1) qldpc_firstmin_destroy(bp->bp1);
   for (DevBuf* d : {&bp->vchk, &bp->llr, &bp->rdeg, &bp->rowtab, &bp->perm, &bp->rperm, &bp->work, &bp->ps_rp, &bp->ps_ci, &bp->ps_cp,
-                    &bp->ps_ce, &bp->ps_ws, &bp->h_rp, &bp->h_rcol, &bp->h_rcpos, &bp->h_cp, &bp->h_crpos, &bp->h_ws})
+                    &bp->ps_ce, &bp->ps_ws, &bp->h_rp, &bp->h_rcol, &bp->h_rcpos, &bp->h_cp, &bp->h_crpos, &bp->h_ws,
+                    &bp->rl_gam, &bp->rl_wq})
     d->release();
   delete bp;
+  return 0;
+}
+
+// Engine 7 (relay.hip): Relay-BP, min-sum with a memory term run as a chain of legs.
+int qldpc_bp_create_relay(qldpc_graph* g, const double* channel_probs, int32_t pre_iter, double pre_gamma,
+                          int32_t num_legs, int32_t leg_iter, double gamma_lo, double gamma_hi, int32_t stop_nconv,
+                          uint64_t gamma_seed, double ms_scaling_factor, int32_t precision, qldpc_bp** out) {
+  if (!out) return set_err(QLDPC_EINVAL, "NULL argument");
+  int rc = validate_create(g, channel_probs, precision, QLDPC_MIN_SUM);
+  if (rc) return rc;
+  if ((rc = relay_check_params(g->n, pre_iter, pre_gamma, num_legs, leg_iter, gamma_lo, gamma_hi, stop_nconv, precision)))
+    return rc;
+  if ((long long)pre_iter + (long long)num_legs * leg_iter > 0x7fffffffLL)
+    return set_err(QLDPC_EINVAL, "relay: pre_iter + num_legs * leg_iter overflows");
+  QLDPC_HIP(hipSetDevice(g->device));
+  auto* bp = new qldpc_bp();
+  auto fail = [&](int code) {
+    qldpc_bp_destroy(bp);
+    return code;
+  };
+  bp->g = g;
+  bp->route.engine = 7;
+  bp->route.precision = precision;
+  bp->route.TB = 256;
+  bp->route.VPL = (g->n + 255) / 256;
+  bp->method = QLDPC_MIN_SUM;
+  bp->alpha = ms_scaling_factor;
+  bp->rl_pre_iter = pre_iter;
+  bp->rl_legs = num_legs;
+  bp->rl_leg_iter = num_legs > 0 ? leg_iter : 0;
+  bp->rl_stop = stop_nconv;
+  bp->rl_pre_gamma = pre_gamma;
+  bp->rl_lo = gamma_lo;
+  bp->rl_hi = gamma_hi;
+  bp->rl_seed = gamma_seed;
+  bp->max_iter = pre_iter + num_legs * bp->rl_leg_iter;
+  bp->probs.assign(channel_probs, channel_probs + g->n);
+  bp->bp1_off = true;
+  const int E = g->nnz;
+  const size_t tsize = precision == 32 ? 4 : 8;
+  if ((rc = upload_csr_csc(bp)) || (rc = bp->llr.alloc(std::max<size_t>(1, g->n) * tsize)) ||
+      (rc = bp->rl_wq.alloc(std::max<size_t>(1, g->n) * 8)) ||
+      (rc = bp->rl_gam.alloc(std::max<size_t>(1, (size_t)(num_legs + 1) * g->n) * tsize)) || (rc = upload_llr(bp)) ||
+      (rc = relay_upload_gammas(bp)))
+    return fail(rc);
+  // the whole per-decode image in LDS when it fits 160 KiB, else the messages in an HBM workspace
+  const bool lds_msgs =
+      relay_lds_bytes(precision, g->m, g->n, E, true, false) <= (size_t)kLdsMax && env_int("QLDPC_RELAY_WS", 0) != 1;
+  size_t lds = relay_lds_bytes(precision, g->m, g->n, E, lds_msgs, false);
+  if (lds > (size_t)kLdsMax) return fail(set_err(QLDPC_ENOTSUP, "graph too large for the relay engine's LDS state"));
+  // the graph's CSR / CSC staged in LDS as 16-bit words when that costs no resident workgroup (of
+  // the 8 that 256-thread workgroups can reach); QLDPC_RELAY_IDX=0 keeps the global walk
+  const size_t lds_idx = relay_lds_bytes(precision, g->m, g->n, E, lds_msgs, true);
+  auto resident = [](size_t bytes) { return std::min<size_t>(8, (size_t)kLdsMax / std::max<size_t>(1, bytes)); };
+  bp->rl_idx = E <= 0xffff && g->n <= 0xffff && g->m <= 0xffff && lds_idx <= (size_t)kLdsMax &&
+               resident(lds_idx) == resident(lds) && env_int("QLDPC_RELAY_IDX", 1) != 0;
+  if (bp->rl_idx) lds = lds_idx;
+  bp->route.lds_bytes = (int)lds;
+  bp->route.TB = relay_threads(lds, g->m, g->n);
+  bp->route.VPL = (g->n + bp->route.TB - 1) / bp->route.TB;
+  int nb = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, relay_kernel_ptr(precision, bp->rl_idx), bp->route.TB,
+                                                   bp->route.lds_bytes) != hipSuccess)
+    nb = 1;
+  bp->blocks_per_cu = std::max(1, nb);
+  if ((rc = device_cus(g->device, bp->cus))) return fail(rc);
+  bp->ps_grid = (long long)bp->blocks_per_cu * bp->cus;
+  if (!lds_msgs && (rc = bp->ps_ws.alloc(std::max<size_t>(1, (size_t)bp->ps_grid * 2 * E * tsize)))) return fail(rc);
+  *out = bp;
   return 0;
 }
 
@@ -1853,6 +1934,7 @@ static int decode_batch(qldpc_bp* bp, const uint8_t* d_synd, uint8_t* d_corr, in
   if (!d_post && bp->bp1) return qldpc_rt::bp1_decode(bp->bp1, d_synd, d_corr, d_iters, d_conv, B, (hipStream_t)stream);
   if (bp->route.engine == 5) return ps_decode_launch(bp, d_synd, d_corr, d_iters, d_conv, B, (hipStream_t)stream, d_post);
   if (bp->route.engine == 6) return hbm_decode_launch(bp, d_synd, d_corr, d_iters, d_conv, B, (hipStream_t)stream);
+  if (bp->route.engine == 7) return relay_decode_launch(bp, d_synd, d_corr, d_iters, d_conv, B, (hipStream_t)stream);
   const long long cap = (long long)bp->blocks_per_cu * bp->cus;
   if (bp->route.engine == 1) {
     DecArgs a;

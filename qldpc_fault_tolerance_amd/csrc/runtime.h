@@ -82,9 +82,17 @@ struct qldpc_bp {
   // engine-3 fp64 variable phase, static LDS model per workgroup-iteration (qldpc_bp_lds_model):
   // CS gather cycles / extra, V-slot read cycles / extra, v2c store group-cycles / extra
   int64_t lds_model[6] = {0, 0, 0, 0, 0, 0};
-  // engine 5 (product-sum, bp_ps.hip): CSR / CSC on the device, optional HBM message workspace
+  // engines 5 (product-sum, bp_ps.hip) and 7 (relay, relay.hip): CSR / CSC on the device, optional
+  // HBM message workspace, the persistent grid the workspace is cut for
   qldpc_rt::DevBuf ps_rp, ps_ci, ps_cp, ps_ce, ps_ws;
   long long ps_grid = 0;
+  // engine 7 (relay.hip): the chain's parameters (max_iter = pre_iter + legs * leg_iter), the gamma
+  // table T [legs + 1][n] and the integer solution weights [n]; llr holds L0 in variable order
+  int rl_pre_iter = 0, rl_legs = 0, rl_leg_iter = 0, rl_stop = 1;
+  double rl_pre_gamma = 0, rl_lo = 0, rl_hi = 0;
+  uint64_t rl_seed = 0;
+  qldpc_rt::DevBuf rl_gam, rl_wq;
+  bool rl_idx = false;  // the graph's CSR / CSC staged in LDS as 16-bit words
   // engine 6 (HBM-resident messages, bp_hbm.hip): uniform edge tables and the message workspace
   qldpc_rt::DevBuf h_rp, h_rcol, h_rcpos, h_cp, h_crpos, h_ws;
 };
@@ -121,6 +129,17 @@ const void* ps_kernel(int precision);
 int ps_decode_launch(const qldpc_bp* bp, const uint8_t* synd, uint8_t* corr, int32_t* iters, uint8_t* conv, int64_t B,
                      hipStream_t stream,
                      double* post = nullptr);
+
+// engine 7 (relay.hip)
+size_t relay_lds_bytes(int precision, int m, int n, int E, bool lds_messages, bool lds_index);
+const void* relay_kernel_ptr(int precision, bool lds_index);
+int relay_threads(size_t lds_bytes, int m, int n);
+int relay_check_params(int64_t n, int32_t pre_iter, double pre_gamma, int32_t num_legs, int32_t leg_iter,
+                       double gamma_lo, double gamma_hi, int32_t stop_nconv, int32_t precision);
+int relay_upload_priors(qldpc_bp* bp);
+int relay_upload_gammas(qldpc_bp* bp);
+int relay_decode_launch(const qldpc_bp* bp, const uint8_t* synd, uint8_t* corr, int32_t* iters, uint8_t* conv,
+                        int64_t B, hipStream_t stream);
 
 // GPU OSD handle built on this graph? (osd.hip; qldpc_phenl_set_final_osd checks it)
 bool osd_gpu_matches(const qldpc_osd_gpu* o, const qldpc_graph* g);

@@ -60,6 +60,46 @@ class BPDecoder:
         return self.decoder.decode_batch(synd)
 
 
+class RelayBPDecoder:
+    """Relay-BP (Mueller et al. 2025; no reference counterpart) on the engine's relay kernel
+    (``qldpc_bp_create_relay``, the law in include/qldpc_hip.h): min-sum BP with a per-variable
+    memory term, ``pre_iter`` iterations at strength ``pre_gamma``, then ``num_legs`` legs of
+    ``leg_iter`` iterations (default: ``pre_iter``) with strengths drawn from ``gamma_interval`` by
+    ``gamma_seed``; stops at ``stop_nconv`` solutions and returns the lightest.  ``decode`` /
+    ``decode_batch`` as :class:`BPDecoder`; ``.decoder`` is the :class:`~.engine.DeviceBP`, so the
+    simulators' fused paths take it as they take a ``BPDecoder``."""
+
+    def __init__(self, h, channel_probs, pre_iter, pre_gamma=0.125, num_legs=20, leg_iter=None,
+                 gamma_interval=(-0.24, 0.66), stop_nconv=1, gamma_seed=0, ms_scaling_factor=0.625,
+                 precision: int = 64, device: int | None = None):
+        from .engine import DeviceBP, RelayParams
+
+        self.h = h
+        self.ms_scaling_factor = ms_scaling_factor
+        self.channel_probs = np.asarray(channel_probs, dtype=np.float64)
+        H = h if isinstance(h, CSR) else CSR.from_dense(h)
+        self.num_checks, self.num_qubits = H.m, H.n
+        pre_iter = _int_max_iter(pre_iter, H.n)
+        self.relay = RelayParams(pre_iter=pre_iter, pre_gamma=float(pre_gamma), num_legs=int(num_legs),
+                                 leg_iter=_int_max_iter(leg_iter, H.n) if leg_iter is not None else pre_iter,
+                                 gamma_lo=float(gamma_interval[0]), gamma_hi=float(gamma_interval[1]),
+                                 stop_nconv=int(stop_nconv), gamma_seed=int(gamma_seed))
+        self.max_iter = self.relay.max_iter
+        self.decoder = DeviceBP(H, self.channel_probs, bp_method="minimum_sum", ms_scaling_factor=ms_scaling_factor,
+                                precision=precision, device=device, relay=self.relay)
+        self.iter = 0
+        self.converge = 0
+
+    def decode(self, synd):
+        corr, it, conv = self.decoder.decode_batch(np.asarray(synd).reshape(1, -1))
+        self.iter, self.converge = int(it[0]), int(conv[0])
+        return corr[0]
+
+    def decode_batch(self, synd):
+        """[B, m] syndromes -> ([B, n] corrections, iterations [B], converged [B])."""
+        return self.decoder.decode_batch(synd)
+
+
 class FirstMinBPDecoder:
     """Repeated one-iteration BP while the syndrome weight does not grow (``src/Decoders.py:49-74``).
 
@@ -236,6 +276,34 @@ class BP_Decoder_Class(DecoderClass):
                          bp_method=self.decoder_default_params["bp_method"],
                          ms_scaling_factor=self.decoder_default_params["ms_scaling_factor"],
                          precision=self.precision, device=self.device)
+
+
+class RelayBP_Decoder_Class(DecoderClass):
+    """:class:`RelayBPDecoder` factory keyed like :class:`BP_Decoder_Class` (``h``, ``p_data``, optional
+    ``p_syndrome``): ``pre_iter = n / pre_iter_ratio`` and ``leg_iter = n / leg_iter_ratio``, truncated
+    as ``max_iter_ratio`` is."""
+
+    def __init__(self, pre_iter_ratio, leg_iter_ratio, num_legs: int, ms_scaling_factor: float = 0.625,
+                 pre_gamma: float = 0.125, gamma_interval=(-0.24, 0.66), stop_nconv: int = 1, gamma_seed: int = 0,
+                 precision: int = 64, device: int | None = None):
+        self.decoder_default_params = {"pre_iter_ratio": pre_iter_ratio, "leg_iter_ratio": leg_iter_ratio,
+                                       "num_legs": num_legs, "ms_scaling_factor": ms_scaling_factor,
+                                       "pre_gamma": pre_gamma, "gamma_interval": tuple(gamma_interval),
+                                       "stop_nconv": stop_nconv, "gamma_seed": gamma_seed}
+        self.precision = precision
+        self.device = device
+
+    def GetDecoder(self, code_and_noise_channel_params):
+        p = code_and_noise_channel_params
+        assert "h" in p.keys(), "missing the check matrix h"
+        assert "p_data" in p.keys(), "missing the data error prob: p_data"
+        num_qubits, probs = BP_Decoder_Class._probs(p)
+        d = self.decoder_default_params
+        return RelayBPDecoder(h=p["h"], channel_probs=probs, pre_iter=num_qubits / d["pre_iter_ratio"],
+                              pre_gamma=d["pre_gamma"], num_legs=d["num_legs"],
+                              leg_iter=num_qubits / d["leg_iter_ratio"], gamma_interval=d["gamma_interval"],
+                              stop_nconv=d["stop_nconv"], gamma_seed=d["gamma_seed"],
+                              ms_scaling_factor=d["ms_scaling_factor"], precision=self.precision, device=self.device)
 
 
 class BPOSD_Decoder_Class(DecoderClass):

@@ -177,8 +177,42 @@ class DeviceGraph(_Handle):
                         self._ints("qldpc_graph_info", "graph_info", 5)))
 
 
+@dataclass(frozen=True)
+class RelayParams:
+    """The chain of a Relay-BP decoder (``qldpc_bp_create_relay``, include/qldpc_hip.h): ``pre_iter``
+    iterations at memory strength ``pre_gamma``, then ``num_legs`` legs of ``leg_iter`` iterations
+    whose per-variable strengths are drawn from ``[gamma_lo, gamma_hi]`` by ``gamma_seed``; the
+    chain stops at ``stop_nconv`` solutions and keeps the lightest."""
+
+    pre_iter: int
+    pre_gamma: float = 0.125
+    num_legs: int = 0
+    leg_iter: int = 0
+    gamma_lo: float = -0.24
+    gamma_hi: float = 0.66
+    stop_nconv: int = 1
+    gamma_seed: int = 0
+
+    @staticmethod
+    def of(relay) -> "RelayParams":
+        return relay if isinstance(relay, RelayParams) else RelayParams(**dict(relay))
+
+    @property
+    def max_iter(self) -> int:
+        return int(self.pre_iter) + int(self.num_legs) * int(self.leg_iter)
+
+    def abi(self, ms_scaling_factor, precision) -> tuple:
+        """The parameter block of the C entry points, in their order."""
+        return (int(self.pre_iter), float(self.pre_gamma), int(self.num_legs), int(self.leg_iter),
+                float(self.gamma_lo), float(self.gamma_hi), int(self.stop_nconv), _seed64(self.gamma_seed),
+                float(ms_scaling_factor), int(precision))
+
+
 class DeviceBP(_Handle):
     """``ldpc.bp_decoder`` equivalent on the GPU (``qldpc_bp_create``).
+
+    ``relay``: a :class:`RelayParams` (or a dict of its fields) makes the handle a Relay-BP decoder
+    (engine 7, ``qldpc_bp_create_relay``): min-sum only, ``max_iter`` is then the chain's total.
 
     ``anneal_iters``: moves of the annealed V-slot placement the fp64 engine-3 families run at
     creation (host time, one core: ~0.18 us per move; default 4000 per edge capped at 2^25, memoised
@@ -189,13 +223,14 @@ class DeviceBP(_Handle):
 
     def __init__(self, H, channel_probs, max_iter: int = 0, bp_method="minimum_sum", ms_scaling_factor=0.625,
                  precision: int = 64, vars_per_thread: int = 0, device: int | None = None, graph: DeviceGraph | None = None,
-                 min_col_slots: int = 0, soft: bool = False, hbm: bool = False, anneal_iters: int | None = None):
+                 min_col_slots: int = 0, soft: bool = False, hbm: bool = False, anneal_iters: int | None = None,
+                 relay=None):
         if anneal_iters is not None:  # read by qldpc_bp_create (QLDPC_M2S_ANNEAL) at creation only
             old = os.environ.get("QLDPC_M2S_ANNEAL")
             os.environ["QLDPC_M2S_ANNEAL"] = str(int(anneal_iters))
             try:
                 self.__init__(H, channel_probs, max_iter, bp_method, ms_scaling_factor, precision, vars_per_thread,
-                              device, graph, min_col_slots, soft, hbm, None)
+                              device, graph, min_col_slots, soft, hbm, None, relay)
             finally:
                 if old is None:
                     os.environ.pop("QLDPC_M2S_ANNEAL", None)
@@ -210,8 +245,14 @@ class DeviceBP(_Handle):
         self.ms_scaling_factor = float(ms_scaling_factor)
         self.precision = int(precision)
         self.soft = bool(soft)
+        self.relay = RelayParams.of(relay) if relay is not None else None
         common = (self.graph.handle, _np_ptr(self.channel_probs), self.max_iter)
-        if hbm:
+        if self.relay is not None:
+            if self.bp_method != 1 or self.soft or hbm:
+                raise NotImplementedError("Relay-BP is minimum_sum on its own engine, without soft output")
+            self.max_iter = self.relay.max_iter
+            self._create("qldpc_bp_create_relay", *common[:2], *self.relay.abi(self.ms_scaling_factor, self.precision))
+        elif hbm:
             # engine 6: HBM-resident messages (automatic when no LDS engine holds the image)
             if self.bp_method != 1:
                 raise NotImplementedError("the HBM-resident engine implements minimum_sum")
@@ -231,6 +272,13 @@ class DeviceBP(_Handle):
     @property
     def n(self):
         return self.graph.n
+
+    def set_channel_probs(self, channel_probs):
+        """New priors on the same handle (``qldpc_bp_set_channel_probs``)."""
+        probs = _channel_probs(channel_probs, self.graph.n)
+        _native.check(_native.lib().qldpc_bp_set_channel_probs(self.handle, _np_ptr(probs)),
+                      "qldpc_bp_set_channel_probs")
+        self.channel_probs = probs
 
     def geometry(self):
         g = dict(zip(["threads", "vars_per_thread", "lds_bytes", "blocks_per_cu"],
@@ -574,6 +622,38 @@ def sample_errors_weight(n, weight, px, py, pz, seed, shot_begin, shot_count, ho
     with torch.cuda.device(dev):
         _native.check(_native.lib().qldpc_sample_errors_weight(*args, _ptr(out), s), "qldpc_sample_errors_weight")
     return out
+
+
+def relay_gammas(n, relay, precision: int = 64):
+    """``qldpc_relay_gammas``: the memory strengths ``[num_legs + 1, n]`` of a Relay-BP decoder with
+    the :class:`RelayParams` ``relay`` (row 0 = ``pre_gamma``), as the kernels hold them (rounded to
+    float for ``precision`` 32), widened to float64.  Host only: needs the library, not a GPU."""
+    r = RelayParams.of(relay)
+    out = np.zeros((max(int(r.num_legs), -1) + 1, int(n)), dtype=np.float64)
+    _native.check(_native.lib().qldpc_relay_gammas(int(n), float(r.pre_gamma), int(r.num_legs), float(r.gamma_lo),
+                                                   float(r.gamma_hi), _seed64(r.gamma_seed), int(precision),
+                                                   _np_ptr(out)), "qldpc_relay_gammas")
+    return out
+
+
+def relay_decode_host(H, channel_probs, relay, synd, ms_scaling_factor=0.625, precision: int = 64, threads: int = 0):
+    """``qldpc_relay_decode_host``: the Relay-BP law in plain C++ on host memory (no GPU, any graph):
+    ``synd`` [B, m] -> (corr [B, n] int64, iters [B], converged [B] bool, solutions found [B])."""
+    c = H if isinstance(H, CSR) else CSR.from_dense(H)
+    r = RelayParams.of(relay)
+    s = _syndromes(synd, c.m)
+    B = s.shape[0]
+    probs = _channel_probs(channel_probs, c.n)
+    rp = np.ascontiguousarray(c.row_ptr, dtype=np.int32)
+    ci = np.ascontiguousarray(c.col_idx, dtype=np.int32)
+    corr = np.zeros((B, c.n), np.uint8)
+    iters = np.zeros(B, np.int32)
+    conv = np.zeros(B, np.uint8)
+    nsol = np.zeros(B, np.int32)
+    _native.check(_native.lib().qldpc_relay_decode_host(
+        c.m, c.n, _np_ptr(rp), _np_ptr(ci), _np_ptr(probs), *r.abi(ms_scaling_factor, precision), _np_ptr(s),
+        _np_ptr(corr), _np_ptr(iters), _np_ptr(conv), _np_ptr(nsol), B, int(threads)), "qldpc_relay_decode_host")
+    return corr.astype(np.int64), iters, conv.astype(bool), nsol
 
 
 def sample_errors(n, px, py, pz, seed, shot_begin, shot_count, uniforms=None, device: int | None = None,
