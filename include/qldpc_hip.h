@@ -138,6 +138,8 @@ int qldpc_bp_decode_batch_soft(qldpc_bp *bp, const uint8_t *d_synd, uint8_t *d_c
  *                uint8 [B] or NULL (converged shots copy bp_corr [B][n]),
  *                out_osd0 (or NULL) / out_osdw uint8 [B][n];
  *   threads    : <= 0 = OMP_NUM_THREADS if set, else all hardware threads.
+ * osd_e takes osd_order <= 20 (a candidate table of 2^order rows).  A syndrome outside the column
+ * space of H is solved on the elimination's pivot rows alone, as ldpc's LU solve does.
  */
 typedef struct qldpc_osd qldpc_osd;
 int qldpc_osd_create(int32_t m, int32_t n, const int32_t *row_ptr, const int32_t *col_idx,
@@ -149,7 +151,7 @@ int qldpc_osd_decode_batch(const qldpc_osd *osd, const uint8_t *synd, const doub
                            int32_t threads);
 
 /*
- * GPU OSD (n <= 8192, osd_e order <= 24): the same outputs as qldpc_osd_decode_batch, one
+ * GPU OSD (n <= 8192, osd_e order <= 20 as the host stage): the same outputs as qldpc_osd_decode_batch, one
  * workgroup per syndrome; all pointers are DEVICE pointers (d_post from
  * qldpc_bp_decode_batch_soft).  Uniform channel_probs weigh candidates by popcount; non-uniform
  * ones (the circuit-level DEM priors) by sum log(1/p_j), added in ascending column order as the
@@ -516,7 +518,7 @@ int qldpc_circ_set_round_firstmin(qldpc_circ *circ, qldpc_firstmin *fm);
 /* decoder2 as bposd_decoder (ST_BPOSD_Decoder_Circuit, src/Decoders_SpaceTime.py:277-292): dec2 from
  * qldpc_bp_create_soft and ONE of a GPU OSD or a host OSD stage on h2; a host stage is turned into a
  * GPU OSD with its method, order, rank and soft weights, so the launch never leaves the device —
- * except past the GPU kernel's envelope (n > 8192, osd_e order > 24), where the host stage decodes
+ * except past the GPU kernel's envelope (n > 8192; osd_e stops at order 20 in both stages), where the host stage decodes
  * the final layer (one synchronous D2H / H2D round trip per batch inside qldpc_circ_launch). */
 int qldpc_circ_set_final_osd(qldpc_circ *circ, qldpc_osd_gpu *osd_gpu, const qldpc_osd *osd_host);
 /* DEM sampler of qldpc_circ_launch / qldpc_circ_sample (stim's compile_detector_sampler().sample,

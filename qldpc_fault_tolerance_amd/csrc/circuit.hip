@@ -308,7 +308,7 @@ struct qldpc_circ {
   qldpc_bp* dec2 = nullptr;
   qldpc_osd_gpu* osd_gpu = nullptr;
   qldpc_osd_gpu* osd_owned = nullptr;  // the GPU OSD built from a host stage (qldpc_circ_set_final_osd)
-  // a host stage past the GPU kernel's envelope (n > 8192, osd_e order > 24, priors of 0 or 1): the
+  // a host stage past the GPU kernel's envelope (n > 8192, priors of 0 or 1): the
   // final layer's soft BP output goes to the host, through qldpc_osd_decode_batch, and back
   const qldpc_osd* osd_host = nullptr;
   std::vector<uint8_t> h_synd, h_conv, h_bpc, h_out;

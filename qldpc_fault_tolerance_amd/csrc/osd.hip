@@ -91,6 +91,27 @@ struct Basis {
       for (int q = 0; q < RW; ++q) c[q] ^= bc[q];
     }
   }
+  // Reduce a syndrome v in place on the key rows alone, accumulating into c: a set bit no basis
+  // vector is keyed by is passed over, where reduce() stops at it.  The key rows are Neal's pivot
+  // rows (both take the lowest row that keeps the pivot block non-singular), so c solves the pivot
+  // rows' equations exactly and ignores the others, as ldpc's LU solve does: the same as reduce()
+  // for a syndrome in the column space, and the LU solve's answer for one outside it.
+  void solve(u64* v, u64* c) const {
+    for (int q0 = 0; q0 < W; ++q0) {
+      u64 pend = v[q0];
+      while (pend) {
+        const int t = ctz64(pend);
+        pend &= pend - 1;
+        const int s = key[q0 * 64 + t];
+        if (s < 0) continue;
+        const u64* bv = &vec[(size_t)s * W];
+        const u64* bc = &comb[(size_t)s * RW];
+        for (int q = q0; q < W; ++q) v[q] ^= bv[q];
+        for (int q = 0; q < RW; ++q) c[q] ^= bc[q];
+        pend = v[q0] & ~((2ull << t) - 1);  // the bits above t, as the xor left them
+      }
+    }
+  }
 };
 
 void load_col(const qldpc_osd& O, int j, u64* v, int W) {
@@ -165,7 +186,7 @@ void osd_one(const qldpc_osd& O, Work& K, const uint8_t* synd, const double* pos
   std::fill(K.v.begin(), K.v.end(), 0ull);
   for (int i = 0; i < m; ++i)
     if (synd[i] & 1u) K.v[i >> 6] ^= 1ull << (i & 63);
-  B.reduce(K.v.data(), K.xs.data());
+  B.solve(K.v.data(), K.xs.data());
   auto expand = [&](const u64* x, uint8_t* dst) {
     std::fill(dst, dst + n, (uint8_t)0);
     for (int i = 0; i < r; ++i)
@@ -246,8 +267,10 @@ extern "C" {
 
 int qldpc_osd_create(int32_t m, int32_t n, const int32_t* row_ptr, const int32_t* col_idx,
                      const double* channel_probs, int32_t osd_method, int32_t osd_order, qldpc_osd** out) {
-  if (!row_ptr || !col_idx || !channel_probs || !out) return set_err(QLDPC_EINVAL, "NULL argument");
+  if (!row_ptr || !channel_probs || !out) return set_err(QLDPC_EINVAL, "NULL argument");
   if (m < 0 || n <= 0) return set_err(QLDPC_EINVAL, "bad matrix shape");
+  // (a matrix without entries has no column indices: qldpc_osd_gpu_create hands over an empty vector's data())
+  if (!col_idx && row_ptr[m] > 0) return set_err(QLDPC_EINVAL, "NULL argument");
   if (osd_method < 0 || osd_method > 2) return set_err(QLDPC_EINVAL, "osd_method must be 0 (osd_0), 1 (osd_e) or 2 (osd_cs)");
   if (osd_order < 0 || (osd_method == 1 && osd_order > 20))
     return set_err(QLDPC_EINVAL, "osd_order must be >= 0 (and <= 20 for osd_e)");
@@ -2817,8 +2840,8 @@ int qldpc_rt::osd_gpu_from_host(const qldpc_graph* g, const qldpc_osd* O, qldpc_
   if (!osd_host_matches(O, g)) return set_err(QLDPC_EINVAL, "host OSD stage was built on a different graph");
   const int osd_method = O->method, osd_order = O->order;
   int rc = 0;
-  if (g->n > kOsdMaxN || (osd_method == 1 && osd_order > 24))
-    return set_err(QLDPC_ENOTSUP, "GPU OSD: n > 8192 or osd_e order > 24");
+  if (g->n > kOsdMaxN || (osd_method == 1 && osd_order > 20))  // 20: the host stage's cap (qldpc_osd_create)
+    return set_err(QLDPC_ENOTSUP, "GPU OSD: n > 8192 or osd_e order > 20");
   auto* G = new qldpc_osd_gpu();
   G->host = *O;
   G->device = g->device;

@@ -385,9 +385,11 @@ class DeviceOSD(_Handle):
     """OSD on the GPU (``qldpc_osd_gpu_*``): one workgroup per non-converged syndrome, fed
     straight from the soft-output BP's device buffers.  Uniform priors weigh candidates by
     popcount; non-uniform ones (the circuit-level DEM priors) by sum log(1/p_j) in column order,
-    as the host stage.  ``supported`` says whether a graph qualifies (n <= 8192, osd_e order <= 24)."""
+    as the host stage.  ``supported`` says whether a graph qualifies (n <= ``MAX_N``, osd_e order <=
+    ``MAX_OSD_E_ORDER``, the host stage's cap: its candidate table has 2^order rows)."""
 
     MAX_N = 8192
+    MAX_OSD_E_ORDER = 20
     _destroy = "qldpc_osd_gpu_destroy"
 
     @staticmethod
@@ -398,7 +400,7 @@ class DeviceOSD(_Handle):
         except ValueError:
             return False
         return (n <= DeviceOSD.MAX_N and bool(np.all((p > 0) & (p < 1))) and meth in (0, 1, 2)
-                and not (meth == 1 and int(osd_order) > 24))
+                and not (meth == 1 and int(osd_order) > DeviceOSD.MAX_OSD_E_ORDER))
 
     def __init__(self, graph: DeviceGraph, channel_probs, osd_method="osd_e", osd_order=10):
         self.graph = graph
