@@ -75,11 +75,13 @@ class CSR:
     def matvec(self, v) -> np.ndarray:
         """``H @ v % 2`` for a 0/1 vector (or ``[B, n]`` batch)."""
         v = np.asarray(v).astype(np.uint8) & 1
-        if v.ndim == 1:
-            return np.bitwise_xor.reduceat(v[self.col_idx], self.row_ptr[:-1]) * (np.diff(self.row_ptr) > 0)
-        g = v[:, self.col_idx]
-        out = np.bitwise_xor.reduceat(g, self.row_ptr[:-1], axis=1)
-        out[:, np.diff(self.row_ptr) == 0] = 0
+        if self.m == 0:
+            return np.zeros(v.shape[:-1] + (0,), np.uint8)
+        # one padding entry: trailing empty rows (and H = 0) start at nnz, past the gathered values
+        g = np.zeros(v.shape[:-1] + (len(self.col_idx) + 1,), np.uint8)
+        g[..., :-1] = v[..., self.col_idx]
+        out = np.bitwise_xor.reduceat(g, self.row_ptr[:-1], axis=-1)
+        out[..., np.diff(self.row_ptr) == 0] = 0  # reduceat gives an empty segment its first entry
         return out
 
 

@@ -45,8 +45,8 @@ namespace {
 
 using namespace qldpc;
 
-constexpr int kHRow = 12;  // max row degree (compile-time register block)
-constexpr int kHCol = 12;  // max column degree
+constexpr int kHRow = qldpc_rt::kHbmMaxDeg;  // max row degree (compile-time register block)
+constexpr int kHCol = qldpc_rt::kHbmMaxDeg;  // max column degree
 constexpr int kHThreads = qldpc_rt::kHbmThreads;
 
 struct HArgs {
@@ -326,7 +326,7 @@ namespace qldpc_rt {
 int hbm_prepare(qldpc_bp* bp) {
   const qldpc_graph* g = bp->g;
   const int m = g->m, n = g->n, E = g->nnz;
-  if (g->max_row > kHRow || g->max_col > kHCol)
+  if (g->max_row > kHRow || g->max_col > kHCol)  // plan_route refuses these first (same message)
     return set_err(QLDPC_ENOTSUP, "HBM engine: row or column degree above 12");
   std::vector<int32_t> rcol((size_t)std::max(1, m) * kHRow, 0), rcpos((size_t)std::max(1, m) * kHRow, 0);
   std::vector<int32_t> cp(n + 1, 0), crpos((size_t)n * kHCol, 0);
@@ -366,7 +366,9 @@ bool hbm_xlds(const qldpc_bp* bp) {
 size_t hbm_wave_bytes(const qldpc_bp* bp) {
   const size_t tsize = bp->route.precision == 32 ? 4 : 8;
   const size_t b = (size_t)2 * bp->g->nnz * 64 * tsize + (hbm_xlds(bp) ? 0 : (size_t)bp->g->n * 64);
-  return (b + 255) & ~(size_t)255;
+  // an edgeless graph on the LDS-ballot path has no messages: one line, so that the wave count
+  // of hbm_decode_launch never divides by zero
+  return std::max<size_t>(256, (b + 255) & ~(size_t)255);
 }
 
 const void* hbm_kernel(int precision) {

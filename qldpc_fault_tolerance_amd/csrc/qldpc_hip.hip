@@ -1119,6 +1119,8 @@ static int validate_create(const qldpc_graph* g, const double* channel_probs, in
   if (precision != 32 && precision != 64) return set_err(QLDPC_EINVAL, "precision must be 32 or 64");
   if (bp_method != QLDPC_MIN_SUM && bp_method != QLDPC_PRODUCT_SUM)
     return set_err(QLDPC_EINVAL, "bp_method must be 0 (product_sum) or 1 (minimum_sum)");
+  // (n = 0 never gets a graph handle; the kernels read the first row and column unconditionally)
+  if (g->m <= 0) return set_err(QLDPC_EINVAL, "a decoder needs at least one check (m = 0)");
   return 0;
 }
 
@@ -1126,8 +1128,11 @@ static bool fits(const Route& c, const qldpc_graph* g) { return route_fits(c, ro
 
 // engine 6: messages in HBM, one decode per lane (bp_hbm.hip) -- requested, or when no LDS engine
 // serves the graph (`why`; QLDPC_HBM_FALLBACK=0 makes that an error instead)
-static int to_hbm(Route& r, std::vector<int32_t>& slot_var, const char* why = nullptr) {
+static int to_hbm(const qldpc_graph* g, Route& r, std::vector<int32_t>& slot_var, const char* why = nullptr) {
   if (why && env_int("QLDPC_HBM_FALLBACK", 1) == 0) return set_err(QLDPC_ENOTSUP, why);
+  // the engine's row / column records (hbm_prepare refuses the same graphs with the same message)
+  if (g->max_row > kHbmMaxDeg || g->max_col > kHbmMaxDeg)
+    return set_err(QLDPC_ENOTSUP, "HBM engine: row or column degree above 12");
   r.engine = 6;
   r.TB = kHbmThreads;
   r.VPL = 1;
@@ -1344,7 +1349,7 @@ static int plan_route(const qldpc_graph* g, bool uniform, int precision, int var
   if (r.engine == 3 && precision == 32 && colmax > 4 && colmax <= 6 && env_int("QLDPC_E3_D56", 1) != 0) r.DMAX = colmax;
   // fp64: column degree 5 on the <= 256-thread family (checked with the geometry below)
   if (r.engine == 3 && precision == 64 && colmax == 5 && env_int("QLDPC_E3_D56", 1) != 0) r.DMAX = 5;
-  if (r.engine == 6) return to_hbm(r, slot_var);
+  if (r.engine == 6) return to_hbm(g, r, slot_var);
   const int tsize = precision == 32 ? 4 : 8;
   if (r.engine == 1) {
     const int rc = choose_geometry(g->n, g->m, vars_per_thread, max_spill_free_vpl(precision, r.DMAX), r.TB, r.VPL);
@@ -1356,7 +1361,7 @@ static int plan_route(const qldpc_graph* g, bool uniform, int precision, int var
   r.nch = r.engine == 4 ? 8 * tsize / 16 : (std::max(1, g->max_row) * tsize + 15) / 16;
   // no LDS image addresses this many slots: HBM-resident messages (engine 6)
   if (route_vslots(r, g->m) >= 0xFFFF)
-    return to_hbm(r, slot_var, "V image exceeds 65535 message slots (QLDPC_HBM_FALLBACK=0)");
+    return to_hbm(g, r, slot_var, "V image exceeds 65535 message slots (QLDPC_HBM_FALLBACK=0)");
   // degree-5/6 variables hold 2.5x the registers of degree-4 ones: fewer per thread
   const int pref = r.DMAX == 4 ? kPrefVplR : 4;
   int vmax = r.DMAX == 4 ? kMaxVplR : 5;
@@ -1400,7 +1405,7 @@ static int plan_route(const qldpc_graph* g, bool uniform, int precision, int var
     }
   }
   // no LDS engine holds this decode: HBM-resident messages
-  if (r.lds_bytes > kLdsMax) return to_hbm(r, slot_var, "per-shot LDS image exceeds 160 KiB (QLDPC_HBM_FALLBACK=0)");
+  if (r.lds_bytes > kLdsMax) return to_hbm(g, r, slot_var, "per-shot LDS image exceeds 160 KiB (QLDPC_HBM_FALLBACK=0)");
   // slot -> variable map: identity, or (engine 3) degree <= 3 variables first
   const bool sort3 = r.engine == 3 && r.DMAX >= 4 && env_int("QLDPC_DEGSORT", 1) != 0;
   // byte-F kernels also keep degree <= 2 variables (the space-time measurement columns) in
@@ -1420,7 +1425,7 @@ static int plan_route(const qldpc_graph* g, bool uniform, int precision, int var
   if (slot_variant(r).dec_k) return 0;
   // no kernel compiled for this engine-3/4 geometry (e.g. fp32 images past 64 KiB at 8 variables per
   // thread, GenBicycleA4 over five rounds): the HBM-resident engine serves any graph
-  return (r.engine == 3 || r.engine == 4) ? to_hbm(r, slot_var, "no kernel variant") : set_err(QLDPC_ENOTSUP, "no kernel variant");
+  return (r.engine == 3 || r.engine == 4) ? to_hbm(g, r, slot_var, "no kernel variant") : set_err(QLDPC_ENOTSUP, "no kernel variant");
 }
 
 // ------------------------------------------------------------ host tables

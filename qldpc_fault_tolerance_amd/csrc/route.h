@@ -8,6 +8,7 @@
 namespace qldpc_rt {
 
 constexpr int kHbmThreads = 256;  // engine 6 workgroup (bp_hbm.hip)
+constexpr int kHbmMaxDeg = 12;    // engine 6 row / column records (bp_hbm.hip): the degrees it takes
 
 struct Route {
   int engine = 2, precision = 64;
