@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import distance_ref as ref
+from distance_cases import run_raw
 from qldpc_fault_tolerance_amd import _native, codes, gf2
 
 SYNTH_SEED = 0x51D5EED0  # tools/synth_hgp_codes.py
@@ -143,39 +144,19 @@ def test_trial_begin_above_2_to_32(oracle):
     assert np.array_equal(r.trial_min, tmin) and (r.weight, r.trial) == (bw, bt) and np.array_equal(r.witness, wit)
 
 
-def _run_host_raw(G, P, trials, seed=0):
-    """qldpc_dist_run_host on an explicit generator (rows may be dependent or zero)."""
-    L = _native.lib()
-    vp = ctypes.c_void_p
-    Gw = codes._pack_rows(G)
-    Pw = codes._pack_rows(P) if P is not None else None
-    h = vp()
-    _native.check(L.qldpc_dist_create(-1, G.shape[0], G.shape[1], 0 if P is None else P.shape[1], Gw.ctypes.data_as(vp),
-                                      Pw.ctypes.data_as(vp) if P is not None else None, ctypes.byref(h)), "create")
-    tmin = np.empty(trials, np.int32)
-    bw, bt = ctypes.c_int32(), ctypes.c_uint64()
-    wit = np.zeros(Gw.shape[1], "<u8")
-    _native.check(L.qldpc_dist_run_host(h, seed, 0, trials, tmin.ctypes.data_as(vp), ctypes.byref(bw), ctypes.byref(bt),
-                                        wit.ctypes.data_as(vp)), "run_host")
-    geo = [ctypes.c_int32(-1) for _ in range(4)]
-    assert L.qldpc_dist_geometry(h, *[ctypes.byref(g) for g in geo]) == 0
-    L.qldpc_dist_destroy(h)
-    return bw.value, tmin, codes._unpack_row(wit, G.shape[1]), [g.value for g in geo]
-
-
 def test_dependent_and_zero_generator_rows_never_give_weight_zero(oracle):
     c = get("toric3")
     G0 = gf2.nullspace(c.hx)
     G = np.vstack([G0, np.zeros((2, c.N), np.uint8), G0[0] ^ G0[1], G0[:3]])  # zero, dependent and repeated rows
     P = gf2.matmul(G, c.lx.T)
-    bw, tmin, wit, geo = _run_host_raw(G, P, 32)
+    bw, _, tmin, wit, geo = run_raw(G, P, 32)
     assert tmin.min() >= 1 and bw == 3 and int(wit.sum()) == 3
     assert geo == [0, 1, 1, 0]  # host handle: no threads, no LDS; one code word, one pairing word
     # the extra rows change nothing: same pivots, same reduced rows
     plain = codes.distance_search(c.hx, c.lx, trials=32, seed=0, backend="host")
     assert np.array_equal(tmin, plain.trial_min) and np.array_equal(wit, plain.witness)
     # classical on the same generator: every pivot row counts, still none of weight 0
-    bw2, tmin2, _, _ = _run_host_raw(G, None, 32)
+    bw2, _, tmin2, _, _ = run_raw(G, None, 32)
     assert tmin2.min() >= 1 and bw2 <= 3
     r = ref.search(oracle, G, None, 0, 0, 32)
     assert np.array_equal(r[3], tmin2)
