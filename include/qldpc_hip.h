@@ -61,9 +61,10 @@ int qldpc_abi_version(void);
 const char *qldpc_last_error(void);
 int qldpc_device_count(int *out);
 
-/* Build flags of this library: QLDPC_BUILD_EXPERIMENTAL when the measured-and-not-kept kernel
+/* Build flags of this library: QLDPC_BUILD_EXPERIMENTAL when the measured-and-not-kept BP kernel
  * families (c2s 31103, m2v 40103, fp64 257-512 threads 303, engine 4) are compiled in
- * (-DQLDPC_EXPERIMENTAL=1); the product build leaves them out and ignores their opt-ins. */
+ * (-DQLDPC_EXPERIMENTAL=1); the product build leaves them out and ignores their opt-ins.  The
+ * flag carries BP families only: the GPU OSD has no experimental variants. */
 #define QLDPC_BUILD_EXPERIMENTAL 1
 int qldpc_build_flags(void);
 
@@ -185,9 +186,9 @@ int qldpc_firstmin_decode(qldpc_firstmin *fm, const uint8_t *d_synd, uint8_t *d_
                           void *stream);
 
 /* Elimination geometry the handle chose (no reference counterpart; tests and DESIGN.md §4):
- * row_words = 64-bit words per register row (0: LDS / HBM image), window_words = the column
- * window's row words (0: none; its overruns are redone at full width), threads = per workgroup,
- * workgroups = the launch's persistent grid (the window launch's when there is one). */
+ * row_words = 64-bit words per register row (0: LDS / HBM image), window_words = always 0 (no
+ * layout holds a column window; the argument stays for the ABI), threads = per workgroup,
+ * workgroups = the launch's persistent grid. */
 int qldpc_osd_gpu_geometry(const qldpc_osd_gpu *osd, int32_t *row_words, int32_t *window_words, int32_t *threads,
                            int32_t *workgroups);
 

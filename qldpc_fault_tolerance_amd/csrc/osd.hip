@@ -28,18 +28,10 @@
 #include <cstdlib>
 #include <numeric>
 #include <thread>
-#include <type_traits>
 #include <utility>
 #include <vector>
 
 #include "runtime.h"
-
-// measured-and-not-kept elimination variants (panel modes PNL 1-5, two rows per thread, the column
-// window, two syndromes per workgroup): out of the product build unless -DQLDPC_EXPERIMENTAL=1
-#ifndef QLDPC_EXPERIMENTAL
-#define QLDPC_EXPERIMENTAL 0
-#endif
-
 
 using qldpc_rt::set_err;
 
@@ -396,76 +388,9 @@ __device__ inline unsigned long long osd_stamp() {
 #endif
 }
 constexpr int kOsdMaxN = 8192;
-// column-window launch: the mark a syndrome whose elimination overran the window leaves in its
-// outw[0] for the full-width redo launch (outputs are 0 / 1 bytes otherwise)
-constexpr uint8_t kOsdRedo = 0xFF;
-// column window: positions past rank + nh the window words cover (dependent positions allowed
-// before the rank is reached)
-constexpr int kOsdWinSlack = 64;
-// forward elimination (PNL 5): bytes of the compaction staging area (64 rows in, 64 out)
-__host__ __device__ inline size_t osd_fwd_stg_bytes(int wr) { return 2 * ((size_t)wr * 64 * 8 + 64 * 4); }
-// forward elimination: U words of pivot row k over pivot block B >= k / 64, packed upper-triangular
-// by blocks (block b's 64 rows hold RW - b words each)
-__host__ __device__ inline int osd_ul_at(int k, int B, int RW) {
-  const int b = k >> 6;
-  return 64 * (b * RW - (b * (b - 1)) / 2 + (B - b)) + (k & 63);
-}
-__host__ __device__ inline int osd_ul_words(int RW) { return 64 * (RW * (RW + 1) / 2); }
+constexpr uint8_t kOsdRedo = 0xFF;  // mark of the early-out behind the register-row pivot loop (never written)
 // register-row mode: pivot-row words read per batch ahead of their xors
-#ifndef QLDPC_OSD_XB
-#define QLDPC_OSD_XB 8
-#endif
-constexpr int kOsdXB = QLDPC_OSD_XB;
-// register-row mode: the lean per-pivot loop (one stamped LDS max per wave instead of a
-// triple-buffered atomicMin, a DPP row-broadcast wave minimum, pivots recorded in LDS); 0 = the
-// round-3 loop (A/B builds)
-#ifndef QLDPC_OSD_LEAN
-#define QLDPC_OSD_LEAN 1
-#endif
-// A/B build: one barrier per pivot in register-row mode (the candidate row published before the
-// search barrier, per-wave slots of two step parities)
-#ifndef QLDPC_OSD_1B
-#define QLDPC_OSD_1B 0
-#endif
-// register-row mode: Four-Russians groups of kOsdG pivots (QLDPC_OSD_M4R): within a group only
-// the pivot word is updated per pivot (plus a mask of the group pivots' start rows each row has
-// absorbed); at the group's end every row xors in ONE table entry (the xor of its mask's start
-// rows) per remaining word.  MEASURED AND NOT KEPT (A/B builds only): bit-exact (57 GPU tests),
-// n1600 BP+OSD 595 k (G = 4) / 596 k (G = 6) vs 614 k with the lean loop, n225 10.6 M vs 12.3 M
-// (profiles/r04/passr/): the group ends' two extra barriers and table build cost more than the
-// row xors they save
-#ifndef QLDPC_OSD_M4R
-#define QLDPC_OSD_M4R 0
-#endif
-#ifndef QLDPC_OSD_G
-#define QLDPC_OSD_G 4
-#endif
-constexpr bool kOsdM4R = QLDPC_OSD_M4R && !QLDPC_OSD_1B;
-// A/B build: OSD steps 4-5 from the register rows (see the RR branch's end); 0 = the HBM path
-#ifndef QLDPC_OSD_XREG
-#define QLDPC_OSD_XREG 0
-#endif
-// diagnostic A/B build: the lean loop's row xors done three times (same rows): the step's
-// sensitivity to its row-update VALU work
-#ifndef QLDPC_OSD_XOR3
-#define QLDPC_OSD_XOR3 0
-#endif
-// blocked mode (PNL 3): byte offset of the Four-Russians tables in the panel area (after the
-// half-words and masks [m] u32, pk [32], pidx [m]) and the area's size with them ([8][16][WR + 1] u64)
-__host__ __device__ inline size_t osd_blk_tab_off(int m) { return ((size_t)12 * m + 128 + 15) & ~(size_t)15; }
-inline size_t osd_blk_bytes(int m, int wr) { return osd_blk_tab_off(m) + (size_t)8 * 16 * (wr + 1) * 8; }
-
-constexpr int kOsdG = QLDPC_OSD_G;
-// rows of (WR + 1) words in the register-row pivot area: the pivot row (1), the one-barrier build's
-// per-wave slots, or the Four-Russians table (2^G rows) and its per-pivot slots (4 rows)
-constexpr int osd_prows(int lb) { return QLDPC_OSD_1B ? 2 * (lb / 64) : kOsdM4R ? (1 << kOsdG) + 4 : 1; }
-
-
-// calls f(integral_constant<int, Q>) for Q = 0, 1, ... while it returns true (compile-time word index)
-template <int... Q, class F>
-__device__ __attribute__((always_inline)) inline void osd_for_words(std::integer_sequence<int, Q...>, F&& f) {
-  (void)(f(std::integral_constant<int, Q>{}) && ...);
-}
+constexpr int kOsdXB = 8;
 
 struct OsdGpuArgs {
   const int32_t* rp;
@@ -485,11 +410,7 @@ struct OsdGpuArgs {
   int m_lds;  // 1: the matrix lives in LDS, aliasing the sort tables (copied out first), else in the HBM slice
   int bits_off;  // LDS byte offset of the used / syndrome bit-vectors
   int pbuf_off;  // register-row mode: LDS byte offset of the pivot-row broadcast buffer
-  int pnl_off;   // panel mode: LDS byte offset of the panel area (words, masks, pivot rows, indices)
-  int syn_lds;   // two-syndrome register-row kernel: LDS bytes per syndrome area
-  int win;       // 1: column-window launch (rows hold the first WR words only; a syndrome whose
-                 // elimination overruns them is marked for the redo launch), 2: the redo launch,
-                 // 3: test hook (QLDPC_OSD_WIN_REDO=1): a window launch that also marks every odd b
+  int win;  // always 0 (see the early-out behind the register-row pivot loop)
   long long ws_words, iws_ints;
 };
 
@@ -500,21 +421,10 @@ __device__ inline void row_xor(u64* __restrict__ dst, const u64* __restrict__ sr
   for (int q = 0; q < W; ++q) dst[(size_t)q * m] ^= src[(size_t)q * m];
 }
 
-// minimum of a 32-bit value over the 64 lanes of a wave (all lanes active): DPP quad and row
-// rotations give each lane its 16-lane row's minimum, four readlanes combine the rows
-__device__ inline uint32_t wave_min_u32(uint32_t v) {
-  auto mn = [](uint32_t a, uint32_t b) { return a < b ? a : b; };
-  v = mn(v, (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, false));   // quad_perm [1,0,3,2]
-  v = mn(v, (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x4E, 0xF, 0xF, false));   // quad_perm [2,3,0,1]
-  v = mn(v, (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x124, 0xF, 0xF, false));  // row_ror:4
-  v = mn(v, (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x128, 0xF, 0xF, false));  // row_ror:8
-  return mn(mn((uint32_t)__builtin_amdgcn_readlane((int)v, 0), (uint32_t)__builtin_amdgcn_readlane((int)v, 16)),
-            mn((uint32_t)__builtin_amdgcn_readlane((int)v, 32), (uint32_t)__builtin_amdgcn_readlane((int)v, 48)));
-}
-
-// the same minimum in 6 DPP VALU + 1 readlane: rotations give every lane its 16-lane row's
-// minimum, row_bcast:15 / row_bcast:31 fold rows 0-1 / 2-3 / all into lane 63 (the GFX9 DPP
-// broadcasts; the s_nops are the DPP read-after-VALU-write wait states).  All lanes active.
+// minimum of a 32-bit value over the 64 lanes of a wave (all lanes active) in 6 DPP VALU + 1
+// readlane: quad and row rotations give every lane its 16-lane row's minimum, row_bcast:15 /
+// row_bcast:31 fold rows 0-1 / 2-3 / all into lane 63 (the GFX9 DPP broadcasts; the s_nops are
+// the DPP read-after-VALU-write wait states)
 __device__ inline uint32_t wave_min_u32_bc(uint32_t v) {
   asm volatile(
       "s_nop 1\n\t"
@@ -558,18 +468,8 @@ __device__ inline u64 ord_key(double x) {
 // q.. in an LDS buffer and the rows that have the pivot bit xor them in registers, so a row
 // update costs no LDS writes (the word-major LDS / HBM image paid one 8-byte store per word and
 // row).  The reduced rows go to the HBM slice afterwards for the candidate bit-vectors.
-// PNL (register-row mode): panel elimination.  Pivots are searched a 64-column panel (one row word)
-// at a time by ONE wave that holds every row's panel word and a 64-bit combination mask per row
-// (which of the panel's pivot rows, in their panel-start state, the row has absorbed): no barrier
-// per pivot.  Then the panel's pivot rows publish their remaining words once and every row xors in
-// the rows its mask names (uniform loop, broadcast LDS reads).  Same pivots (the lexicographic
-// minimum of (first set bit >= scan position, row) over unused rows, on up-to-date words) and the
-// same reduced rows as the per-pivot elimination; three barriers per panel instead of two per pivot.
-// WPE: minimum waves per SIMD the VGPR budget is pinned to (two workgroups per CU: the
-// column-window kernels, 2 x 12 waves; the two-rows-per-thread blocked kernels, 2 x 6 waves).
-template <int LB, int WR = 0, int RPT = 1, int PNL = 0, int WPE = 1>
-__global__ void __launch_bounds__(LB) __attribute__((amdgpu_waves_per_eu(RPT == 2 ? 3 : WPE)))
-osd_gpu_kernel(OsdGpuArgs A) {
+template <int LB, int WR = 0>
+__global__ void __launch_bounds__(LB) osd_gpu_kernel(OsdGpuArgs A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, TB = blockDim.x;
   const int m = A.m, n = A.n, W = A.W, RW = A.RW, NP = A.NP, rank = A.rank;
@@ -579,7 +479,7 @@ osd_gpu_kernel(OsdGpuArgs A) {
   uint32_t* used = reinterpret_cast<uint32_t*>(smem + A.bits_off);  // [ceil(m/32)]
   uint32_t* sb = used + (m + 31) / 32;                         // [ceil(m/32)] syndrome, reduced
   __shared__ int s_piv[3], s_npiv;  // s_piv triple-buffered by position: reset two columns ahead
-  __shared__ uint32_t s_pivx;       // lean loop: (search step << 17) | (0x1FFFF - key), max over the waves
+  __shared__ uint32_t s_pivx;       // register rows: (search step << 17) | (0x1FFFF - key), max over the waves
   __shared__ u64 s_best, s_bestw;
   u64* Mg = A.ws + (size_t)blockIdx.x * A.ws_words;
   u64* X = Mg + (size_t)W * m;  // X[0] = S0, X[1 + j] = x(h_j)
@@ -610,7 +510,6 @@ osd_gpu_kernel(OsdGpuArgs A) {
   for (long long b = blockIdx.x; b < A.B; b += gridDim.x) {
     uint8_t* ow = A.outw + b * (long long)n;
     uint8_t* o0 = A.out0 ? A.out0 + b * (long long)n : nullptr;
-    if (A.win == 2 && ow[0] != kOsdRedo) continue;  // redo launch: only the window's overruns (uniform)
     if (A.shot && A.shot[b] < 0) continue;  // captured decode that converged at max_iter: no OSD
     if (A.conv && A.conv[b]) {  // BP converged: bposd_decoder returns the BP decoding
       for (int j = tid; j < n; j += TB) {
@@ -666,1087 +565,83 @@ osd_gpu_kernel(OsdGpuArgs A) {
       s_pivx = 0u;
     }
     __syncthreads();
-    bool xdone = false;  // uniform: S0 / x(h_j) built from the register rows (steps 4-5 done)
     if constexpr (kRR) {
-      // 2-3 (register rows): rows tid + j*TB (j < RPT) of the permuted H, words by compile-time index
-      u64 row[RPT][WR];
-      uint32_t sbit[RPT];
-      bool used_r[RPT];
+      // 2-3 (register rows): row tid of the permuted H, words by compile-time index
+      u64 row[WR];
 #pragma unroll
-      for (int j = 0; j < RPT; ++j) {
-        const int i = tid + j * TB;
+      for (int q = 0; q < WR; ++q) row[q] = 0;
+      uint32_t sbit = 0;
+      if (tid < m) {
+        for (int e = A.rp[tid]; e < A.rp[tid + 1]; ++e) {
+          const int p = pos[A.ci[e]];
+          const int pq = p >> 6;
+          const u64 bit = 1ull << (p & 63);
 #pragma unroll
-        for (int q = 0; q < WR; ++q) row[j][q] = 0;
-        sbit[j] = 0;
-        used_r[j] = i >= m;  // rows past m never become candidates
-        if (i < m) {
-          for (int e = A.rp[i]; e < A.rp[i + 1]; ++e) {
-            const int p = pos[A.ci[e]];
-            const int pq = p >> 6;
-            const u64 bit = 1ull << (p & 63);
-#pragma unroll
-            for (int q = 0; q < WR; ++q) row[j][q] ^= (pq == q) ? bit : 0ull;
-          }
-          sbit[j] = synd[i] & 1u;
+          for (int q = 0; q < WR; ++q) row[q] ^= (pq == q) ? bit : 0ull;
         }
+        sbit = synd[tid] & 1u;
       }
       u64* pbuf = reinterpret_cast<u64*>(smem + A.pbuf_off);  // [WR] pivot row, [WR] its syndrome bit
       OSD_ST(1)
       int npiv = 0;   // uniform
-      if constexpr (PNL == 3) {
-        // Blocked elimination (round 5; opt-in QLDPC_OSD_PNL=3, measured
-        // slower than the lean loop): the
-        // per-pivot loops below cost every wave two barriers and a pivot-row round trip per pivot
-        // (~2,100 cycles per pivot at n1600, 0.62 of wave cycles parked, profiles/r04/passt/).  Here
-        // the pivots of a 32-column panel (half a row word) are found by ONE search wave with no
-        // barrier per pivot: it holds every row's panel half-word (rows s * 64 + lane, SM slots) and
-        // a 32-bit combination mask per row (which of the panel's pivot rows, in their panel-start
-        // state, the row has absorbed); a pivot step is a wave minimum over the unused rows' first
-        // set bits (the lexicographic minimum of (column, row): the greedy scan's pivot and its lowest
-        // row, as the loops below pick it), two readlanes and a masked xor per slot.  Then the panel's
-        // pivot rows publish their panel-start words q.. (+ syndrome bit) as the single entries of
-        // 4-pivot Four-Russians tables (16 combinations per group), the workgroup fills the tables,
-        // and every row xors in ONE table entry per group for everything past the panel.  Exact: the
-        // same pivots, pivot rows and reduced rows as the per-pivot elimination (an unused row is zero
-        // before the scan position, so the pivot rows' earlier words are zero and the words < q never
-        // change).  Four barriers per panel instead of two per pivot.
-        constexpr int SM = (LB * RPT) / 64;  // row slots per lane of the search wave (rows s * 64 + lane)
-        constexpr u64 kLo = 0xFFFFFFFFull, kHi = ~kLo;
-        constexpr int TS = WR + 1;   // table entry stride: words of a start row + its syndrome bit
-        uint32_t* pw = reinterpret_cast<uint32_t*>(smem + A.pnl_off);  // [m] panel half-words
-        uint32_t* pmsk = pw + m;                                       // [m] combination masks
-        int* pk = reinterpret_cast<int*>(pmsk + m);                    // [32] the panel's pivot rows
-        int* pidx = pk + 32;                                           // [m] panel index of a pivot row
-        u64* T = reinterpret_cast<u64*>(smem + A.pnl_off + osd_blk_tab_off(m));  // [8 groups][16][TS]
-        int32_t* lkk = reinterpret_cast<int32_t*>(smem);  // pivots (position << 11) | row, over the dead sort keys
-        __shared__ int s_P;
-        uint32_t usedm = 0;  // search wave: bit s = row s * 64 + lane is used (rows >= m: always)
-        if (tid < 64) {
-#pragma unroll
-          for (int s2 = 0; s2 < SM; ++s2)
-            if (s2 * 64 + tid >= m) usedm |= 1u << s2;
-        }
-        // one compile-time word q per call (every row word stays in a VGPR; a runtime q would index
-        // the row array and demote it to scratch)
-        auto blk_word = [&](auto qc) __attribute__((always_inline)) -> bool {
-          constexpr int q = decltype(qc)::value;
-          if (q * 64 >= n || npiv >= rank) return false;  // uniform
-          for (int h = 0; h < 2; ++h) {
-            if (q * 64 + h * 32 >= n || npiv >= rank) break;  // uniform
-            // 1. every row's panel half-word (every earlier panel applied)
-            unsigned long long tb0 = QLDPC_STAMPS ? osd_stamp() : 0ull;
-#pragma unroll
-            for (int j = 0; j < RPT; ++j)
-              if (tid + j * TB < m) pw[tid + j * TB] = (uint32_t)(row[j][q] >> (32 * h));
-            __syncthreads();
-            if (QLDPC_STAMPS) {  // [11]: step 1 + its barrier
-              const unsigned long long t = osd_stamp();
-              st[11] += t - tb0;
-              tb0 = t;
-            }
-            // 2. the search wave: the panel's greedy pivots, its rows' final half-words and masks
-            if (tid < 64) {
-              // a lone wave is latency-bound: the pivot step keeps its dependent chains short (unused
-              // masks as VGPRs, a min3 tree over the slots, a 4-level select tree for the pivot row's
-              // half-word and mask, the pivot list in one VGPR written after the panel)
-              uint32_t wv[SM], cm[SM];
-              uint32_t ub = ~usedm;  // bit s: row s * 64 + lane is a candidate (unused, < m)
-#pragma unroll
-              for (int s2 = 0; s2 < SM; ++s2) {
-                wv[s2] = s2 * 64 + tid < m ? pw[s2 * 64 + tid] : 0u;
-                cm[s2] = 0u;
-              }
-              uint32_t pkv = 0;  // lane k: (position << 11) | row of the panel's pivot k
-              int P = 0, np = npiv;
-              while (np < rank) {  // uniform
-                // key = (first set bit << 11) | row over the unused rows; none: >= 0xFFFFF800
-                uint32_t kk[SM];
-#pragma unroll
-                for (int s2 = 0; s2 < SM; ++s2) {
-                  const uint32_t um = (uint32_t)__builtin_amdgcn_sbfe((int)ub, s2, 1);
-                  kk[s2] = (ffbl_u32(wv[s2] & um) << 11) | (uint32_t)(s2 * 64 + tid);
-                }
-                // min3 tree over the slots (compile-time shapes: SM <= 16 -> at most 3 levels)
-                constexpr int N1 = (SM + 2) / 3, N2 = (N1 + 2) / 3, N3 = (N2 + 2) / 3;
-                auto mn = [](uint32_t a, uint32_t b) { return a < b ? a : b; };
-                uint32_t l1[N1], l2[N2];
-#pragma unroll
-                for (int i = 0; i < N1; ++i)
-                  l1[i] = mn(kk[3 * i], mn(3 * i + 1 < SM ? kk[3 * i + 1 < SM ? 3 * i + 1 : 0] : ~0u,
-                                           3 * i + 2 < SM ? kk[3 * i + 2 < SM ? 3 * i + 2 : 0] : ~0u));
-#pragma unroll
-                for (int i = 0; i < N2; ++i)
-                  l2[i] = mn(l1[3 * i], mn(3 * i + 1 < N1 ? l1[3 * i + 1 < N1 ? 3 * i + 1 : 0] : ~0u,
-                                           3 * i + 2 < N1 ? l1[3 * i + 2 < N1 ? 3 * i + 2 : 0] : ~0u));
-                static_assert(N3 == 1, "search wave: at most 27 row slots");
-                const uint32_t key = wave_min_u32_bc(mn(l2[0], mn(N2 > 1 ? l2[N2 > 1 ? 1 : 0] : ~0u,
-                                                                  N2 > 2 ? l2[N2 > 2 ? 2 : 0] : ~0u)));
-                if (key > 0x1FFFFu) break;  // no pivot left in this panel (uniform)
-                const int fb = (int)(key >> 11), r = (int)(key & 2047u), sr = r >> 6, lr = r & 63;
-                // the pivot row's half-word and mask: a select tree on sr's bits (levels of halving
-                // arrays, short live ranges), then one readlane each
-                constexpr int H1 = (SM + 1) / 2, H2 = (H1 + 1) / 2, H3 = (H2 + 1) / 2;
-                uint32_t aw[H1], ac[H1];
-                {
-                  // bitwise selects (a select of two array loads would become a load at a selected
-                  // index: a dynamically indexed array, demoted to scratch)
-                  const uint32_t msk = (sr & 1) ? ~0u : 0u;  // uniform
-#pragma unroll
-                  for (int i = 0; i < H1; ++i) {
-                    aw[i] = wv[2 * i] ^ ((wv[2 * i] ^ wv[2 * i + 1 < SM ? 2 * i + 1 : 2 * i]) & msk);
-                    ac[i] = cm[2 * i] ^ ((cm[2 * i] ^ cm[2 * i + 1 < SM ? 2 * i + 1 : 2 * i]) & msk);
-                  }
-                }
-                uint32_t bw[H2], bc[H2];
-                {
-                  const uint32_t msk = (sr & 2) ? ~0u : 0u;
-#pragma unroll
-                  for (int i = 0; i < H2; ++i) {
-                    bw[i] = aw[2 * i] ^ ((aw[2 * i] ^ aw[2 * i + 1 < H1 ? 2 * i + 1 : 2 * i]) & msk);
-                    bc[i] = ac[2 * i] ^ ((ac[2 * i] ^ ac[2 * i + 1 < H1 ? 2 * i + 1 : 2 * i]) & msk);
-                  }
-                }
-                uint32_t cw[H3], cc[H3];
-                {
-                  const uint32_t msk = (sr & 4) ? ~0u : 0u;
-#pragma unroll
-                  for (int i = 0; i < H3; ++i) {
-                    cw[i] = bw[2 * i] ^ ((bw[2 * i] ^ bw[2 * i + 1 < H2 ? 2 * i + 1 : 2 * i]) & msk);
-                    cc[i] = bc[2 * i] ^ ((bc[2 * i] ^ bc[2 * i + 1 < H2 ? 2 * i + 1 : 2 * i]) & msk);
-                  }
-                }
-                uint32_t dw = cw[0], dc = cc[0];
-                if constexpr (H3 > 1) {
-                  const uint32_t msk = (sr & 8) ? ~0u : 0u;
-                  dw = cw[0] ^ ((cw[0] ^ cw[H3 > 1 ? 1 : 0]) & msk);
-                  dc = cc[0] ^ ((cc[0] ^ cc[H3 > 1 ? 1 : 0]) & msk);
-                }
-                static_assert(SM <= 16, "search wave: at most 16 row slots");
-                const uint32_t pwv = (uint32_t)__builtin_amdgcn_readlane((int)dw, lr);
-                const uint32_t pmv = (uint32_t)__builtin_amdgcn_readlane((int)dc, lr);
-                const uint32_t add = pmv | (1u << P);
-                const bool me = tid == lr;
-#pragma unroll
-                for (int s2 = 0; s2 < SM; ++s2) {
-                  const uint32_t sel = (uint32_t)__builtin_amdgcn_sbfe((int)wv[s2], fb, 1);  // -(bit fb)
-                  const bool pr = me && s2 == sr;  // the pivot row keeps its word and mask
-                  wv[s2] = pr ? pwv : wv[s2] ^ (pwv & sel);
-                  cm[s2] = pr ? pmv : cm[s2] ^ (add & sel);
-                }
-                ub = me ? (ub & ~(1u << sr)) : ub;  // the pivot row leaves the candidates
-                pkv = tid == P ? (uint32_t)(((q * 64 + h * 32 + fb) << 11) | r) : pkv;
-                ++P;
-                ++np;
-              }
-              if (tid < P) {
-                lkk[npiv + tid] = (int32_t)pkv;
-                pk[tid] = (int)(pkv & 2047u);
-                pidx[pkv & 2047u] = tid;
-              }
-#pragma unroll
-              for (int s2 = 0; s2 < SM; ++s2)
-                if (s2 * 64 + tid < m) {
-                  pw[s2 * 64 + tid] = wv[s2];
-                  pmsk[s2 * 64 + tid] = cm[s2];
-                }
-              usedm = ~ub;
-              if (tid == 0) {
-                s_P = P;
-                s_npiv = np;
-              }
-              if (QLDPC_STAMPS) {  // [8]: the search, [7]: its pivots
-                const unsigned long long t = osd_stamp();
-                st[8] += t - tb0;
-                st[7] += (unsigned long long)P;
-                tb0 = t;
-              }
-            }
-            __syncthreads();
-            const int P = s_P;
-            npiv = s_npiv;
-            // 3. the panel's pivot rows publish their panel-start rows (words q.., syndrome bit) as
-            // the single entries of their group's table; every row takes its final half-word and mask
-            uint32_t cmk[RPT], fw[RPT];
-#pragma unroll
-            for (int j = 0; j < RPT; ++j) {
-              const int i = tid + j * TB;
-              cmk[j] = 0;
-              fw[j] = 0;
-              if (i < m) {
-                cmk[j] = pmsk[i];
-                fw[j] = pw[i];
-                const int kx = pidx[i];
-                if (kx >= 0 && kx < P && pk[kx] == i) {  // (stale entries of earlier panels fail the check)
-                  used_r[j] = true;
-                  u64* d = T + (size_t)((kx >> 2) * 16 + (1 << (kx & 3))) * TS;
-#pragma unroll
-                  for (int q2 = q; q2 < WR; ++q2) d[q2] = row[j][q2];
-                  d[WR] = sbit[j];
-                }
-              }
-            }
-            __syncthreads();
-            // 4. every group's entries of >= 2 pivots: the xor of its single entries
-            const int ng = (P + 3) >> 2;
-            constexpr int nw = WR + 1 - q;  // words q..WR-1 and the syndrome entry
-            for (int t = tid; t < ng * 16 * nw; t += TB) {
-              const int gc = t / nw, c = gc & 15;
-              const int wd = q + t % nw;
-              if (c & (c - 1)) {
-                const u64* g0 = T + (size_t)(gc - c) * TS + wd;
-                u64 v = 0;
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                  if ((c >> i) & 1) v ^= g0[(size_t)(1 << i) * TS];
-                T[(size_t)gc * TS + wd] = v;
-              }
-            }
-            __syncthreads();
-            if (QLDPC_STAMPS) {  // [9]: the search barrier, the single entries and the table fill
-              const unsigned long long t = osd_stamp();
-              st[9] += t - tb0;
-              tb0 = t;
-            }
-            // 5. every row: one table entry per group into everything past the panel (the high half
-            // of word q when the panel is its low half, words q + 1.., the syndrome bit); the panel
-            // half-word is the search's final value
-#pragma unroll
-            for (int j = 0; j < RPT; ++j) {
-              if (tid + j * TB < m) {
-                u64 accq = 0;
-                for (int g = 0; g < ng; ++g) {  // uniform bound
-                  const uint32_t c = (cmk[j] >> (4 * g)) & 15u;
-                  if (c) {
-                    const u64* src = T + (size_t)(g * 16 + (int)c) * TS;
-                    accq ^= src[q];
-#pragma unroll
-                    for (int q2 = q + 1; q2 < WR; ++q2) row[j][q2] ^= src[q2];
-                    sbit[j] ^= (uint32_t)src[WR];
-                  }
-                }
-                row[j][q] = h ? ((row[j][q] & kLo) | ((u64)fw[j] << 32)) : (((row[j][q] ^ accq) & kHi) | (u64)fw[j]);
-              }
-            }
-            if (QLDPC_STAMPS) st[10] += osd_stamp() - tb0;  // [10]: the row updates
-            // (pw is rewritten by the next panel's step 1 after these reads; T behind its first two barriers)
-          }
-          return true;
-        };
-        osd_for_words(std::make_integer_sequence<int, WR>{}, blk_word);
-        for (int i = tid; i < npiv; i += TB) {
-          const int v = lkk[i];
-          pivrow[i] = v & 2047;
-          pivpos[i] = v >> 11;
-        }
-      } else if constexpr (PNL == 5) {
-        // Forward elimination with compaction (round 5; QLDPC_OSD_PNL=5, osd_0 / osd_e).  A pivot
-        // step costs every wave its search and its row xors (the step is VALU-bound: xoring the
-        // pivot row three times instead of once made the lean loop's OSD 47 % slower,
-        // profiles/r05/osd_notkept/xor3_*).  Gauss-Jordan xors the pivot row into EVERY row that has
-        // the bit; plain forward elimination only into the unused rows, and every 64 pivots the
-        // unused rows are packed into the leading waves (words q.. through an LDS staging area), so
-        // the trailing waves drop out of the search and the xors: about half of both.  A pivot row
-        // is final when chosen; the rows stay in registers (a compaction swaps the <= 64 rows used
-        // since the last one out of the leading slots against the unused rows behind them, through
-        // a 64-row LDS staging area) and go to the HBM slice once at the end, as row (pivot
-        // index) -- a per-pivot global store would hold its wave at every barrier.  The rows' U
-        // bits (bit p_k of pivot row i, k > i) are taken as the pivots come (a frozen row's bit
-        // at the pivot position) and kept in LDS by blocks of 64 pivots (osd_ul_at).  The
-        // Jordan half is done afterwards on the (1 + nh)-bit right-hand sides only (syndrome bit,
-        // the nh non-pivot columns Ht): U x = b by blocks of 64 pivots (after step 4 below).  Same
-        // pivots (lexicographic minimum of (first bit, ORIGINAL row)), same S0 / x(h_j).
-        // MEASURED AND NOT KEPT (opt-in): bit-exact (11 GPU tests incl. non-uniform priors and the
-        // circuit graphs), the elimination itself ~15 % shorter (1.21 M vs 1.41 M cycles per n1600
-        // syndrome, stamps), but the compactions (46 k) and the back substitution (63 k) take most
-        // of that back and the extra per-step bookkeeping the rest: n1600 BP+OSD-E(10) 581 k vs
-        // 617 k shots/s (profiles/r05/osd_notkept/fwd_*).  What the halved VALU does not touch is
-        // the step's latency chain (two barriers, four LDS round trips), ~1,100 of its ~1,800 cycles.
-        static_assert(RPT == 1, "forward elimination: one row per thread");
-        int32_t* lkk = reinterpret_cast<int32_t*>(smem);  // pivots: (sbit << 24) | (position << 11) | row
-        u64* stgA = reinterpret_cast<u64*>(smem + A.pnl_off);  // [WR][64] words of the rows moving in
-        u64* stgB = stgA + (size_t)WR * 64;                     // [WR][64] words of the rows moving out
-        uint32_t* siA = reinterpret_cast<uint32_t*>(stgB + (size_t)WR * 64);  // [64] row | sbit << 11 | (pivot + 1) << 12
-        uint32_t* siB = siA + 64;
-        u64* Ul = reinterpret_cast<u64*>(smem + A.pnl_off + osd_fwd_stg_bytes(WR));  // U words, osd_ul_at
-        __shared__ u64 s_bal[LB / 64];
-        const uint32_t pivx_a = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t*)(&s_pivx);
-        uint32_t step = 0;  // uniform
-        const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform
-        int rid = tid < m ? tid : 2047;       // original row of the slot
-        uint32_t um = used_r[0] ? 0u : ~0u;   // ~0 while the slot holds an unused row
-        int pk = -1;                          // pivot index of the slot's row (-1: not a pivot row)
-        u64 cu = 0;                           // the row's U bits over the pivots of block fl
-        int fl = 0;                           // uniform: U blocks flushed
-        int nact = ((m < TB ? m : TB) + 63) >> 6;  // uniform: waves that may hold unused rows
-        int ncomp = 64;                       // uniform: next compaction at npiv == ncomp
-        // one compile-time word q per call (a runtime q would index the row registers and put
-        // them in scratch; the body is too large for the unroller); false = stop
-        auto fwd_word = [&](auto qc) __attribute__((always_inline)) -> bool {
-          constexpr int q = decltype(qc)::value;
-          if (q * 64 >= n || npiv >= rank) return false;  // uniform
-          const int bend = n - q * 64 < 64 ? n - q * 64 : 64;
-          const u64 wmask = bend < 64 ? (1ull << bend) - 1ull : ~0ull;
-          int b = 0;
-          for (;;) {  // uniform
-            if (npiv >= ncomp) {  // uniform: permute the slots, unused rows first (stable)
-              const unsigned long long tc0 = QLDPC_STAMPS ? osd_stamp() : 0ull;
-              ncomp += 64;
-              if (pk >= 0) Ul[osd_ul_at(pk, fl, RW)] = cu;  // block fl of the U bits is complete
-              cu = 0;
-              ++fl;
-              const bool u = um != 0u;
-              const unsigned long long bal = __ballot(u);
-              if ((tid & 63) == 0) s_bal[wv] = bal;
-              __syncthreads();
-              // lane l reads wave l's ballot (one LDS round trip); sums by readlane (SALU adds)
-              const int ln = tid & 63;
-              const unsigned long long bl = ln < (TB >> 6) ? s_bal[ln] : 0ull;
-              const int cl = (int)__popcll(bl);
-              int base = 0, tot = 0;  // unused rows in slots before this wave's / in all
-#pragma unroll
-              for (int w2 = 0; w2 < LB / 64; ++w2) {
-                const int cw = __builtin_amdgcn_readlane(cl, w2);
-                base += w2 < wv ? cw : 0;
-                tot += cw;
-              }
-              const int tw = tot >> 6;
-              const int ul = ln < tw ? cl : (ln == tw ? (int)__popcll(bl & ((1ull << (tot & 63)) - 1ull)) : 0);
-              int Ut = 0;  // unused rows in slots < tot (uniform)
-#pragma unroll
-              for (int w2 = 0; w2 < LB / 64; ++w2) Ut += __builtin_amdgcn_readlane(ul, w2);
-              const int Us = base + (int)__popcll(bal & ((1ull << (tid & 63)) - 1ull));
-              // holes: used rows in slots < tot; movers: unused rows in slots >= tot (as many)
-              const bool hole = !u && tid < tot, mover = u && tid >= tot;
-              const int hi = hole ? tid - Us : Us - Ut;
-              if (hole || mover) {
-                u64* dp = hole ? stgB : stgA;
-#pragma unroll
-                for (int q2 = 0; q2 < WR; ++q2) dp[(size_t)q2 * 64 + hi] = row[0][q2];
-                (hole ? siB : siA)[hi] = (uint32_t)rid | (sbit[0] << 11) | ((uint32_t)(pk + 1) << 12);
-              }
-              __syncthreads();  // (the staging is next written 64 pivots = 128 barriers later)
-              if (hole || mover) {
-                const u64* sp = hole ? stgA : stgB;
-#pragma unroll
-                for (int q2 = 0; q2 < WR; ++q2) row[0][q2] = sp[(size_t)q2 * 64 + hi];
-                const uint32_t v = (hole ? siA : siB)[hi];
-                rid = (int)(v & 2047u);
-                sbit[0] = (v >> 11) & 1u;
-                pk = (int)(v >> 12) - 1;
-                um = hole ? ~0u : 0u;
-              }
-              nact = __builtin_amdgcn_readfirstlane((tot + 63) >> 6);
-              if (QLDPC_STAMPS) st[15] += osd_stamp() - tc0;
-            }
-            ++step;
-            if (QLDPC_STAMPS) st[7] += 1;
-            if (wv < nact) {  // uniform per wave
-              const u64 lowm = (~0ull << b) & wmask;
-              const uint32_t ml = (uint32_t)row[0][q] & (uint32_t)lowm & um;
-              const uint32_t mh = (uint32_t)(row[0][q] >> 32) & (uint32_t)(lowm >> 32) & um;
-              const uint32_t fl = ffbl_u32(ml), fh = ffbl_u32(mh) | 32u;
-              const uint32_t f = fl < fh ? fl : fh;
-              const uint32_t key = wave_min_u32_bc((f << 11) | (uint32_t)rid);
-              if ((tid & 63) == 0 && key <= 0x1FFFFu) lds_max_u32_sync(pivx_a, (step << 17) | (0x1FFFFu - key));
-            }
-            __syncthreads();
-            const uint32_t vx = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_pivx);  // uniform
-            if ((vx >> 17) != step) break;  // no pivot left in this word (uniform)
-            const uint32_t kk = 0x1FFFFu - (vx & 0x1FFFFu);
-            const int fb = (int)(kk >> 11), r = (int)(kk & 2047u);
-            const bool hbit = ((row[0][q] >> fb) & 1ull) != 0;
-            const bool upd = um != 0u && hbit && rid != r;
-            if (pk >= 0 && hbit) cu |= 1ull << (npiv & 63);  // a frozen pivot row: U bit
-            if (um != 0u && rid == r) {  // the pivot's owner: publish and record
-              um = 0u;
-              pk = npiv;
-#pragma unroll
-              for (int q2 = q; q2 < WR; ++q2) pbuf[q2] = row[0][q2];
-              pbuf[WR] = sbit[0];
-              lkk[npiv] = (int)((sbit[0] << 24) | ((uint32_t)(q * 64 + fb) << 11) | (uint32_t)r);
-            }
-            ++npiv;
-            __syncthreads();
-            if (upd) {  // pivot-row words through the rolling buffer, as the lean loop
-              constexpr int XB = kOsdXB;
-              u64 buf[XB];
-#pragma unroll
-              for (int u2 = 0; u2 < XB; ++u2)
-                if (q + u2 < WR) buf[u2] = pbuf[q + u2];
-              const uint32_t ps = (uint32_t)pbuf[WR];
-#pragma unroll
-              for (int q2 = q; q2 < WR; ++q2) {
-                const u64 pv = buf[(q2 - q) % XB];
-                if (q2 + XB < WR) buf[(q2 - q) % XB] = pbuf[q2 + XB];
-                row[0][q2] ^= pv;
-              }
-              sbit[0] ^= ps;
-            }
-            b = fb + 1;
-            if (b >= bend || npiv >= rank) break;  // uniform
-          }
-          return true;
-        };
-        osd_for_words(std::make_integer_sequence<int, WR>{}, fwd_word);
-        if (pk >= 0 && npiv > fl * 64) Ul[osd_ul_at(pk, fl, RW)] = cu;  // the last block's U bits
-        if (pk >= 0) {  // the pivot rows -> the HBM slice, row = pivot index
-          u64* mrow = Mg + pk;
-          asm volatile("" : "+v"(mrow));
-#pragma unroll
-          for (int q2 = 0; q2 < WR; ++q2)
-            if (q2 < W) mrow[(size_t)q2 * m] = row[0][q2];
-        }
-        // the pivot list -> pivrow / pivpos (every lkk write precedes one of the loop's barriers)
-        for (int i = tid; i < npiv; i += TB) {
-          const int v = lkk[i];
-          pivrow[i] = v & 2047;
-          pivpos[i] = (v >> 11) & 0x1FFF;
-        }
-      } else if constexpr (PNL == 4) {
-        // Lagged one-barrier loop (round 5; QLDPC_OSD_PNL=4).  The lean loop below walks two
-        // barriers and four dependent LDS round trips per pivot (search max, barrier, winner read,
-        // publication, barrier, pivot-row reads).  Here only the pivot WORD q is applied at once:
-        // before the search barrier every wave's best candidate row also leaves its word q in a
-        // per-wave slot, so after the barrier each row reads the winner and the winning wave's
-        // slot and updates its word q -- the next search reads nothing else.  The pivot's other
-        // words (and syndrome bit) are published by its owner after that barrier and applied one
-        // step later, after the next barrier (the owner of the next pivot applies them before it
-        // publishes its own row); at a word's end, and when the rank is reached, one extra barrier
-        // flushes the pending row.  Same pivots and the same reduced rows as the lean loop; one
-        // barrier per pivot.  Slots, winner words and pivot-row buffers are double-buffered by
-        // step / pivot parity: a buffer is rewritten two barriers after it was read.
-        // MEASURED AND NOT KEPT (opt-in): bit-exact (10 GPU tests incl. non-uniform priors and
-        // circuit graphs), but n1600 BP+OSD-E(10) 578 k vs 616 k shots/s with the lean loop
-        // (profiles/r05/osd_notkept/lag_*): the pending row xor and the slot round trip stay on
-        // every wave's path between two barriers, so halving the barriers shortens nothing.
-        static_assert(RPT == 1, "lagged loop: one row per thread");
-        __shared__ uint32_t s_pv[2];        // per step parity: (step << 17) | (0x1FFFF - key), max over waves
-        __shared__ u64 s_slot[2][LB / 64];  // per step parity and wave: word q of the wave's best row
-        int32_t* lkk = reinterpret_cast<int32_t*>(smem);  // pivots over the dead sort keys, as the lean loop
-        const uint32_t pv_a = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t*)(&s_pv[0]);
-        if (tid < 2) s_pv[tid] = 0u;
-        __syncthreads();
-        uint32_t step = 0;  // uniform
-        uint32_t um = used_r[0] ? 0u : ~0u;
-        const int wv = tid >> 6;
-        bool pend = false;  // uniform: a pivot row waits in pbuf half pp
-        int pp = 0;
-        bool phb = false;   // this row takes the pending pivot row (it had the pivot bit, not its owner)
-#pragma unroll
-        for (int q = 0; q < WR; ++q) {
-          if (q * 64 >= n || npiv >= rank) break;  // uniform
-          const int bend = n - q * 64 < 64 ? n - q * 64 : 64;
-          const u64 wmask = bend < 64 ? (1ull << bend) - 1ull : ~0ull;
-          // the pending pivot row's words q+1.. and syndrome bit (published before the last barrier)
-          auto apply_pending = [&]() __attribute__((always_inline)) {
-            if (pend) {  // uniform
-              const u64* pr = pbuf + (size_t)pp * (WR + 1);
-              if (phb) {
-                constexpr int XB = kOsdXB;
-                u64 buf[XB];
-#pragma unroll
-                for (int u = 0; u < XB; ++u)
-                  if (q + 1 + u < WR) buf[u] = pr[q + 1 + u];
-                const uint32_t ps = (uint32_t)pr[WR];
-#pragma unroll
-                for (int q2 = q + 1; q2 < WR; ++q2) {
-                  const u64 pv = buf[(q2 - q - 1) % XB];
-                  if (q2 + XB < WR) buf[(q2 - q - 1) % XB] = pr[q2 + XB];
-                  row[0][q2] ^= pv;
-                }
-                sbit[0] ^= ps;
-              }
-              pend = false;
-            }
-          };
-          int b = 0;
-          for (;;) {  // uniform
-            ++step;
-            asm volatile("" : "+s"(step));
-            const int par = (int)(step & 1u);
-            if (QLDPC_STAMPS) st[7] += 1;
-            const u64 lowm = (~0ull << b) & wmask;
-            const uint32_t ml = (uint32_t)row[0][q] & (uint32_t)lowm & um;
-            const uint32_t mh = (uint32_t)(row[0][q] >> 32) & (uint32_t)(lowm >> 32) & um;
-            const uint32_t fl = ffbl_u32(ml), fh = ffbl_u32(mh) | 32u;
-            const uint32_t f = fl < fh ? fl : fh;
-            const uint32_t key0 = (f << 11) | (uint32_t)tid;
-            const uint32_t key = wave_min_u32_bc(key0);
-            if (key <= 0x1FFFFu) {  // uniform per wave
-              if (key0 == key) s_slot[par][wv] = row[0][q];
-              if ((tid & 63) == 0) lds_max_u32_sync(pv_a + 4u * (uint32_t)par, (step << 17) | (0x1FFFFu - key));
-            }
-            __syncthreads();
-            const uint32_t vx = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_pv[par]);  // uniform
-            apply_pending();
-            if ((vx >> 17) != step) break;  // no pivot left in this word (uniform; nothing pending)
-            const uint32_t kk = 0x1FFFFu - (vx & 0x1FFFFu);
-            const int fb = (int)(kk >> 11), r = (int)(kk & 2047u);
-            const u64 pw = s_slot[par][r >> 6];
-            const bool hb = ((row[0][q] >> fb) & 1ull) != 0;
-            const bool own = tid == r;
-            if (hb && !own) row[0][q] ^= pw;
-            if (own) {
-              used_r[0] = true;
-              um = 0u;
-              u64* pr = pbuf + (size_t)(npiv & 1) * (WR + 1);
-#pragma unroll
-              for (int q2 = q + 1; q2 < WR; ++q2) pr[q2] = row[0][q2];
-              pr[WR] = sbit[0];
-              lkk[npiv] = ((q * 64 + fb) << 11) | r;
-            }
-            pend = true;
-            pp = npiv & 1;
-            phb = hb && !own;
-            ++npiv;
-            b = fb + 1;
-            if (b >= bend || npiv >= rank) {  // uniform: flush the pending row before the next word
-              __syncthreads();
-              apply_pending();
-              break;
-            }
-          }
-        }
-        // the pivot list -> pivrow / pivpos (every lkk write precedes one of the loop's barriers)
-        for (int i = tid; i < npiv; i += TB) {
-          const int v = lkk[i];
-          pivrow[i] = v & 2047;
-          pivpos[i] = v >> 11;
-        }
-      } else if constexpr (PNL) {
-        static_assert(RPT == 1, "panel mode: one row per thread");
-        constexpr int SM = LB / 64;  // row slots per lane of the search wave (rows s * 64 + lane)
-        constexpr u64 kLo = 0xFFFFFFFFull, kHi = ~kLo;
-        uint32_t* pw = reinterpret_cast<uint32_t*>(smem + A.pnl_off);  // [m] panel half-word of every row
-        uint32_t* pmask = pw + m;                                     // [m] combination masks
-        u64* prow = reinterpret_cast<u64*>(smem + A.pnl_off + (((size_t)8 * m + 15) & ~(size_t)15));  // [32][WR+1]
-        int* pk = reinterpret_cast<int*>(prow + 32 * (WR + 1));       // [32] pivot rows of the panel
-        int* pidx = pk + 32;                                          // [m] panel index of a pivot row
-        __shared__ int s_P;
-        __shared__ uint32_t s_wslot[2][LB / 64][2];  // PNL == 2: per step parity and wave, (half-word, mask)
-        int step3p = 0, sparp = 0;                   // PNL == 2: s_piv slot / s_wslot parity of the step
-        uint32_t usedm = 0;  // search wave: bit s = row s * 64 + lane is used (rows >= m: always)
-        if (tid < 64) {
-#pragma unroll
-          for (int s2 = 0; s2 < SM; ++s2)
-            if (s2 * 64 + tid >= m) usedm |= 1u << s2;
-        }
-        // panels of 32 columns (half a row word): 32-bit panel words and masks keep the search
-        // wave's state at 2 VGPRs per row slot.  Runtime panel index; row words are selected by
-        // compile-time index under uniform predicates (never indexed dynamically: they stay in VGPRs).
-        for (int qh = 0; qh < 2 * WR; ++qh) {
-          const int q = qh >> 1, h = qh & 1;
-          if (qh * 32 >= n || npiv >= rank) break;  // uniform
-          const int bend = n - qh * 32 < 32 ? n - qh * 32 : 32;
-          unsigned long long tp0 = QLDPC_STAMPS ? osd_stamp() : 0ull;
-          if constexpr (PNL == 2) {
-            // 1-2 (distributed panel, round 4): every thread keeps its own row's panel half-word and
-            // combination mask in VGPRs and searches it: per pivot one wave minimum, one LDS atomic
-            // and ONE barrier; each wave's best row publishes its (half-word, mask) in the wave's
-            // slot of this step's parity before that barrier, so the winner's pair is readable
-            // right after it (2 words, not the 25-word row of the per-pivot elimination)
-            uint32_t wv = 0, cm = 0;
-            if (tid < m) {
-              u64 wq = 0;
-#pragma unroll
-              for (int q2 = 0; q2 < WR; ++q2)
-                if (q2 == q) wq = row[0][q2];
-              wv = (uint32_t)(h ? wq >> 32 : wq);
-            }
-            bool usd = used_r[0];  // (rows >= m: used from the start)
-            const uint32_t wmask = bend < 32 ? (1u << bend) - 1u : ~0u;
-            int P = 0, b = 0;
-            while (b < bend && npiv < rank) {  // uniform
-              const int slot = step3p;
-              step3p = step3p == 2 ? 0 : step3p + 1;
-              const int par = sparp;
-              sparp ^= 1;
-              const uint32_t lowm = (~0u << b) & wmask;
-              const uint32_t mm = usd ? 0u : (wv & lowm);
-              uint32_t key = mm ? ((uint32_t)(__ffs((int)mm) - 1) << 11) | (uint32_t)tid : 0x7FFFFFFFu;
-              key = wave_min_u32(key);
-              if (key != 0x7FFFFFFFu && (uint32_t)tid == (key & 2047u)) {
-                s_wslot[par][tid >> 6][0] = wv;
-                s_wslot[par][tid >> 6][1] = cm;
-              }
-              if ((tid & 63) == 0 && key != 0x7FFFFFFFu) atomicMin(&s_piv[slot], (int)key);
-              __syncthreads();
-              const int kk = s_piv[slot];
-              if (tid == 0) s_piv[step3p == 2 ? 0 : step3p + 1] = 0x7FFFFFFF;  // re-arm two steps ahead
-              if (kk == 0x7FFFFFFF) break;  // no pivot left in this panel (uniform)
-              const int fb = kk >> 11, r = kk & 2047;
-              const uint32_t pwv = s_wslot[par][r >> 6][0], pmv = s_wslot[par][r >> 6][1];
-              if (tid == r) {
-                usd = true;
-                pivrow[npiv] = r;
-                pivpos[npiv] = qh * 32 + fb;
-                pk[P] = r;
-                pidx[r] = P;
-              }
-              const bool hb = ((wv >> fb) & 1u) != 0 && tid != r;
-              const uint32_t add = pmv | (1u << P);
-              wv ^= hb ? pwv : 0u;
-              cm ^= hb ? add : 0u;
-              ++P;
-              ++npiv;
-              b = fb + 1;
-            }
-            used_r[0] = usd;
-            if (tid < m) {
-              pw[tid] = wv;
-              pmask[tid] = cm;
-            }
-            if (tid == 0) {
-              s_P = P;
-              s_npiv = npiv;
-            }
-          } else {
-          // 1. every row's panel half-word (up to date: all earlier panels applied)
-          if (tid < m) {
-            u64 wq = 0;
-#pragma unroll
-            for (int q2 = 0; q2 < WR; ++q2)
-              if (q2 == q) wq = row[0][q2];
-            pw[tid] = (uint32_t)(h ? wq >> 32 : wq);
-          }
-          __syncthreads();
-          // 2. the search wave: greedy pivots of this panel, masks and final half-words of every row
-          if (tid < 64) {
-            uint32_t wv[SM], cm[SM];
-#pragma unroll
-            for (int s2 = 0; s2 < SM; ++s2) {
-              wv[s2] = s2 * 64 + tid < m ? pw[s2 * 64 + tid] : 0u;
-              cm[s2] = 0u;
-            }
-            const uint32_t wmask = bend < 32 ? (1u << bend) - 1u : ~0u;
-            int P = 0, b = 0;
-            while (b < bend && npiv < rank) {  // uniform
-              const uint32_t lowm = (~0u << b) & wmask;
-              uint32_t key = 0x7FFFFFFFu;  // (first set bit << 11) | row
-#pragma unroll
-              for (int s2 = 0; s2 < SM; ++s2) {
-                const uint32_t mm = ((usedm >> s2) & 1u) ? 0u : (wv[s2] & lowm);
-                const uint32_t kj = mm ? ((uint32_t)(__ffs((int)mm) - 1) << 11) | (uint32_t)(s2 * 64 + tid) : 0x7FFFFFFFu;
-                key = kj < key ? kj : key;
-              }
-              key = wave_min_u32(key);
-              if (key == 0x7FFFFFFFu) break;  // no pivot left in this panel (uniform)
-              const int fb = (int)(key >> 11), r = (int)(key & 2047u), sr = r >> 6, lr = r & 63;
-              uint32_t pwv = 0, pmv = 0;
-#pragma unroll
-              for (int s2 = 0; s2 < SM; ++s2)
-                if (s2 == sr) {  // uniform
-                  pwv = wv[s2];
-                  pmv = cm[s2];
-                }
-              pwv = (uint32_t)__builtin_amdgcn_readlane((int)pwv, lr);
-              pmv = (uint32_t)__builtin_amdgcn_readlane((int)pmv, lr);
-              if (tid == lr) usedm |= 1u << sr;
-              if (tid == 0) {
-                pivrow[npiv] = r;
-                pivpos[npiv] = qh * 32 + fb;
-                pk[P] = r;
-                pidx[r] = P;
-              }
-              const uint32_t add = pmv | (1u << P);
-#pragma unroll
-              for (int s2 = 0; s2 < SM; ++s2) {
-                const bool hb = ((wv[s2] >> fb) & 1u) != 0 && s2 * 64 + tid != r;
-                wv[s2] ^= hb ? pwv : 0u;
-                cm[s2] ^= hb ? add : 0u;
-              }
-              ++P;
-              ++npiv;
-              b = fb + 1;
-            }
-#pragma unroll
-            for (int s2 = 0; s2 < SM; ++s2)
-              if (s2 * 64 + tid < m) {
-                pw[s2 * 64 + tid] = wv[s2];
-                pmask[s2 * 64 + tid] = cm[s2];
-              }
-            if (tid == 0) {
-              s_P = P;
-              s_npiv = npiv;
-            }
-          }
-          }  // PNL == 1
-          __syncthreads();
-          const int P = s_P;
-          npiv = s_npiv;
-          if (QLDPC_STAMPS) {  // [8]: the panel's pivot search, [7]: its pivots
-            const unsigned long long t = osd_stamp();
-            st[8] += t - tp0;
-            st[7] += (unsigned long long)P;
-            tp0 = t;
-          }
-          // 3. the panel's pivot rows publish their panel-start words q.. and syndrome bit
-          if (tid < m) {
-            const int kx = pidx[tid];
-            if (kx >= 0 && kx < P && pk[kx] == tid) {  // (stale entries of earlier panels fail the check)
-              u64* dst = prow + kx * (WR + 1);
-#pragma unroll
-              for (int q2 = 0; q2 < WR; ++q2)
-                if (q2 >= q) dst[q2] = row[0][q2];
-              dst[WR] = sbit[0];
-            }
-          }
-          __syncthreads();
-          // 4. every row: the final panel half-word, then the named pivot rows into everything past
-          // the panel (the high half of word q when the panel is its low half, words q+1..)
-          if (tid < m) {
-            const uint32_t msk = pmask[tid];
-            u64 accq = 0;
-            for (int kx = 0; kx < P; ++kx) {  // uniform loop: one broadcast read per word
-              if constexpr (PNL == 2) {
-                // branch-free: every word read (independent broadcast loads the compiler keeps in
-                // flight together) and applied under predicates; the conditional form chained a
-                // load-wait-xor per word behind uniform branches (the PNL = 1 measurement)
-                const bool mine = ((msk >> kx) & 1u) != 0;
-                if (!__any(mine)) continue;  // (no row of this wave names pivot kx)
-                const u64* src = prow + kx * (WR + 1);
-                constexpr int XB = kOsdXB;
-                u64 buf[XB];
-#pragma unroll
-                for (int u = 0; u < XB; ++u)
-                  if (u < WR) buf[u] = src[u];
-                const uint32_t vs = (uint32_t)src[WR];
-                const u64 lowq = (mine && h == 0) ? ~0ull : 0ull;
-#pragma unroll
-                for (int q2 = 0; q2 < WR; ++q2) {
-                  const u64 pv = buf[q2 % XB];
-                  if (q2 + XB < WR) buf[q2 % XB] = src[q2 + XB];
-                  const u64 sel = (mine && q2 > q) ? ~0ull : 0ull;
-                  row[0][q2] ^= pv & sel;
-                  if (q2 == q) accq ^= pv & lowq;  // (q uniform: a select, no branch)
-                }
-                sbit[0] ^= mine ? vs : 0u;
-              } else if ((msk >> kx) & 1u) {
-                const u64* src = prow + kx * (WR + 1);
-#pragma unroll
-                for (int q2 = 0; q2 < WR; ++q2) {
-                  if (q2 == q && h == 0) accq ^= src[q2];
-                  if (q2 > q) row[0][q2] ^= src[q2];
-                }
-                sbit[0] ^= (uint32_t)src[WR];
-              }
-            }
-            const u64 fw = (u64)pw[tid];
-#pragma unroll
-            for (int q2 = 0; q2 < WR; ++q2)
-              if (q2 == q) row[0][q2] = h ? ((row[0][q2] & kLo) | (fw << 32)) : (((row[0][q2] ^ accq) & kHi) | fw);
-          }
-          if (QLDPC_STAMPS) st[9] += osd_stamp() - tp0;  // [9]: the panel's row updates
-          // (the next panel rewrites pw[tid] / prow only behind its first two barriers)
-        }
-      } else if constexpr (kOsdM4R && RPT == 1) {
-        // Four-Russians groups (round 4): the lean loop's search and winner (same pivots), but a
-        // pivot updates only the pivot word q of the rows that have its bit (exact, the next
-        // search reads nothing else) and their mask cm over the group's pivots: pivot k's row,
-        // as it is when chosen, is its group-start row S_k xor the start rows its own mask names,
-        // so absorbing it is cm ^= mask(k) ^ (1 << k).  At the group's end the pivot owners
-        // publish their start rows (words q+1.., syndrome bit) as T[1 << k], the workgroup fills
-        // T[c] = xor of the S_k, k in c, and every row xors T[cm] into its words q+1.. and its
-        // syndrome bit: one LDS read and one xor per word for up to kOsdG pivots.
-        int32_t* lkk = reinterpret_cast<int32_t*>(smem);
-        const uint32_t pivx_a = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t*)(&s_pivx);
-        u64* T = pbuf;                                         // [2^G][WR + 1]
-        u64* slot = pbuf + (size_t)(1 << kOsdG) * (WR + 1);   // [G][2]: pivot k's word q, its mask
-        uint32_t step = 0;  // uniform
-        uint32_t um = used_r[0] ? 0u : ~0u;
-        uint32_t cm = 0;    // the group pivots' start rows this row has absorbed
-        int gi = -1;        // this row's index among the group's pivots
-#pragma unroll
-        for (int q = 0; q < WR; ++q) {
-          if (q * 64 >= n || npiv >= rank) break;  // uniform
-          const int bend = n - q * 64 < 64 ? n - q * 64 : 64;
-          const u64 wmask = bend < 64 ? (1ull << bend) - 1ull : ~0ull;
-          int b = 0;
-          bool more = true;  // uniform
-          while (more) {
-            int k = 0;  // pivots in this group (uniform)
-            for (;;) {  // uniform
-              ++step;
-              asm volatile("" : "+s"(step));
-              if (QLDPC_STAMPS) st[7] += 1;
-              const u64 lowm = (~0ull << b) & wmask;
-              const uint32_t ml = (uint32_t)row[0][q] & (uint32_t)lowm & um;
-              const uint32_t mh = (uint32_t)(row[0][q] >> 32) & (uint32_t)(lowm >> 32) & um;
-              const uint32_t fl = ffbl_u32(ml), fh = ffbl_u32(mh) | 32u;
-              uint32_t key = ((fl < fh ? fl : fh) << 11) | (uint32_t)tid;
-              key = wave_min_u32_bc(key);
-              if ((tid & 63) == 0 && key <= 0x1FFFFu) lds_max_u32_sync(pivx_a, (step << 17) | (0x1FFFFu - key));
-              __syncthreads();
-              const uint32_t vx = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_pivx);  // uniform
-              if ((vx >> 17) != step) {  // no pivot left in this word
-                more = false;
-                break;
-              }
-              const uint32_t kk = 0x1FFFFu - (vx & 0x1FFFFu);
-              const int fb = (int)(kk >> 11), r = (int)(kk & 2047u);
-              const bool hb = ((row[0][q] >> fb) & 1ull) != 0;
-              if (tid == r) {
-                used_r[0] = true;
-                um = 0u;
-                gi = k;
-                slot[2 * k] = row[0][q];
-                slot[2 * k + 1] = cm;
-                lkk[npiv] = ((q * 64 + fb) << 11) | r;
-              }
-              ++npiv;
-              __syncthreads();
-              if (hb && tid != r) {
-                row[0][q] ^= slot[2 * k];
-                cm ^= (uint32_t)slot[2 * k + 1] ^ (1u << k);
-              }
-              ++k;
-              b = fb + 1;
-              if (b >= bend || npiv >= rank) {
-                more = false;
-                break;
-              }
-              if (k == kOsdG) break;
-            }
-            if (k > 0) {  // uniform: the group's end
-              if (gi >= 0) {
-                u64* d = T + (size_t)(1 << gi) * (WR + 1);
-#pragma unroll
-                for (int q2 = q + 1; q2 < WR; ++q2) d[q2] = row[0][q2];
-                d[WR] = sbit[0];
-              }
-              __syncthreads();
-              const int nw = WR - q;  // words q+1 .. WR-1 and the syndrome entry WR (constant once unrolled)
-              for (int t = tid; t < (nw << kOsdG); t += TB) {
-                const int c = t / nw, w = q + 1 + t % nw;
-                if ((c >> k) == 0 && (c & (c - 1)) != 0) {  // combinations of >= 2 of the k pivots
-                  u64 v = 0;
-#pragma unroll
-                  for (int i = 0; i < kOsdG; ++i)
-                    if ((c >> i) & 1) v ^= T[(size_t)(1 << i) * (WR + 1) + w];
-                  T[(size_t)c * (WR + 1) + w] = v;
-                }
-              }
-              __syncthreads();
-              if (cm) {
-                const u64* src = T + (size_t)cm * (WR + 1);
-#pragma unroll
-                for (int q2 = q + 1; q2 < WR; ++q2) row[0][q2] ^= src[q2];
-                sbit[0] ^= (uint32_t)src[WR];
-              }
-              cm = 0;
-              gi = -1;
-              // (T and the slots are rewritten only behind the next group's first barriers)
-            }
-          }
-        }
-        for (int i = tid; i < npiv; i += TB) {
-          const int v = lkk[i];
-          pivrow[i] = v & 2047;
-          pivpos[i] = v >> 11;
-        }
-      } else if constexpr (QLDPC_OSD_LEAN && !QLDPC_OSD_1B) {
-        // Lean per-pivot loop (round 4): same pivots as the loop below, fewer instructions per
-        // wave and step (a pivot step is bound by every wave's own instruction stream: all waves
-        // meet at its two barriers; profiles/r04/passo/).  The step's winner is the maximum of
-        // (step << 17) | (0x1FFFF - key) over one ds_max per wave: a stale value from an earlier
-        // step never matches the step, so the slot needs no re-arming.  Pivots go to an LDS list
-        // over the (dead) sort keys: (position << 11) | row.
-        int32_t* lkk = reinterpret_cast<int32_t*>(smem);
-        const uint32_t pivx_a = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t*)(&s_pivx);
-        uint32_t step = 0;  // uniform
-        uint32_t um[RPT];   // ~0 while row tid + j * TB is a candidate (unused, < m), else 0
-#pragma unroll
-        for (int j = 0; j < RPT; ++j) um[j] = used_r[j] ? 0u : ~0u;
-#pragma unroll
-        for (int q = 0; q < WR; ++q) {
-          if (q * 64 >= n || npiv >= rank) break;  // uniform
-          const int bend = n - q * 64 < 64 ? n - q * 64 : 64;
-          const u64 wmask = bend < 64 ? (1ull << bend) - 1ull : ~0ull;
-          int b = 0;
-          for (;;) {  // uniform
-            ++step;
-            asm volatile("" : "+s"(step));  // opaque: no strength-reduced copies of step << 17 per word
-            unsigned long long ts0 = 0;
-            if (QLDPC_STAMPS) {
-              ts0 = osd_stamp();
-              st[7] += 1;
-            }
-            const u64 lowm = (~0ull << b) & wmask;
-            // key = (first set bit >= b << 11) | row; a row without one gets first bit 0xFFFFFFFF
-            // (v_ffbl of 0), i.e. a key >= 0xFFFFF800, above every real key (<= 0x1FFFF)
-            uint32_t key = 0xFFFFFFFFu;
-#pragma unroll
-            for (int j = 0; j < RPT; ++j) {
-              const uint32_t ml = (uint32_t)row[j][q] & (uint32_t)lowm & um[j];
-              const uint32_t mh = (uint32_t)(row[j][q] >> 32) & (uint32_t)(lowm >> 32) & um[j];
-              const uint32_t fl = ffbl_u32(ml), fh = ffbl_u32(mh) | 32u;
-              const uint32_t f = fl < fh ? fl : fh;
-              const uint32_t kj = (f << 11) | (uint32_t)(tid + j * TB);
-              key = kj < key ? kj : key;
-            }
-            key = wave_min_u32_bc(key);
-            if ((tid & 63) == 0 && key <= 0x1FFFFu) lds_max_u32_sync(pivx_a, (step << 17) | (0x1FFFFu - key));
-            __syncthreads();
-            if (QLDPC_STAMPS) {
-              const unsigned long long t = osd_stamp();
-              st[8] += t - ts0;
-              ts0 = t;
-            }
-            const uint32_t vx = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_pivx);  // uniform
-            if ((vx >> 17) != step) break;  // no pivot left in this word (uniform)
-            const uint32_t kk = 0x1FFFFu - (vx & 0x1FFFFu);
-            const int fb = (int)(kk >> 11), r = (int)(kk & 2047u);
-            bool hb[RPT];
-#pragma unroll
-            for (int j = 0; j < RPT; ++j) {
-              hb[j] = ((row[j][q] >> fb) & 1ull) != 0;
-              if (tid + j * TB == r) {
-                used_r[j] = true;
-                um[j] = 0u;
-#pragma unroll
-                for (int q2 = q; q2 < WR; ++q2) pbuf[q2] = row[j][q2];
-                pbuf[WR] = sbit[j];
-                lkk[npiv] = ((q * 64 + fb) << 11) | r;
-              }
-            }
-            ++npiv;
-            __syncthreads();
-            if (QLDPC_STAMPS) st[9] += osd_stamp() - ts0;
-            bool upd[RPT], any = false;
-#pragma unroll
-            for (int j = 0; j < RPT; ++j) {
-              upd[j] = hb[j] && tid + j * TB != r;
-              any = any || upd[j];
-            }
-            if (any) {  // pivot-row words through the rolling buffer, as below
-              constexpr int XB = kOsdXB;
-              u64 buf[XB];
-#pragma unroll
-              for (int u = 0; u < XB; ++u)
-                if (q + u < WR) buf[u] = pbuf[q + u];
-              const uint32_t ps = (uint32_t)pbuf[WR];
-#pragma unroll
-              for (int q2 = q; q2 < WR; ++q2) {
-                const u64 pv = buf[(q2 - q) % XB];
-                if (q2 + XB < WR) buf[(q2 - q) % XB] = pbuf[q2 + XB];
-#pragma unroll
-                for (int j = 0; j < RPT; ++j) {
-                  u64 t = upd[j] ? pv : 0ull;
-                  row[j][q2] ^= t;
-                  if (QLDPC_OSD_XOR3) {  // diagnostic: the same xor twice more (same result, 3x the work)
-                    asm volatile("" : "+v"(t));
-                    row[j][q2] ^= t;
-                    asm volatile("" : "+v"(t));
-                    row[j][q2] ^= t;
-                  }
-                }
-              }
-#pragma unroll
-              for (int j = 0; j < RPT; ++j) sbit[j] ^= upd[j] ? ps : 0u;
-            }
-            b = fb + 1;
-            if (b >= bend || npiv >= rank) break;  // uniform
-          }
-        }
-        // the pivot list -> pivrow / pivpos (every lkk write precedes one of the loop's barriers)
-        for (int i = tid; i < npiv; i += TB) {
-          const int v = lkk[i];
-          pivrow[i] = v & 2047;
-          pivpos[i] = v >> 11;
-        }
-      } else {
-      int step3 = 0;  // search step mod 3: s_piv slot of the step (triple-buffered as above)
-      int spar = 0;   // search step mod 2
+      // Per-pivot loop.  Positions without a candidate row change nothing, so one search step finds
+      // the next pivot of this word directly: the lexicographic minimum of (first set bit >= b, row)
+      // over the unused rows = the first position with a candidate and its lowest row, as the
+      // position-by-position greedy scan picks it (ldpc's pivot set), without a barrier per
+      // dependent position.  A pivot step is bound by every wave's own instruction stream (all
+      // waves meet at its two barriers; profiles/r04/passo/), so the step's winner is the maximum
+      // of (step << 17) | (0x1FFFF - key) over one ds_max per wave: a stale value from an earlier
+      // step never matches the step, so the slot needs no re-arming.  Pivots go to an LDS list
+      // over the (dead) sort keys: (position << 11) | row.
+      int32_t* lkk = reinterpret_cast<int32_t*>(smem);
+      const uint32_t pivx_a = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t*)(&s_pivx);
+      uint32_t step = 0;  // uniform
+      uint32_t um = tid < m ? ~0u : 0u;  // ~0 while row tid is a candidate (unused, < m), else 0
 #pragma unroll
       for (int q = 0; q < WR; ++q) {
         if (q * 64 >= n || npiv >= rank) break;  // uniform
         const int bend = n - q * 64 < 64 ? n - q * 64 : 64;
-        // Positions without a candidate row change nothing, so one search step finds the next
-        // pivot of this word directly: the lexicographic minimum of (first set bit >= b, row)
-        // over the unused rows = the first position with a candidate and its lowest row, as the
-        // position-by-position greedy scan picks it (ldpc's pivot set), without a barrier per
-        // dependent position.
         const u64 wmask = bend < 64 ? (1ull << bend) - 1ull : ~0ull;
         int b = 0;
-        while (b < bend && npiv < rank) {  // uniform
-          const int slot = step3;
-          step3 = step3 == 2 ? 0 : step3 + 1;
-          const int par = spar;  // QLDPC_OSD_1B: slot half of this step (alternates every step)
-          spar ^= 1;
-          (void)par;
+        for (;;) {  // uniform
+          ++step;
+          asm volatile("" : "+s"(step));  // opaque: no strength-reduced copies of step << 17 per word
           unsigned long long ts0 = 0;
           if (QLDPC_STAMPS) {
             ts0 = osd_stamp();
             st[7] += 1;
           }
           const u64 lowm = (~0ull << b) & wmask;
-          uint32_t key = 0x7FFFFFFFu;  // (first set bit << 11) | row
-#pragma unroll
-          for (int j = 0; j < RPT; ++j) {
-            const u64 mm = used_r[j] ? 0ull : (row[j][q] & lowm);
-            const uint32_t kj = mm ? ((uint32_t)(__ffsll((long long)mm) - 1) << 11) | (uint32_t)(tid + j * TB) : 0x7FFFFFFFu;
-            key = kj < key ? kj : key;
-          }
-          key = wave_min_u32(key);
-#if QLDPC_OSD_1B
-          // one barrier per pivot: the wave's winning row goes to the wave's slot of this step's
-          // parity before the barrier (rewritten two steps later, behind the next barrier)
-          u64* wsl = pbuf + (size_t)((par * (LB / 64) + (tid >> 6)) * (WR + 1));
-          (void)wsl;
-#endif
-          if (QLDPC_OSD_1B && key != 0x7FFFFFFFu) {
-#pragma unroll
-            for (int j = 0; j < RPT; ++j)
-              if ((uint32_t)(tid + j * TB) == (key & 2047u)) {
-#if QLDPC_OSD_1B
-#pragma unroll
-                for (int q2 = q; q2 < WR; ++q2) wsl[q2] = row[j][q2];
-                wsl[WR] = sbit[j];
-#endif
-              }
-          }
-          if ((tid & 63) == 0 && key != 0x7FFFFFFFu) atomicMin(&s_piv[slot], (int)key);
+          // key = (first set bit >= b << 11) | row; a row without one gets first bit 0xFFFFFFFF
+          // (v_ffbl of 0), i.e. a key >= 0xFFFFF800, above every real key (<= 0x1FFFF)
+          const uint32_t ml = (uint32_t)row[q] & (uint32_t)lowm & um;
+          const uint32_t mh = (uint32_t)(row[q] >> 32) & (uint32_t)(lowm >> 32) & um;
+          const uint32_t fl = ffbl_u32(ml), fh = ffbl_u32(mh) | 32u;
+          uint32_t key = ((fl < fh ? fl : fh) << 11) | (uint32_t)tid;
+          key = wave_min_u32_bc(key);
+          if ((tid & 63) == 0 && key <= 0x1FFFFu) lds_max_u32_sync(pivx_a, (step << 17) | (0x1FFFFu - key));
           __syncthreads();
           if (QLDPC_STAMPS) {
             const unsigned long long t = osd_stamp();
             st[8] += t - ts0;
             ts0 = t;
           }
-          const int kk = s_piv[slot];
-          if (tid == 0) s_piv[step3 == 2 ? 0 : step3 + 1] = 0x7FFFFFFF;  // re-arm the slot two steps ahead
-          if (kk == 0x7FFFFFFF) break;  // no pivot left in this word (uniform)
-          const int fb = kk >> 11, r = kk & 2047;
-          const int p = q * 64 + fb;
-          bool hb[RPT];
+          const uint32_t vx = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_pivx);  // uniform
+          if ((vx >> 17) != step) break;  // no pivot left in this word (uniform)
+          const uint32_t kk = 0x1FFFFu - (vx & 0x1FFFFu);
+          const int fb = (int)(kk >> 11), r = (int)(kk & 2047u);
+          const bool hb = ((row[q] >> fb) & 1ull) != 0;
+          if (tid == r) {
+            um = 0u;
 #pragma unroll
-          for (int j = 0; j < RPT; ++j) {
-            hb[j] = ((row[j][q] >> fb) & 1ull) != 0;
-            if (tid + j * TB == r) {
-              used_r[j] = true;
-              if (!QLDPC_OSD_1B) {
-#pragma unroll
-                for (int q2 = q; q2 < WR; ++q2) pbuf[q2] = row[j][q2];
-                pbuf[WR] = sbit[j];
-              }
-              pivrow[npiv] = r;
-              pivpos[npiv] = p;
-            }
+            for (int q2 = q; q2 < WR; ++q2) pbuf[q2] = row[q2];
+            pbuf[WR] = sbit;
+            lkk[npiv] = (int)(((uint32_t)q << 17) | kk);  // ((q * 64 + fb) << 11) | r, from the uniform key
           }
           ++npiv;
-#if QLDPC_OSD_1B
-          const u64* prow = pbuf + (size_t)(par * (LB / 64) + (r >> 6)) * (WR + 1);
-#else
           __syncthreads();
-          const u64* prow = pbuf;
-#endif
           if (QLDPC_STAMPS) st[9] += osd_stamp() - ts0;
-          bool upd[RPT], any = false;
-#pragma unroll
-          for (int j = 0; j < RPT; ++j) {
-            upd[j] = hb[j] && tid + j * TB != r;
-            any = any || upd[j];
-          }
-          if (any) {  // one broadcast read of each pivot word serves all of the thread's rows
+          if (hb && tid != r) {
             // pivot-row words read kOsdXB ahead of their xors (a rolling buffer): written as
             // read-xor pairs, the compiler chained them with a wait after each read (13 LDS round
             // trips per pivot on the 25-word rows, round 4 asm review)
@@ -1754,115 +649,50 @@ osd_gpu_kernel(OsdGpuArgs A) {
             u64 buf[XB];
 #pragma unroll
             for (int u = 0; u < XB; ++u)
-              if (q + u < WR) buf[u] = prow[q + u];
-            const uint32_t ps = (uint32_t)prow[WR];
+              if (q + u < WR) buf[u] = pbuf[q + u];
+            const uint32_t ps = (uint32_t)pbuf[WR];
 #pragma unroll
             for (int q2 = q; q2 < WR; ++q2) {
               const u64 pv = buf[(q2 - q) % XB];
-              if (q2 + XB < WR) buf[(q2 - q) % XB] = prow[q2 + XB];
-#pragma unroll
-              for (int j = 0; j < RPT; ++j) row[j][q2] ^= upd[j] ? pv : 0ull;
+              if (q2 + XB < WR) buf[(q2 - q) % XB] = pbuf[q2 + XB];
+              row[q2] ^= pv;
             }
-#pragma unroll
-            for (int j = 0; j < RPT; ++j) sbit[j] ^= upd[j] ? ps : 0u;
+            sbit ^= ps;
           }
           b = fb + 1;
+          if (b >= bend || npiv >= rank) break;  // uniform
         }
       }
-      }  // per-pivot elimination
-      if ((A.win == 1 || A.win == 3) && (npiv < rank || (A.win == 3 && (b & 1)))) {
-        // the pivots run past the column window (uniform): redo at full width
+      // the pivot list -> pivrow / pivpos (every lkk write precedes one of the loop's barriers)
+      for (int i = tid; i < npiv; i += TB) {
+        const int v = lkk[i];
+        pivrow[i] = v & 2047;
+        pivpos[i] = v >> 11;
+      }
+      // The one remnant of the removed column-window launch (A.win is always 0, so this never
+      // runs): without this uniform early-out behind the pivot loop the compiler places SGPR spill
+      // reloads inside the loop (+4 to +8 instructions per pivot step), measured 0.9 % (n1600) and
+      // 2 % (n225) slower in the BP+OSD shot loop.
+      if (A.win == 1 && npiv < rank) {
         if (tid == 0) ow[0] = kOsdRedo;
         __syncthreads();
         continue;
       }
-      // Steps 4-5 from the registers (osd_e / osd_0, round 5): the reduced rows never leave them.
-      // The swap trace runs on one wave with the staged pivot positions read 64 at a time (one LDS
-      // round trip per 64 transpositions instead of one per transposition), the needed non-pivot
-      // positions Ht[j] go to LDS, and every pivot row writes its bits of S0 / x(h_j) as bytes at
-      // its pivot index (no atomics: one writer per index), packed by one ballot per word; the
-      // reduced-row write-out to the HBM slice and step 5's two dependent global reads per bit are
-      // gone.  MEASURED AND NOT KEPT (A/B build QLDPC_OSD_XREG=1): bit-exact (96 BP+OSD / circuit
-      // GPU tests), but the n1600 OSD total is unchanged (1.672 M vs 1.675 M cycles per syndrome,
-      // BP+OSD 605 k vs 614 k shots/s, profiles/r05/osd_notkept/xreg_*): the steps' time is not the
-      // HBM round trips this removes.
-      const int rW = (npiv + 63) / 64;
-      if (QLDPC_OSD_XREG && PNL != 5 && nh <= 31 && (size_t)4 * (m + 32) + (size_t)(1 + nh) * npiv <= (size_t)NP * 8) {  // uniform
-        if (tid == 0) s_npiv = npiv;
-        int32_t* rowpiv = reinterpret_cast<int32_t*>(smem);  // [m] pivot index of each row, -1 (over the dead keys)
-        int32_t* swl = rowpiv + m;                          // [32] Ht positions
-        uint8_t* xb = reinterpret_cast<uint8_t*>(swl + 32);  // [1 + nh][npiv] bits of S0 / x(h_j) by pivot index
-        int32_t* lpp = reinterpret_cast<int32_t*>(smem + A.pbuf_off + (size_t)(osd_prows(LB) + (PNL == 4 ? 1 : 0)) * (WR + 1) * 8);
-        __syncthreads();  // pivrow / pivpos written, the (dead) pivot list read
-        for (int i = tid; i < npiv; i += TB) lpp[i] = pivpos[i];
-        for (int i = tid; i < m; i += TB) rowpiv[i] = -1;
-        __syncthreads();
-        for (int i = tid; i < npiv; i += TB) rowpiv[pivrow[i]] = i;
-        if (tid < 64) {  // wave 0: lane j traces position npiv + j back through the transpositions
-          int cur = npiv + tid;
-          for (int c0 = ((npiv - 1) >> 6) << 6; c0 >= 0; c0 -= 64) {  // uniform
-            const int il = c0 + tid;
-            const int v = il < npiv ? lpp[il] : 0;
-            const int top = npiv - 1 - c0 < 63 ? npiv - 1 - c0 : 63;
-            for (int t = top; t >= 0; --t) {  // uniform
-              const int pi = __builtin_amdgcn_readlane(v, t);
-              const int i = c0 + t;
-              cur = cur == i ? pi : (cur == pi ? i : cur);
-            }
-          }
-          if (tid < nh && npiv + tid < n) {
-            swp[npiv + tid] = cur;
-            swl[tid] = cur;
-          }
-        }
-        __syncthreads();
+      // reduced rows -> the HBM slice (word-major), syndrome bits -> sb
+      if (tid < m) {
+        // opaque row pointer: the compiler otherwise hoists the WR word addresses out of the
+        // syndrome loop, 2 * WR VGPRs live through the whole elimination (round 4 asm review)
+        u64* mrow = Mg + tid;
+        asm volatile("" : "+v"(mrow));
 #pragma unroll
-        for (int j = 0; j < RPT; ++j) {
-          const int i = tid + j * TB;
-          const int k = i < m ? rowpiv[i] : -1;
-          if (k >= 0) {
-            xb[k] = (uint8_t)(sbit[j] & 1u);
-            for (int jj = 0; jj < nh; ++jj) {  // uniform
-              const int hp = swl[jj];
-              const int hq = hp >> 6;
-              u64 wsel = 0;
-              osd_for_words(std::make_integer_sequence<int, WR>{}, [&](auto Qc) __attribute__((always_inline)) {
-                constexpr int Q = decltype(Qc)::value;
-                if (Q == hq) wsel = row[j][Q];
-                return true;
-              });
-              xb[(size_t)(1 + jj) * npiv + k] = (uint8_t)((wsel >> (hp & 63)) & 1ull);
-            }
-          }
-        }
-        __syncthreads();
-        for (int t = tid >> 6; t < (1 + nh) * rW; t += TB >> 6) {  // uniform per wave: one ballot per word
-          const int jj = t / rW, q = t % rW, i = q * 64 + (tid & 63);
-          const unsigned long long v = __ballot(i < npiv && xb[(size_t)jj * npiv + i] != 0);
-          if ((tid & 63) == 0) X[(size_t)jj * RW + q] = v;
-        }
-        xdone = true;
+        for (int q = 0; q < WR; ++q)
+          if (q < W) mrow[(size_t)q * m] = row[q];
       }
-      // reduced rows -> the HBM slice (word-major), syndrome bits -> sb (forward elimination: the
-      // pivot rows are there already, in pivot order)
-#pragma unroll
-      for (int j = 0; j < RPT && PNL != 5 && !xdone; ++j) {
-        const int i = tid + j * TB;
-        if (i < m) {
-          // opaque row pointer: the compiler otherwise hoists the WR word addresses out of the
-          // syndrome loop, 2 * WR VGPRs live through the whole elimination (round 4 asm review)
-          u64* mrow = Mg + i;
-          asm volatile("" : "+v"(mrow));
-#pragma unroll
-          for (int q = 0; q < WR; ++q)
-            if (q < W) mrow[(size_t)q * m] = row[j][q];
-        }
-        const unsigned long long sbal = __ballot(i < m && sbit[j]);
-        if ((tid & 63) == 0) {
-          const int w0 = ((tid & ~63) + j * TB) >> 5;
-          if (w0 < (m + 31) / 32) sb[w0] = (uint32_t)sbal;
-          if (w0 + 1 < (m + 31) / 32) sb[w0 + 1] = (uint32_t)(sbal >> 32);
-        }
+      const unsigned long long sbal = __ballot(tid < m && sbit);
+      if ((tid & 63) == 0) {
+        const int w0 = tid >> 5;
+        if (w0 < (m + 31) / 32) sb[w0] = (uint32_t)sbal;
+        if (w0 + 1 < (m + 31) / 32) sb[w0 + 1] = (uint32_t)(sbal >> 32);
       }
       if (tid == 0) s_npiv = npiv;
       __syncthreads();
@@ -1973,14 +803,13 @@ osd_gpu_kernel(OsdGpuArgs A) {
     const int r = s_npiv;
     OSD_ST(2)
     const int RWr = (r + 63) / 64;
-    if (!xdone) {  // (register rows, osd_e / osd_0: done from the registers above)
     // 4. Neal's column swaps -> non-pivot order Ht.  Only the non-pivot positions swp[r + j],
     // j < nh, are used: each is the identity traced backwards through the transpositions
     // (i, pivpos[i]), i = r-1 .. 0 -- one thread per needed position, no serial replay.
     // (Register-row mode stages pivpos in LDS first: the trace reads it r times.)
     const int32_t* pp = pivpos;
     if constexpr (kRR) {
-      int32_t* lpp = reinterpret_cast<int32_t*>(smem + A.pbuf_off + (size_t)(osd_prows(LB) + (PNL == 4 ? 1 : 0)) * (WR + 1) * 8);
+      int32_t* lpp = reinterpret_cast<int32_t*>(smem + A.pbuf_off + (size_t)(WR + 1) * 8);  // after the pivot-row buffer
       for (int i = tid; i < r; i += TB) lpp[i] = pivpos[i];
       __syncthreads();
       pp = lpp;
@@ -1996,73 +825,6 @@ osd_gpu_kernel(OsdGpuArgs A) {
     __syncthreads();
     // 5. S0 and x(h_j) as bit-vectors over the pivot index: one wave per 64-bit word, lane c
     // forms bit c (pivot q*64 + c) and a ballot packs the word
-    if constexpr (kRR && PNL == 5) {
-      // 5'. (forward elimination) the Jordan half on the right-hand sides: thread k holds pivot row
-      // k (final since it was chosen, HBM slice row k) and b_k = (syndrome bit, bits Ht[j] of the
-      // row) as bits 0, 1 + j; U_kj = bit p_j of row k for pivots j > k (upper unitriangular in
-      // pivot order, the pivots being found in ascending position; its words were taken during
-      // the elimination).  Back substitution U x = b by blocks of 64 pivots from the last: the
-      // block's wave solves it lane by lane (readlane of the finished lane's x, xor into the lanes
-      // whose U bit names it), publishes x as 1 + nh ballot words, and every earlier row takes
-      // parity(U_k,block & x) per right-hand side.
-      const int32_t* lk = reinterpret_cast<const int32_t*>(smem);
-      const u64* Ul = reinterpret_cast<const u64*>(smem + A.pnl_off + osd_fwd_stg_bytes(WR));
-      u64* xv = const_cast<u64*>(Ul) + osd_ul_words(RW);      // [1 + nh][RWr] x as bit-vectors
-      uint32_t bk = 0;
-      {
-        u64 rw[WR];
-        const u64* mrow = Mg + tid;
-        asm volatile("" : "+v"(mrow));
-#pragma unroll
-        for (int Q = 0; Q < WR; ++Q) rw[Q] = (tid < r && Q < W) ? mrow[(size_t)Q * m] : 0ull;
-        if (tid < r) bk = ((uint32_t)lk[tid] >> 24) & 1u;
-        for (int j = 0; j < nh; ++j) {  // uniform
-          const int hp = swp[r + j];
-          const int hq = hp >> 6;
-          u64 wsel = 0;
-          osd_for_words(std::make_integer_sequence<int, WR>{}, [&](auto Qc) __attribute__((always_inline)) {
-            constexpr int Q = decltype(Qc)::value;
-            if (Q == hq) wsel = rw[Q];
-            return true;
-          });
-          bk |= (uint32_t)((wsel >> (hp & 63)) & 1ull) << (1 + j);
-        }
-      }
-      unsigned long long tj0 = QLDPC_STAMPS ? osd_stamp() : 0ull;
-      const int B0 = __builtin_amdgcn_readfirstlane(tid >> 6);  // this wave's pivot block (uniform)
-      for (int B = RWr - 1; B >= 0; --B) {  // uniform
-        if (B0 == B) {
-          // U bits name later pivots only (bit t of lane l: t > l), lanes past r hold zeros
-          const u64 uo = tid < r ? Ul[osd_ul_at(tid, B, RW)] : 0ull;
-          const uint32_t ulo = (uint32_t)uo, uhi = (uint32_t)(uo >> 32);
-#pragma unroll
-          for (int t = 63; t > 0; --t) {  // lane t is final: x_t (constant lanes, no hazards)
-            const uint32_t x = (uint32_t)__builtin_amdgcn_readlane((int)bk, t);
-            const uint32_t bit = ((t < 32 ? ulo : uhi) >> (t & 31)) & 1u;
-            bk ^= x & (0u - bit);
-          }
-#pragma unroll
-          for (int j = 0; j < 32; ++j) {
-            if (j > nh) break;  // uniform
-            const unsigned long long bal = __ballot(tid < r && ((bk >> j) & 1u));
-            if ((tid & 63) == 0) xv[(size_t)j * RWr + B] = bal;
-          }
-        }
-        __syncthreads();
-        if (B0 < B) {  // uniform per wave; lanes past r: uB = 0
-          const u64 uB = tid < r ? Ul[osd_ul_at(tid, B, RW)] : 0ull;
-          uint32_t acc = 0;
-#pragma unroll
-          for (int j = 0; j < 32; ++j) {
-            if (j > nh) break;  // uniform
-            acc |= (uint32_t)(__popcll(uB & xv[(size_t)j * RWr + B]) & 1) << j;
-          }
-          bk ^= acc;
-        }
-      }
-      if (QLDPC_STAMPS) st[13] += osd_stamp() - tj0;
-      for (int t = tid; t < (1 + nh) * RWr; t += TB) X[(size_t)(t / RWr) * RW + t % RWr] = xv[t];
-    } else
     for (int t = tid >> 6; t < (1 + nh) * RWr; t += TB >> 6) {  // uniform per wave
       const int j = t / RWr, q = t % RWr;
       const int c = tid & 63, i = q * 64 + c;
@@ -2079,7 +841,6 @@ osd_gpu_kernel(OsdGpuArgs A) {
       const unsigned long long v = __ballot(bitv);
       if (c == 0) X[(size_t)j * RW + q] = v;
     }
-    }  // !xdone
     if (tid == 0) s_best = ~0ull;
     __syncthreads();
     OSD_ST(3)
@@ -2254,375 +1015,6 @@ osd_gpu_kernel(OsdGpuArgs A) {
     for (int k2 = 0; k2 < 16; ++k2) atomicAdd(&g_osd_stamps[k2], st[k2]);
 }
 
-#if QLDPC_EXPERIMENTAL
-
-// Two syndromes per workgroup (register-row mode, 768 threads, m <= 768; round 4, VERDICT r03 item
-// 5).  The Gauss-Jordan of one syndrome is a chain of ~780 dependent steps (wave minimum, LDS
-// atomic, barrier, pivot-row publication, barrier, row update) that leaves the CU mostly idle, and
-// an OSD workgroup cannot share its CU with another (768 x 163 VGPRs).  Here every thread holds
-// row tid of BOTH syndromes' permuted H (2 x WR words) and each step searches, publishes and
-// updates both, so one chain of barriers serves two eliminations.  Per syndrome: its own LDS area
-// (sort tables, bit-vectors, pivot-row buffer, staged pivots) at s * A.syn_lds, its own HBM slice
-// (blockIdx.x * 2 + s), the same sort / swap trace / candidates / outputs as osd_gpu_kernel, one
-// syndrome after the other.  A syndrome that finishes its word (no pivot left, or rank reached)
-// idles through the other's remaining steps of that word.  Outputs identical to osd_gpu_kernel.
-// MEASURED AND NOT KEPT (experimental builds only): bit-exact (52 BP+OSD / phenl / circuit GPU
-// tests), but 2 x 25 row words left too few of the 168 VGPRs (105 spilled): n1600 BP+OSD 539 k
-// vs 548 k shots/s with one syndrome per workgroup (profiles/r04/passf/).  Most of the pressure
-// was hoisted write-out addresses; with those opaque (1 dword spilled, 57 GPU tests green) it is
-// 537.5 k vs 539 k on one box (profiles/r04/passo/): two eliminations per chain of barriers cost
-// what two chains cost, i.e. a pivot step is bound by its VALU issue (~3 waves per SIMD x ~90
-// VALU x 4 cycles), not by the barrier latency.
-template <int WR>
-__global__ void __launch_bounds__(768) osd_rr2_kernel(OsdGpuArgs A) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int tid = threadIdx.x, TB = blockDim.x;
-  const int m = A.m, n = A.n, W = A.W, RW = A.RW, NP = A.NP, rank = A.rank;
-  const int k = n - rank;
-  const int w = A.order < k ? A.order : k;
-  const int nh = A.method == 2 ? k : w;
-  __shared__ int s_piv[2][3], s_npiv[2];
-  __shared__ u64 s_best[2];
-  constexpr int XB = kOsdXB;
-  for (long long b0 = (long long)blockIdx.x * 2; b0 < A.B; b0 += 2ll * gridDim.x) {
-    bool act[2];
-    u64 row[2][WR];
-    uint32_t sbit[2];
-    bool used_r[2];
-    // (per-syndrome phases as lambdas on a compile-time s: the row registers are never indexed by
-    // a runtime value, which would put them in scratch)
-    auto prologue = [&](auto sc) __attribute__((always_inline)) {
-      constexpr int s = decltype(sc)::value;
-      const long long b = b0 + s;
-      act[s] = false;
-#pragma unroll
-      for (int q = 0; q < WR; ++q) row[s][q] = 0;
-      sbit[s] = 0;
-      used_r[s] = true;
-      if (b >= A.B || (A.shot && A.shot[b] < 0)) return;
-      uint8_t* ow = A.outw + b * (long long)n;
-      uint8_t* o0 = A.out0 ? A.out0 + b * (long long)n : nullptr;
-      if (A.conv && A.conv[b]) {  // BP converged: bposd_decoder returns the BP decoding
-        for (int j = tid; j < n; j += TB) {
-          const uint8_t v = A.bp_corr[b * (long long)n + j];
-          ow[j] = v;
-          if (o0) o0[j] = v;
-        }
-        return;
-      }
-      act[s] = true;
-      unsigned char* L = smem + (size_t)s * A.syn_lds;
-      u64* skey = reinterpret_cast<u64*>(L);
-      int32_t* sidx = reinterpret_cast<int32_t*>(skey + NP);
-      int32_t* pos = sidx + NP;
-      uint32_t* used = reinterpret_cast<uint32_t*>(L + A.bits_off);
-      uint32_t* sb = used + (m + 31) / 32;
-      const double* post = A.post + b * (long long)n;
-      const uint8_t* synd = A.synd + b * (long long)m;
-      // 1. stable ascending sort of the columns by posterior (bitonic on (key, index))
-      for (int q = tid; q < NP; q += TB) {
-        skey[q] = q < n ? ord_key(post[q]) : ~0ull;
-        sidx[q] = q < n ? q : 0x7FFFFFFF;
-      }
-      __syncthreads();
-      for (int size = 2; size <= NP; size <<= 1)
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-          for (int q = tid; q < NP / 2; q += TB) {
-            const int lo = 2 * q - (q & (stride - 1));
-            const int hi = lo + stride;
-            const bool up = (lo & size) == 0;
-            const u64 ka = skey[lo], kb = skey[hi];
-            const int ia = sidx[lo], ib = sidx[hi];
-            const bool gt = ka > kb || (ka == kb && ia > ib);
-            if (gt == up) {
-              skey[lo] = kb; skey[hi] = ka;
-              sidx[lo] = ib; sidx[hi] = ia;
-            }
-          }
-          __syncthreads();
-        }
-      for (int q = tid; q < n; q += TB) pos[sidx[q]] = q;
-      for (int q = tid; q < (m + 31) / 32; q += TB) {
-        used[q] = 0;
-        uint32_t v = 0;
-        for (int t = 0; t < 32 && q * 32 + t < m; ++t) v |= (uint32_t)(synd[q * 32 + t] & 1u) << t;
-        sb[q] = v;
-      }
-      if (tid == 0) {
-        s_npiv[s] = 0;
-        s_piv[s][0] = s_piv[s][1] = s_piv[s][2] = 0x7FFFFFFF;
-      }
-      __syncthreads();
-      // 2. row tid of the permuted H
-      const int i = tid;
-      used_r[s] = i >= m;
-      if (i < m) {
-        for (int e = A.rp[i]; e < A.rp[i + 1]; ++e) {
-          const int p = pos[A.ci[e]];
-          const int pq = p >> 6;
-          const u64 bit = 1ull << (p & 63);
-#pragma unroll
-          for (int q = 0; q < WR; ++q) row[s][q] ^= (pq == q) ? bit : 0ull;
-        }
-        sbit[s] = synd[i] & 1u;
-      }
-    };
-    prologue(std::integral_constant<int, 0>{});
-    prologue(std::integral_constant<int, 1>{});
-    if (!act[0] && !act[1]) continue;  // uniform
-    __syncthreads();
-    // 3. joint Gauss-Jordan over positions in order (per syndrome as osd_gpu_kernel's search skip)
-    int npiv[2] = {0, 0};
-    int step3 = 0;
-    // one word q per call, q compile-time (the unroller gives up on this loop nest: the row
-    // registers would then be indexed at run time and live in scratch); false = stop
-    auto word = [&](auto qc) __attribute__((always_inline)) -> bool {
-      constexpr int q = decltype(qc)::value;
-      if (q * 64 >= n) return false;  // uniform
-      bool dn[2];
-#pragma unroll
-      for (int s = 0; s < 2; ++s) dn[s] = !act[s] || npiv[s] >= rank;
-      if (dn[0] && dn[1]) return false;  // uniform
-      const int bend = n - q * 64 < 64 ? n - q * 64 : 64;
-      const u64 wmask = bend < 64 ? (1ull << bend) - 1ull : ~0ull;
-      int bs[2] = {0, 0};
-      while (true) {  // uniform
-        const int slot = step3;
-        step3 = step3 == 2 ? 0 : step3 + 1;
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-          if (dn[s]) continue;  // uniform
-          const u64 lowm = (~0ull << bs[s]) & wmask;
-          const u64 mm = used_r[s] ? 0ull : (row[s][q] & lowm);
-          uint32_t key = mm ? ((uint32_t)(__ffsll((long long)mm) - 1) << 11) | (uint32_t)tid : 0x7FFFFFFFu;
-          key = wave_min_u32(key);
-          if ((tid & 63) == 0 && key != 0x7FFFFFFFu) atomicMin(&s_piv[s][slot], (int)key);
-        }
-        __syncthreads();
-        int kk[2];
-#pragma unroll
-        for (int s = 0; s < 2; ++s) kk[s] = s_piv[s][slot];
-        if (tid == 0) {
-          const int nx = step3 == 2 ? 0 : step3 + 1;  // re-arm the slot two steps ahead
-          s_piv[0][nx] = 0x7FFFFFFF;
-          s_piv[1][nx] = 0x7FFFFFFF;
-        }
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-          if (kk[s] == 0x7FFFFFFF) dn[s] = true;  // no pivot left in this word (uniform)
-        if (dn[0] && dn[1]) break;
-        bool hb[2];
-        int rr[2], fbs[2];
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-          hb[s] = false;
-          rr[s] = -1;
-          fbs[s] = 0;
-          if (dn[s]) continue;
-          const int fb = kk[s] >> 11, r = kk[s] & 2047;
-          fbs[s] = fb;
-          rr[s] = r;
-          hb[s] = ((row[s][q] >> fb) & 1ull) != 0;
-          if (tid == r) {
-            used_r[s] = true;
-            u64* pbuf = reinterpret_cast<u64*>(smem + (size_t)s * A.syn_lds + A.pbuf_off);
-#pragma unroll
-            for (int q2 = q; q2 < WR; ++q2) pbuf[q2] = row[s][q2];
-            pbuf[WR] = sbit[s];
-            int32_t* pivrow = A.iws + ((size_t)blockIdx.x * 2 + s) * A.iws_ints;
-            pivrow[npiv[s]] = r;
-            pivrow[rank + npiv[s]] = q * 64 + fb;  // pivpos
-          }
-          ++npiv[s];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-          if (dn[s]) continue;
-          if (hb[s] && tid != rr[s]) {  // the pivot row's words q.., read XB ahead of their xors
-            const u64* prow = reinterpret_cast<const u64*>(smem + (size_t)s * A.syn_lds + A.pbuf_off);
-            u64 buf[XB];
-#pragma unroll
-            for (int u = 0; u < XB; ++u)
-              if (q + u < WR) buf[u] = prow[q + u];
-            const uint32_t ps = (uint32_t)prow[WR];
-#pragma unroll
-            for (int q2 = q; q2 < WR; ++q2) {
-              const u64 pv = buf[(q2 - q) % XB];
-              if (q2 + XB < WR) buf[(q2 - q) % XB] = prow[q2 + XB];
-              row[s][q2] ^= pv;
-            }
-            sbit[s] ^= ps;
-          }
-          bs[s] = fbs[s] + 1;
-          if (bs[s] >= bend || npiv[s] >= rank) dn[s] = true;
-        }
-        if (dn[0] && dn[1]) break;
-      }
-      return true;
-    };
-    osd_for_words(std::make_integer_sequence<int, WR>{}, word);
-    // 4-7 per syndrome: reduced rows -> HBM slice, swaps, bit-vectors, candidates, outputs
-    auto finish = [&](auto sc) __attribute__((always_inline)) {
-      constexpr int s = decltype(sc)::value;
-      if (!act[s]) return;  // uniform
-      const long long b = b0 + s;
-      unsigned char* L = smem + (size_t)s * A.syn_lds;
-      const int32_t* sidx = reinterpret_cast<const int32_t*>(reinterpret_cast<u64*>(L) + NP);
-      uint32_t* used = reinterpret_cast<uint32_t*>(L + A.bits_off);
-      uint32_t* sb = used + (m + 31) / 32;
-      int32_t* lpp = reinterpret_cast<int32_t*>(L + A.pbuf_off + (WR + 1) * 8);
-      u64* Mg = A.ws + ((size_t)blockIdx.x * 2 + s) * A.ws_words;
-      u64* X = Mg + (size_t)W * m;
-      int32_t* pivrow = A.iws + ((size_t)blockIdx.x * 2 + s) * A.iws_ints;
-      int32_t* pivpos = pivrow + rank;
-      int32_t* swp = pivpos + rank;
-      uint8_t* ow = A.outw + b * (long long)n;
-      uint8_t* o0 = A.out0 ? A.out0 + b * (long long)n : nullptr;
-      {
-        const int i = tid;
-        if (i < m) {
-          // opaque row pointer: the compiler otherwise hoists the WR word addresses out of the
-          // syndrome loop (2 * WR VGPRs live through the elimination: 105 VGPRs spilled -> 1 dword)
-          u64* mrow = Mg + i;
-          asm volatile("" : "+v"(mrow));
-#pragma unroll
-          for (int q = 0; q < WR; ++q)
-            if (q < W) mrow[(size_t)q * m] = row[s][q];
-        }
-        const unsigned long long sbal = __ballot(i < m && sbit[s]);
-        if ((tid & 63) == 0) {
-          const int w0 = (tid & ~63) >> 5;
-          if (w0 < (m + 31) / 32) sb[w0] = (uint32_t)sbal;
-          if (w0 + 1 < (m + 31) / 32) sb[w0 + 1] = (uint32_t)(sbal >> 32);
-        }
-      }
-      __syncthreads();  // pivrow / pivpos (global, written by the pivot owners) and sb visible
-      const int r = npiv[s];
-      for (int i = tid; i < r; i += TB) lpp[i] = pivpos[i];
-      __syncthreads();
-      for (int x = r + tid; x < r + nh && x < n; x += TB) {
-        int cur = x;
-        for (int i = r - 1; i >= 0; --i) {
-          const int pi = lpp[i];
-          cur = cur == i ? pi : (cur == pi ? i : cur);
-        }
-        swp[x] = cur;
-      }
-      __syncthreads();
-      const int RWr = (r + 63) / 64;
-      for (int t = tid >> 6; t < (1 + nh) * RWr; t += TB >> 6) {  // uniform per wave
-        const int j = t / RWr, q = t % RWr;
-        const int c = tid & 63, i = q * 64 + c;
-        bool bitv = false;
-        if (i < r) {
-          const int rw = pivrow[i];
-          if (j == 0) {
-            bitv = ((sb[rw >> 5] >> (rw & 31)) & 1u) != 0;
-          } else {
-            const int hp = swp[r + j - 1];
-            bitv = ((Mg[(size_t)(hp >> 6) * m + rw] >> (hp & 63)) & 1ull) != 0;
-          }
-        }
-        const unsigned long long v = __ballot(bitv);
-        if (c == 0) X[(size_t)j * RW + q] = v;
-      }
-      if (tid == 0) s_best[s] = ~0ull;
-      __syncthreads();
-      long long Lc = 1;
-      if (A.method == 1 && w > 0) Lc = 1ll << w;
-      if (A.method == 2 && w >= 0) Lc = 1 + (long long)k + (long long)w * (w - 1) / 2;
-      if (A.method == 0 || A.order == 0 || k == 0) Lc = 1;
-      u64 best = ~0ull;
-      for (long long c = tid; c < Lc; c += TB) {
-        int tj[2];
-        int nt = 0;
-        unsigned long long ebits = 0;
-        if (A.method == 1) {
-          ebits = (unsigned long long)c;
-          nt = __popcll(ebits);
-        } else if (c >= 1 && c <= k) {
-          tj[0] = (int)(c - 1);
-          nt = 1;
-        } else if (c > k) {
-          long long rem = c - 1 - k;
-          int i = 0;
-          while (rem >= w - 1 - i) {
-            rem -= w - 1 - i;
-            ++i;
-          }
-          tj[0] = i;
-          tj[1] = i + 1 + (int)rem;
-          nt = 2;
-        }
-        long long cnt = nt;
-        for (int q = 0; q < RWr; ++q) {
-          u64 v = X[q];
-          if (A.method == 1) {
-            for (unsigned long long e = ebits; e; e &= e - 1) v ^= X[(size_t)(1 + __ffsll((long long)e) - 1) * RW + q];
-          } else {
-            for (int a = 0; a < nt; ++a) v ^= X[(size_t)(1 + tj[a]) * RW + q];
-          }
-          cnt += __popcll(v);
-        }
-        const u64 key = ((u64)cnt << 40) | (u64)c;
-        if (key < best) best = key;
-      }
-      if (best != ~0ull) atomicMin(&s_best[s], best);
-      __syncthreads();
-      const long long cw = (long long)(s_best[s] & ((1ull << 40) - 1));
-      int tw[2];
-      int ntw = 0;
-      unsigned long long ewb = 0;
-      if (A.method == 1) {
-        ewb = (unsigned long long)cw;
-      } else if (cw >= 1 && cw <= k) {
-        tw[0] = (int)(cw - 1);
-        ntw = 1;
-      } else if (cw > k) {
-        long long rem = cw - 1 - k;
-        int i = 0;
-        while (rem >= w - 1 - i) {
-          rem -= w - 1 - i;
-          ++i;
-        }
-        tw[0] = i;
-        tw[1] = i + 1 + (int)rem;
-        ntw = 2;
-      }
-      for (int j = tid; j < n; j += TB) {
-        ow[j] = 0;
-        if (o0) o0[j] = 0;
-      }
-      __syncthreads();
-      for (int i = tid; i < r; i += TB) {
-        const int q = i >> 6, c = i & 63;
-        const u64 s0 = (X[q] >> c) & 1ull;
-        u64 v = X[q];
-        if (A.method == 1) {
-          for (unsigned long long e = ewb; e; e &= e - 1) v ^= X[(size_t)(1 + __ffsll((long long)e) - 1) * RW + q];
-        } else {
-          for (int a = 0; a < ntw; ++a) v ^= X[(size_t)(1 + tw[a]) * RW + q];
-        }
-        const int col = sidx[pivpos[i]];
-        ow[col] = (uint8_t)((v >> c) & 1ull);
-        if (o0) o0[col] = (uint8_t)s0;
-      }
-      if (tid == 0) {
-        if (A.method == 1) {
-          for (unsigned long long e = ewb; e; e &= e - 1) ow[sidx[swp[r + __ffsll((long long)e) - 1]]] = 1;
-        } else {
-          for (int a = 0; a < ntw; ++a) ow[sidx[swp[r + tw[a]]]] = 1;
-        }
-      }
-      __syncthreads();
-    };
-    finish(std::integral_constant<int, 0>{});
-    finish(std::integral_constant<int, 1>{});
-  }
-}
-
-#endif  // QLDPC_EXPERIMENTAL
 }  // namespace
 
 struct qldpc_osd_gpu {
@@ -2630,9 +1022,6 @@ struct qldpc_osd_gpu {
   int device = 0, grid = 0, W = 0, RW = 0, NP = 0, nh = 0, m_lds = 0, bits_off = 0;
   int wr = 0, pbuf_off = 0;  // register-row mode: compile-time words per row (0 = off), LDS pivot buffer
   int rr_tb = 0;             // register-row mode: threads per workgroup = m rounded up to waves
-  int pnl = 0, pnl_off = 0;  // register-row mode: panel elimination (QLDPC_OSD_PNL), its LDS area
-  int nsy = 1, syn_lds = 0;  // register-row mode: syndromes per workgroup (osd_rr2_kernel), LDS per syndrome
-  int win_wr = 0, win_grid = 0;  // column window (osd_win_kernel): row words held, workgroups
   size_t lds = 0;
   long long ws_words = 0, iws_ints = 0;
   qldpc_rt::DevBuf rp, ci, ws, iws, softw;  // softw: [n] log(1 / p_j) when the priors are not uniform
@@ -2698,93 +1087,19 @@ namespace {
 // per thread: 2 or 3 rows per thread in 384 / 256 threads (fewer waves reading each broadcast
 // pivot word) measured 16 % / 26 % slower on n1600 (the per-pivot chain is latency-bound).
 constexpr int kOsdWR[] = {2, 4, 8, 12, 16, 20, 25};
-// rows per thread: 1, or 2 for the lean loop / blocked elimination of the 20-25-word rows with
-// QLDPC_OSD_RPT=2 (384-thread workgroups, two syndromes per CU, VGPRs pinned to 3 waves per SIMD).
-// MEASURED AND NOT KEPT (opt-in): bit-exact (GPU tests), but n1600 BP+OSD 521 k vs 588 k shots/s for
-// the blocked elimination (46 VGPRs spilled) and 499 k vs 614 k for the lean loop (spills outside
-// the pivot loop only): two half-size syndromes per CU cost more than one full-size
-// (profiles/r05/osd_notkept/rpt2_*, lean_rpt2_*)
-inline int osd_rpt(int wr, int pnl) {
-#if QLDPC_EXPERIMENTAL
-  const char* e = std::getenv("QLDPC_OSD_RPT");
-  return ((pnl == 3 || pnl == 0) && wr >= 20 && e && std::atoi(e) == 2) ? 2 : 1;
-#else
-  (void)wr;
-  (void)pnl;
-  return 1;  // (two rows per thread: experimental builds only)
-#endif
-}
-inline int osd_rr_threads(int wr, int pnl = 0) { return wr <= 16 ? 1024 : 768 / osd_rpt(wr, pnl); }
+inline int osd_rr_threads(int wr) { return wr <= 16 ? 1024 : 768; }
 using OsdKern = void (*)(OsdGpuArgs);
-template <int WR, int PNL>
-OsdKern osd_rr_wide(int rpt) {
-  if constexpr ((PNL == 3 || PNL == 0) && QLDPC_EXPERIMENTAL)  // two rows per thread, 384 threads, two syndromes per CU
-    if (rpt == 2) return &osd_gpu_kernel<384, WR, 2, PNL>;
-  (void)rpt;
-  return &osd_gpu_kernel<768, WR, 1, PNL>;
-}
-template <int PNL>
-OsdKern osd_rr_kernel_t(int wr) {
+OsdKern osd_rr_kernel(int wr) {
   switch (wr) {
-    case 2: return &osd_gpu_kernel<1024, 2, 1, PNL>;
-    case 4: return &osd_gpu_kernel<1024, 4, 1, PNL>;
-    case 8: return &osd_gpu_kernel<1024, 8, 1, PNL>;
-    case 12: return &osd_gpu_kernel<1024, 12, 1, PNL>;
-    case 16: return &osd_gpu_kernel<1024, 16, 1, PNL>;
-    case 20: return osd_rr_wide<20, PNL>(osd_rpt(wr, PNL));
-    case 25: return osd_rr_wide<25, PNL>(osd_rpt(wr, PNL));
+    case 2: return &osd_gpu_kernel<1024, 2>;
+    case 4: return &osd_gpu_kernel<1024, 4>;
+    case 8: return &osd_gpu_kernel<1024, 8>;
+    case 12: return &osd_gpu_kernel<1024, 12>;
+    case 16: return &osd_gpu_kernel<1024, 16>;
+    case 20: return &osd_gpu_kernel<768, 20>;
+    case 25: return &osd_gpu_kernel<768, 25>;
     default: return nullptr;
   }
-}
-// (the panel / blocked / lagged / forward-elimination modes PNL 1-5 were measured and not kept
-// (DESIGN.md §4): compiled into experimental builds only, -DQLDPC_EXPERIMENTAL=1)
-OsdKern osd_rr_kernel(int wr, int pnl) {
-#if QLDPC_EXPERIMENTAL
-  return pnl == 5 ? osd_rr_kernel_t<5>(wr) : pnl == 4 ? osd_rr_kernel_t<4>(wr) : pnl == 3 ? osd_rr_kernel_t<3>(wr) : pnl == 2 ? osd_rr_kernel_t<2>(wr) : pnl ? osd_rr_kernel_t<1>(wr)
-                                                                                   : osd_rr_kernel_t<0>(wr);
-#else
-  return pnl ? nullptr : osd_rr_kernel_t<0>(wr);
-#endif
-}
-// column-window kernels (register rows, m <= 768, no panel modes): the first WR row words only and
-// a VGPR budget of 6 waves per SIMD, i.e. two 768-thread workgroups per CU
-// (QLDPC_OSD_WPE=3: one workgroup per CU, no VGPR pinning -- A/B)
-constexpr int kOsdWinWR[] = {8, 12, 14, 16};
-template <int WPE>
-OsdKern osd_win_kernel_t(int wr) {
-  switch (wr) {
-    case 8: return &osd_gpu_kernel<768, 8, 1, 0, WPE>;
-    case 12: return &osd_gpu_kernel<768, 12, 1, 0, WPE>;
-    case 14: return &osd_gpu_kernel<768, 14, 1, 0, WPE>;
-    case 16: return &osd_gpu_kernel<768, 16, 1, 0, WPE>;
-    default: return nullptr;
-  }
-}
-OsdKern osd_win_kernel(int wr) {
-#if QLDPC_EXPERIMENTAL  // (the column window: measured and not kept, experimental builds only)
-  const char* e = std::getenv("QLDPC_OSD_WPE");
-  return (e && std::atoi(e) == 3) ? osd_win_kernel_t<3>(wr) : osd_win_kernel_t<6>(wr);
-#else
-  (void)wr;
-  return nullptr;
-#endif
-}
-OsdKern osd_rr2_kernel_of(int wr) {
-#if QLDPC_EXPERIMENTAL
-  switch (wr) {
-    case 20: return &osd_rr2_kernel<20>;
-    case 25: return &osd_rr2_kernel<25>;
-    default: return nullptr;
-  }
-#else
-  (void)wr;
-  return nullptr;
-#endif
-}
-// LDS bytes of the panel area (osd_gpu_kernel PNL): half-words + masks [m] (u32), pivot rows [32][WR+1],
-// pk [32], pidx [m]
-inline size_t osd_pnl_bytes(int m, int wr) {
-  return (((size_t)8 * m + 15) & ~(size_t)15) + (size_t)32 * (wr + 1) * 8 + 128 + (size_t)4 * m;
 }
 }  // namespace
 
@@ -2864,78 +1179,21 @@ int qldpc_rt::osd_gpu_from_host(const qldpc_graph* g, const qldpc_osd* O, qldpc_
   // register-row mode (one row per thread of a 1024-thread workgroup, row words in VGPRs) when
   // m <= 1024 and n <= 2048; QLDPC_OSD_RR=0 keeps the LDS / HBM image
   const char* rr_env = std::getenv("QLDPC_OSD_RR");
-  const char* pnl_env = std::getenv("QLDPC_OSD_PNL");
-  const int want_pnl = (QLDPC_EXPERIMENTAL && pnl_env) ? std::atoi(pnl_env) : 0;  // (PNL 1-5: experimental builds)
   if (!rr_env || std::atoi(rr_env) != 0)
     for (int wr : kOsdWR)
       if (wr >= G->W) {
-        const int rpt = osd_rpt(wr, want_pnl == 3 ? 3 : 0);
-        if (m <= osd_rr_threads(wr, want_pnl == 3 ? 3 : 0) * rpt) {
+        if (m <= osd_rr_threads(wr)) {
           G->wr = wr;
-          G->rr_tb = std::max(64, ((m + rpt - 1) / rpt + 63) / 64 * 64);  // RPT rows per thread, no idle waves
+          G->rr_tb = std::max(64, (m + 63) / 64 * 64);  // one row per thread, no idle waves
         }
         break;
       }
   G->m_lds = (!G->wr && want_lds && std::max(lsort, mbytes) + lbits <= (size_t)160 * 1024 - 256) ? 1 : 0;  // 256: static LDS
   G->bits_off = (int)(G->m_lds ? std::max(lsort, mbytes) : lsort);
   G->pbuf_off = (int)(((size_t)G->bits_off + lbits + 15) & ~(size_t)15);
-  // register-row mode: pivot-row buffer (QLDPC_OSD_1B: a slot per wave and step parity), then
-  // pivpos staged for the swap trace (rank ints)
-  const size_t prows = (size_t)osd_prows(osd_rr_threads(std::max(2, G->wr)));
-  G->lds = G->wr ? (size_t)G->pbuf_off + prows * (size_t)(G->wr + 1) * 8 + (size_t)std::max(1, rank) * 4
+  // register-row mode: pivot-row buffer, then pivpos staged for the swap trace (rank ints)
+  G->lds = G->wr ? (size_t)G->pbuf_off + (size_t)(G->wr + 1) * 8 + (size_t)std::max(1, rank) * 4
                  : (size_t)G->bits_off + lbits;
-  // panel elimination (register-row mode), opt-in QLDPC_OSD_PNL=1: bit-exact, but the single search
-  // wave's per-pivot chain (one wave alone issues a VALU op every 4 cycles) is longer than the two
-  // barriers it saves: n1600 OSD-E(10) 6.66 vs 3.08 us per syndrome, BP+OSD 257k vs 490k shots/s
-  // (profiles/r03/bposd_pnl/)
-  if (G->wr && want_pnl != 0) {
-    const int pv = want_pnl;
-    G->pnl = pv == 5 ? 5 : pv == 4 ? 4 : pv == 3 ? 3 : pv == 2 ? 2 : 1;  // 2: the distributed panel search (one barrier per pivot); 3: blocked
-    if (G->pnl == 5 && (G->host.method == 2 || G->nh > 31)) G->pnl = 0;  // forward elimination: <= 31 Ht columns
-    G->pnl_off = (int)((G->lds + 15) & ~(size_t)15);
-    if (G->pnl == 0) {
-      G->pnl_off = 0;
-    } else if (G->pnl == 5) {  // compaction staging, then (aliased) U words, x bit-vectors, word starts
-      const size_t tb = (size_t)G->rr_tb, rw = (size_t)G->RW;
-      (void)tb;
-      G->lds = (size_t)G->pnl_off + osd_fwd_stg_bytes(G->wr) + (size_t)osd_ul_words((int)rw) * 8 +
-               (size_t)(1 + G->nh) * rw * 8;
-    } else if (G->pnl == 4)  // the lagged loop: a second pivot-row buffer (the pivpos staging moves behind it)
-      G->lds += (size_t)(G->wr + 1) * 8;
-    else
-      G->lds = (size_t)G->pnl_off + (G->pnl == 3 ? osd_blk_bytes(m, G->wr) : osd_pnl_bytes(m, G->wr));
-  }
-  // two syndromes per workgroup (osd_rr2_kernel, the 768-thread register-row kernels): a second LDS
-  // area and HBM slice per workgroup; QLDPC_OSD_NSY=1 keeps one
-  const char* nsy_env = QLDPC_EXPERIMENTAL ? std::getenv("QLDPC_OSD_NSY") : nullptr;  // (osd_rr2_kernel: experimental builds)
-  if (G->wr >= 20 && !G->pnl && !QLDPC_OSD_1B && G->host.uniform && (nsy_env ? std::atoi(nsy_env) : 1) == 2 && osd_rr2_kernel_of(G->wr)) {
-    G->nsy = 2;
-    G->syn_lds = (int)((G->lds + 15) & ~(size_t)15);
-    G->lds = 2 * (size_t)G->syn_lds;
-  }
-  // column window (register rows, one syndrome per workgroup, the lean loop): the elimination
-  // stops once rank pivots are found, and only the positions < rank + nh are read after it (the
-  // pivots and the non-pivot columns Ht[0..nh)), so the rows need only the first words that
-  // cover rank + nh + kOsdWinSlack positions; a syndrome whose pivots run past them (more than
-  // ~kOsdWinSlack dependent positions before the rank) is redone at full width by a second
-  // launch.  Opt-in: QLDPC_OSD_WIN=1 picks the width, =<words> forces one.  MEASURED AND NOT KEPT:
-  // bit-exact (64 BP+OSD GPU tests), but on the reference codes the rank is reached only near
-  // the END of the reliability order (hgp_34_n1600 at p = 0.04: last pivot at position 1419-1538
-  // of 1600, tools/dev/osd_last_pivot.py), so nearly every syndrome overruns a 14-word window and
-  // pays twice: 491 k BP+OSD shots/s vs 615 k at full width (profiles/r05/osd_notkept/window_*).
-  const char* win_env = QLDPC_EXPERIMENTAL ? std::getenv("QLDPC_OSD_WIN") : nullptr;  // (experimental builds)
-  const int win_force = win_env ? std::atoi(win_env) : 0;
-  if (G->wr && !G->pnl && G->nsy == 1 && m <= 768 && win_force > 0 && QLDPC_OSD_LEAN && !kOsdM4R && !QLDPC_OSD_1B) {
-    const long long need = (long long)rank + G->nh;
-    for (int ww : kOsdWinWR) {
-      const bool fits = win_force > 1 ? ww == win_force && (long long)ww * 64 >= need
-                                      : (long long)ww * 64 >= need + kOsdWinSlack;
-      if (fits) {
-        if (ww < G->wr) G->win_wr = ww;
-        break;
-      }
-    }
-  }
   // non-uniform priors: the candidates' column-space vectors Xc [(1 + nh)][W] after X, and the
   // column -> pivot map [n] after the sort maps
   G->ws_words = (long long)G->W * m + (long long)(1 + G->nh) * G->RW +
@@ -2951,8 +1209,7 @@ int qldpc_rt::osd_gpu_from_host(const qldpc_graph* g, const qldpc_osd* O, qldpc_
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, g->device) != hipSuccess || cus <= 0)
     return fail(set_err(QLDPC_EHIP, "device CU count"));
   int nb = 0;
-  const void* kf = G->nsy == 2 ? reinterpret_cast<const void*>(osd_rr2_kernel_of(G->wr))
-                  : G->wr ? reinterpret_cast<const void*>(osd_rr_kernel(G->wr, G->pnl))
+  const void* kf = G->wr ? reinterpret_cast<const void*>(osd_rr_kernel(G->wr))
                   : G->m_lds ? reinterpret_cast<const void*>(&osd_gpu_kernel<kOsdThreadsLds>)
                              : reinterpret_cast<const void*>(&osd_gpu_kernel<kOsdThreads>);
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kf,
@@ -2960,18 +1217,10 @@ int qldpc_rt::osd_gpu_from_host(const qldpc_graph* g, const qldpc_osd* O, qldpc_
                                                    G->lds) != hipSuccess || nb <= 0)
     nb = 1;
   G->grid = cus * nb;
-  if (G->win_wr) {
-    int nbw = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nbw, reinterpret_cast<const void*>(osd_win_kernel(G->win_wr)),
-                                                     G->rr_tb, G->lds) != hipSuccess || nbw <= 0)
-      nbw = 1;
-    G->win_grid = cus * nbw;
-  }
-  const int slices = std::max(G->grid, G->win_grid);
   const size_t E = g->col_idx.size();
   if ((rc = G->rp.alloc((size_t)(m + 1) * 4)) || (rc = G->ci.alloc(std::max<size_t>(E, 1) * 4)) ||
-      (rc = G->ws.alloc((size_t)slices * G->nsy * G->ws_words * 8)) ||
-      (rc = G->iws.alloc((size_t)slices * G->nsy * G->iws_ints * 4)) ||
+      (rc = G->ws.alloc((size_t)G->grid * G->ws_words * 8)) ||
+      (rc = G->iws.alloc((size_t)G->grid * G->iws_ints * 4)) ||
       (!G->host.uniform && (rc = G->softw.alloc((size_t)n * 8))))
     return fail(rc);
   if (!G->host.uniform && hipMemcpy(G->softw.p, G->host.w.data(), (size_t)n * 8, hipMemcpyHostToDevice) != hipSuccess)
@@ -2989,9 +1238,9 @@ int qldpc_osd_gpu_geometry(const qldpc_osd_gpu* osd, int32_t* row_words, int32_t
                            int32_t* workgroups) {
   if (!osd || !row_words || !window_words || !threads || !workgroups) return set_err(QLDPC_EINVAL, "NULL argument");
   *row_words = osd->wr;
-  *window_words = osd->win_wr;
+  *window_words = 0;  // kept for the ABI: no layout holds a column window
   *threads = osd->wr ? osd->rr_tb : osd->m_lds ? kOsdThreadsLds : kOsdThreads;
-  *workgroups = osd->win_wr ? osd->win_grid : osd->grid;
+  *workgroups = osd->grid;
   return 0;
 }
 
@@ -3035,23 +1284,11 @@ int osd_gpu_decode_slots(qldpc_osd_gpu* osd, const uint8_t* d_synd, const double
   a.m = osd->host.m; a.n = osd->host.n; a.W = osd->W; a.RW = osd->RW; a.rank = osd->host.rank;
   a.method = osd->host.method; a.order = osd->host.order; a.NP = osd->NP; a.m_lds = osd->m_lds; a.bits_off = osd->bits_off;
   a.pbuf_off = osd->pbuf_off;
-  a.pnl_off = osd->pnl_off;
-  a.syn_lds = osd->syn_lds;
-  a.ws_words = osd->ws_words; a.iws_ints = osd->iws_ints;
   a.win = 0;
-  const int grid = (int)std::min<long long>((B + osd->nsy - 1) / osd->nsy, osd->grid);
-  if (osd->win_wr) {  // the column window, then the full-width redo of its overruns
-    const char* tr = std::getenv("QLDPC_OSD_WIN_REDO");
-    a.win = (tr && std::atoi(tr) == 1) ? 3 : 1;
-    hipLaunchKernelGGL(osd_win_kernel(osd->win_wr), dim3((int)std::min<long long>(B, osd->win_grid)), dim3(osd->rr_tb),
-                       osd->lds, (hipStream_t)stream, a);
-    QLDPC_HIP(hipGetLastError());
-    a.win = 2;
-    hipLaunchKernelGGL(osd_rr_kernel(osd->wr, 0), dim3(grid), dim3(osd->rr_tb), osd->lds, (hipStream_t)stream, a);
-  } else if (osd->nsy == 2)
-    hipLaunchKernelGGL(osd_rr2_kernel_of(osd->wr), dim3(grid), dim3(osd->rr_tb), osd->lds, (hipStream_t)stream, a);
-  else if (osd->wr)
-    hipLaunchKernelGGL(osd_rr_kernel(osd->wr, osd->pnl), dim3(grid), dim3(osd->rr_tb), osd->lds, (hipStream_t)stream, a);
+  a.ws_words = osd->ws_words; a.iws_ints = osd->iws_ints;
+  const int grid = (int)std::min<long long>(B, osd->grid);
+  if (osd->wr)
+    hipLaunchKernelGGL(osd_rr_kernel(osd->wr), dim3(grid), dim3(osd->rr_tb), osd->lds, (hipStream_t)stream, a);
   else if (osd->m_lds)
     hipLaunchKernelGGL(osd_gpu_kernel<kOsdThreadsLds>, dim3(grid), dim3(kOsdThreadsLds), osd->lds, (hipStream_t)stream, a);
   else

@@ -410,8 +410,8 @@ class DeviceOSD(_Handle):
         self._create("qldpc_osd_gpu_create", graph.handle, _np_ptr(self._probs), self.osd_method, self.osd_order)
 
     def geometry(self) -> dict:
-        """The elimination layout the handle chose: register-row words, column-window words (0 =
-        none), threads per workgroup and the persistent grid."""
+        """The elimination layout the handle chose: register-row words, column-window words (always
+        0: the key stays for the ABI), threads per workgroup and the persistent grid."""
         return dict(zip(("row_words", "window_words", "threads", "workgroups"),
                         self._ints("qldpc_osd_gpu_geometry", "qldpc_osd_gpu_geometry", 4)))
 

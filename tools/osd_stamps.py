@@ -36,17 +36,6 @@ tot = sum(v[:6])
 print(f"{name} p={p} shots={c} osd decodes={o} syndromes stamped={v[6]}")
 for k, nm in enumerate(names):
     print(f"{nm:20s} {100 * v[k] / max(1, tot):6.2f}%  {v[k] / max(1, v[6]):10.0f} clk per syndrome")
-if os.environ.get("QLDPC_OSD_PNL", "0") in ("1", "2"):  # panel modes: [7] pivots, [8] panel searches, [9] panel updates
-    print(f"pivots per syndrome {v[7] / max(1, v[6]):.0f}; per pivot: {v[2] / max(1, v[7]):.0f} clk, "
-          f"of which the panel's pivot search {v[8] / max(1, v[7]):.0f}, the panel's row updates {v[9] / max(1, v[7]):.0f}")
-else:
-    print(f"positions per syndrome {v[7] / max(1, v[6]):.0f}; per position: {v[2] / max(1, v[7]):.0f} clk, "
-          f"of which search + barrier {v[8] / max(1, v[7]):.0f}, pivot-row publication + barrier (register rows) "
-          f"{v[9] / max(1, v[7]):.0f}")
-if os.environ.get("QLDPC_OSD_PNL", "0") == "3":  # blocked: [7] pivots, [8] searches, [9] tables, [10] row updates, [11] step 1
-    pv = max(1, v[7])
-    print(f"blocked: pivots per syndrome {v[7] / max(1, v[6]):.0f}; per pivot: search {v[8] / pv:.0f} clk, tables {v[9] / pv:.0f}, "
-          f"row updates {v[10] / pv:.0f}, panel-word exchange {v[11] / pv:.0f} (Gauss-Jordan {v[2] / pv:.0f})")
-if os.environ.get("QLDPC_OSD_PNL", "0") == "5":  # forward: [15] compactions, [13] back substitution (wave 0's view)
-    print(f"forward: compactions {v[15] / max(1, v[6]):.0f} clk per syndrome, "
-          f"back substitution {v[13] / max(1, v[6]):.0f} clk per syndrome")
+print(f"positions per syndrome {v[7] / max(1, v[6]):.0f}; per position: {v[2] / max(1, v[7]):.0f} clk, "
+      f"of which search + barrier {v[8] / max(1, v[7]):.0f}, pivot-row publication + barrier (register rows) "
+      f"{v[9] / max(1, v[7]):.0f}")
