@@ -308,7 +308,7 @@ int qldpc_bp_geometry(const qldpc_bp *bp, int32_t *threads, int32_t *vars_per_th
  * < 64 KiB), 2 = streamed variables, 1 = LDS-atomic check state, 4 = engine 3
  * with c2v computed by the check phase, 5 = product-sum (bp_method 0), 6 = HBM-resident
  * messages (qldpc_bp_create_hbm; automatic for images over 160 KiB), 7 = Relay-BP
- * (qldpc_bp_create_relay).
+ * (qldpc_bp_create_relay), 8 = serial-schedule min-sum (qldpc_bp_create_serial).
  * QLDPC_ENGINE in the environment selects 1, 2 or 4 explicitly. */
 int qldpc_bp_engine(const qldpc_bp *bp, int32_t *engine);
 
@@ -388,6 +388,58 @@ int qldpc_relay_decode_host(int32_t m, int32_t n, const int32_t *row_ptr, const 
                             int32_t leg_iter, double gamma_lo, double gamma_hi, int32_t stop_nconv,
                             uint64_t gamma_seed, double ms_scaling_factor, int32_t precision, const uint8_t *synd,
                             uint8_t *corr, int32_t *iters, uint8_t *conv, int32_t *nsol, int64_t B, int32_t threads);
+
+/*
+ * Min-sum BP on the serial (variable-by-variable, "layered") schedule, engine 8 (serial.hip).  No
+ * reference counterpart (the reference's ldpc release offered the flooding schedule only; current ldpc
+ * calls this schedule="serial").
+ * THE LAW, T = double (precision 64) or float (32), every operation in T, the primitives those of
+ * ldpc's min-sum:
+ *   priors   L0_j = (T) log((1 - p_j) / p_j), computed in double with libm.
+ *   layers   layer(j) is the smallest l >= 0 such that no variable j' < j with layer(j') = l shares a
+ *            check with j: first-fit in ascending variable index.  The sweep order pi is the variables
+ *            sorted by (layer, index).  Two variables of one layer share no check, so updating a layer in
+ *            parallel equals the sequential sweep in order pi.  The host law is that sequential sweep.
+ *   start    b2c[e] = L0_col(e) for every edge.
+ *   iteration t = 1 .. max_iter: a_t = (T) ms_scaling_factor, or (T)(1 - 2^-t) when ms_scaling_factor
+ *            is 0.  For each variable j in order pi:
+ *            1. for each edge e of column j, rows ascending, with i = row(e): mag = the minimum of
+ *               |b2c[e']| over the other edges e' of row i, or the sentinel (1e308 for double, FLT_MAX
+ *               for float) when there is none; s = synd_i + the number of those e' with b2c[e'] <= 0;
+ *               c2b[e] = mag * (s odd ? -a_t : a_t);
+ *            2. the variable pass of min-sum on column j alone: forward over the column's edges, temp =
+ *               L0_j, for each edge b2c[e] = temp, temp = temp + c2b[e]; post_j = temp, dec_j = (temp <=
+ *               0); backward, temp = 0, for each edge in reverse b2c[e] = b2c[e] + temp, temp = temp +
+ *               c2b[e].
+ *            After the sweep iters = t.  The decode stops with conv = 1 when H dec == synd.
+ *   output   corr = dec of the last sweep; iters; conv.  The soft output is post_j widened to double,
+ *            laid out like qldpc_bp_create_soft's posteriors ([B][n]).
+ * A minimum and a parity count do not depend on the order in which a row is walked, so the kernel may
+ * read a row in any order; the column sums keep the stated order.
+ *
+ * qldpc_bp_create_serial returns an ordinary qldpc_bp (qldpc_bp_engine: 8) for qldpc_bp_decode_batch
+ * and, with soft = 1, qldpc_bp_decode_batch_soft, and for every loop that decodes through a qldpc_bp:
+ * the staged data-error pipeline (qldpc_mc_create sends it there), qldpc_mc_launch_weight, the
+ * phenomenological and circuit loops.  qldpc_bp_set_channel_probs rebuilds L0.  No qldpc_mc_set_osd
+ * and no qldpc_phenl_set_final_osd: QLDPC_ENOTSUP.  Min-sum only.  QLDPC_EINVAL: max_iter < 1, a
+ * precision other than 32 / 64.  One decode per workgroup (64, 128 or 256 threads: the widest layer
+ * decides; QLDPC_SERIAL_TB overrides), the whole decode in the kernel; b2c in LDS when the image fits
+ * 160 KiB, else in an HBM workspace (QLDPC_SERIAL_WS=1 forces that); the index arrays and the layer
+ * table are staged in LDS as 16-bit words when they fit that range and cost no resident workgroup
+ * (QLDPC_SERIAL_IDX=0: walked in global memory).
+ * qldpc_serial_layers: layer(j) of every variable and the number of layers, host only.
+ * qldpc_serial_decode_host: the law in plain C++ on host memory (no HIP call, any graph): synd [B][m],
+ * corr [B][n], iters / conv [B], post [B][n] (each of the three may be NULL); threads <= 0 =
+ * OMP_NUM_THREADS if set, else all hardware threads.
+ */
+int qldpc_bp_create_serial(qldpc_graph *g, const double *channel_probs, int32_t max_iter, double ms_scaling_factor,
+                           int32_t precision, int32_t soft, qldpc_bp **out);
+int qldpc_serial_layers(int32_t m, int32_t n, const int32_t *row_ptr, const int32_t *col_idx, int32_t *layer_out,
+                        int32_t *num_layers);
+int qldpc_serial_decode_host(int32_t m, int32_t n, const int32_t *row_ptr, const int32_t *col_idx,
+                             const double *channel_probs, int32_t max_iter, double ms_scaling_factor,
+                             int32_t precision, const uint8_t *synd, uint8_t *corr, int32_t *iters, uint8_t *conv,
+                             double *post, int64_t B, int32_t threads);
 
 /* BP+OSD in the fused shot loop (bposd_decoder per sector, src/Decoders.py:26-41, inside
  * _single_run, src/Simulators.py:117-168): after qldpc_mc_set_osd, qldpc_mc_launch captures

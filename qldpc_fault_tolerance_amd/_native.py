@@ -35,6 +35,7 @@ EXPORTED = [
     "qldpc_mc_create_staged", "qldpc_mc_launch_weight", "qldpc_sample_errors_weight",
     "qldpc_sample_errors_weight_host",
     "qldpc_bp_create_relay", "qldpc_relay_gammas", "qldpc_relay_decode_host",
+    "qldpc_bp_create_serial", "qldpc_serial_layers", "qldpc_serial_decode_host",
 ]
 BUILD_EXPERIMENTAL = 1  # qldpc_build_flags(): the measured-and-not-kept kernel families are compiled in
 COMM_ID_BYTES = 128
@@ -44,6 +45,7 @@ class NativeUnavailable(RuntimeError):
     pass
 
 
+EINVAL = -1  # QLDPC_EINVAL (include/qldpc_hip.h)
 ENOTSUP = -4  # QLDPC_ENOTSUP (include/qldpc_hip.h)
 
 
@@ -242,6 +244,13 @@ def _declare(L):
     L.qldpc_relay_gammas.argtypes = [_i32, _dbl, _i32, _dbl, _dbl, _u64, _i32, _vp]
     L.qldpc_relay_decode_host.restype = ctypes.c_int
     L.qldpc_relay_decode_host.argtypes = [_i32, _i32, _vp, _vp, _vp] + relay + [_vp, _vp, _vp, _vp, _vp, _i64, _i32]
+    L.qldpc_bp_create_serial.restype = ctypes.c_int
+    L.qldpc_bp_create_serial.argtypes = [_vp, _vp, _i32, _dbl, _i32, _i32, _pp]
+    L.qldpc_serial_layers.restype = ctypes.c_int
+    L.qldpc_serial_layers.argtypes = [_i32, _i32, _vp, _vp, _vp, _vp]
+    L.qldpc_serial_decode_host.restype = ctypes.c_int
+    L.qldpc_serial_decode_host.argtypes = [_i32, _i32, _vp, _vp, _vp, _i32, _dbl, _i32, _vp, _vp, _vp, _vp, _vp, _i64,
+                                           _i32]
 
 
 def lib():

@@ -361,6 +361,7 @@ int qldpc_graph_info(const qldpc_graph* g, int32_t* m, int32_t* n, int32_t* nnz,
 static int upload_llr(qldpc_bp* bp) {
   const int TB = bp->route.TB, VPL = bp->route.VPL, n = bp->g->n;
   if (bp->route.engine == 7) return relay_upload_priors(bp);  // L0 and the integer solution weights
+  if (bp->route.engine == 8) return serial_upload_priors(bp);
   if (bp->route.engine == 6) {  // HBM engine: log((1-p)/p) per variable, variable order
     std::vector<double> l64(n);
     for (int j = 0; j < n; ++j) l64[j] = std::log((1.0 - bp->probs[j]) / bp->probs[j]);  // glibc log, as Cython
@@ -1074,8 +1075,9 @@ static void bp1_prepare(qldpc_bp* bp) {
     qldpc_firstmin_destroy(bp->bp1);
     bp->bp1 = nullptr;
   }
-  // (a relay decoder with one iteration in all still runs its own law: memory term, solution weights)
-  bp->bp1_off = !(bp->max_iter == 1 && bp->method == 1) || bp->route.engine == 7 || env_int("QLDPC_BP1", 1) == 0;
+  // (a relay decoder with one iteration in all still runs its own law: memory term, solution weights;
+  // one serial sweep is not one flooding iteration)
+  bp->bp1_off = !(bp->max_iter == 1 && bp->method == 1) || bp->route.engine >= 7 || env_int("QLDPC_BP1", 1) == 0;
   if (bp->bp1_off) return;
   const std::string keep = qldpc_rt::g_err;  // an ENOTSUP here is not the caller's error
   if (qldpc_firstmin_create(bp->g, bp->probs.data(), 0, bp->alpha, bp->route.precision, &bp->bp1) != 0) {
@@ -1706,7 +1708,7 @@ int qldpc_bp_destroy(qldpc_bp* bp) {
   if (bp->bp1) qldpc_firstmin_destroy(bp->bp1);
   for (DevBuf* d : {&bp->vchk, &bp->llr, &bp->rdeg, &bp->rowtab, &bp->perm, &bp->rperm, &bp->work, &bp->ps_rp, &bp->ps_ci, &bp->ps_cp,
                     &bp->ps_ce, &bp->ps_ws, &bp->h_rp, &bp->h_rcol, &bp->h_rcpos, &bp->h_cp, &bp->h_crpos, &bp->h_ws,
-                    &bp->rl_gam, &bp->rl_wq})
+                    &bp->rl_gam, &bp->rl_wq, &bp->sr_cr, &bp->sr_ord, &bp->sr_lp})
     d->release();
   delete bp;
   return 0;
@@ -1777,6 +1779,37 @@ int qldpc_bp_create_relay(qldpc_graph* g, const double* channel_probs, int32_t p
   if ((rc = device_cus(g->device, bp->cus))) return fail(rc);
   bp->ps_grid = (long long)bp->blocks_per_cu * bp->cus;
   if (!lds_msgs && (rc = bp->ps_ws.alloc(std::max<size_t>(1, (size_t)bp->ps_grid * 2 * E * tsize)))) return fail(rc);
+  *out = bp;
+  return 0;
+}
+
+// Engine 8 (serial.hip): min-sum BP on the serial schedule, run as layers of independent variables.
+int qldpc_bp_create_serial(qldpc_graph* g, const double* channel_probs, int32_t max_iter, double ms_scaling_factor,
+                           int32_t precision, int32_t soft, qldpc_bp** out) {
+  if (!out) return set_err(QLDPC_EINVAL, "NULL argument");
+  int rc = validate_create(g, channel_probs, precision, QLDPC_MIN_SUM);
+  if (rc) return rc;
+  if ((rc = serial_check_params(g->n, max_iter, precision))) return rc;
+  QLDPC_HIP(hipSetDevice(g->device));
+  auto* bp = new qldpc_bp();
+  auto fail = [&](int code) {
+    qldpc_bp_destroy(bp);
+    return code;
+  };
+  bp->g = g;
+  bp->route.engine = 8;
+  bp->route.precision = precision;
+  bp->method = QLDPC_MIN_SUM;
+  bp->alpha = ms_scaling_factor;
+  bp->max_iter = max_iter;
+  bp->probs.assign(channel_probs, channel_probs + g->n);
+  bp->bp1_off = true;
+  bp->sr_soft = soft != 0;
+  if ((rc = upload_csr_csc(bp)) || (rc = bp->llr.alloc(std::max<size_t>(1, g->n) * (precision == 32 ? 4 : 8))) ||
+      (rc = upload_llr(bp)) || (rc = device_cus(g->device, bp->cus)) ||
+      (rc = serial_prepare(bp, env_int("QLDPC_SERIAL_WS", 0) == 1, env_int("QLDPC_SERIAL_IDX", 1) != 0,
+                           env_int("QLDPC_SERIAL_TB", 0), kLdsMax)))
+    return fail(rc);
   *out = bp;
   return 0;
 }
@@ -1922,8 +1955,8 @@ int qldpc_bp_decode_batch_soft(qldpc_bp* bp, const uint8_t* d_synd, uint8_t* d_c
   if (!bp || (B > 0 && !d_post)) return set_err(QLDPC_EINVAL, "NULL argument");
   // engine 1 (min-sum, qldpc_bp_create_soft) or engine 5 (product-sum: any qldpc_bp_create decoder with
   // bp_method 0 writes ldpc's log_prob_ratios on request)
-  if (bp->route.engine != 1 && bp->route.engine != 5)
-    return set_err(QLDPC_ENOTSUP, "soft output needs a decoder from qldpc_bp_create_soft (min-sum) or a product-sum decoder");
+  if (bp->route.engine != 1 && bp->route.engine != 5 && !(bp->route.engine == 8 && bp->sr_soft))
+    return set_err(QLDPC_ENOTSUP, "soft output needs a decoder from qldpc_bp_create_soft (min-sum), a product-sum decoder or a serial decoder created with soft = 1");
   return decode_batch(bp, d_synd, d_corr, d_iters, d_conv, d_post, B, stream);
 }
 
@@ -1940,6 +1973,7 @@ static int decode_batch(qldpc_bp* bp, const uint8_t* d_synd, uint8_t* d_corr, in
   if (bp->route.engine == 5) return ps_decode_launch(bp, d_synd, d_corr, d_iters, d_conv, B, (hipStream_t)stream, d_post);
   if (bp->route.engine == 6) return hbm_decode_launch(bp, d_synd, d_corr, d_iters, d_conv, B, (hipStream_t)stream);
   if (bp->route.engine == 7) return relay_decode_launch(bp, d_synd, d_corr, d_iters, d_conv, B, (hipStream_t)stream);
+  if (bp->route.engine == 8) return serial_decode_launch(bp, d_synd, d_corr, d_iters, d_conv, d_post, B, (hipStream_t)stream);
   const long long cap = (long long)bp->blocks_per_cu * bp->cus;
   if (bp->route.engine == 1) {
     DecArgs a;

@@ -93,6 +93,12 @@ struct qldpc_bp {
   uint64_t rl_seed = 0;
   qldpc_rt::DevBuf rl_gam, rl_wq;
   bool rl_idx = false;  // the graph's CSR / CSC staged in LDS as 16-bit words
+  // engine 8 (serial.hip): the CSC rows [E], the sweep order [n] and the layer boundaries [layers + 1]
+  // beside engine 5's CSR / CSC; llr holds L0 in variable order
+  qldpc_rt::DevBuf sr_cr, sr_ord, sr_lp;
+  int sr_layers = 0;
+  bool sr_idx = false;   // the index arrays staged in LDS as 16-bit words
+  bool sr_soft = false;  // the kernel keeps the posteriors (qldpc_bp_decode_batch_soft)
   // engine 6 (HBM-resident messages, bp_hbm.hip): uniform edge tables and the message workspace
   qldpc_rt::DevBuf h_rp, h_rcol, h_rcpos, h_cp, h_crpos, h_ws;
 };
@@ -140,6 +146,14 @@ int relay_upload_priors(qldpc_bp* bp);
 int relay_upload_gammas(qldpc_bp* bp);
 int relay_decode_launch(const qldpc_bp* bp, const uint8_t* synd, uint8_t* corr, int32_t* iters, uint8_t* conv,
                         int64_t B, hipStream_t stream);
+
+// engine 8 (serial.hip)
+int serial_check_params(int64_t n, int32_t max_iter, int32_t precision);
+const void* serial_kernel_ptr(int precision, bool lds_index);
+int serial_upload_priors(qldpc_bp* bp);
+int serial_prepare(qldpc_bp* bp, bool force_ws, bool allow_idx, int want_tb, int lds_max);
+int serial_decode_launch(const qldpc_bp* bp, const uint8_t* synd, uint8_t* corr, int32_t* iters, uint8_t* conv,
+                         double* post, int64_t B, hipStream_t stream);
 
 // GPU OSD handle built on this graph? (osd.hip; qldpc_phenl_set_final_osd checks it)
 bool osd_gpu_matches(const qldpc_osd_gpu* o, const qldpc_graph* g);

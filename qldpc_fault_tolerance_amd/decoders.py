@@ -31,22 +31,27 @@ def _int_max_iter(max_iter, n):
 
 
 class BPDecoder:
-    """``BPDecoder(h, channel_probs, max_iter, bp_method, ms_scaling_factor)`` (``src/Decoders.py:77-90``)."""
+    """``BPDecoder(h, channel_probs, max_iter, bp_method, ms_scaling_factor)`` (``src/Decoders.py:77-90``).
+
+    ``schedule="serial"`` (no reference counterpart; ``schedule="serial"`` of current ldpc) runs min-sum
+    on the serial, variable-by-variable schedule (engine 8, ``qldpc_bp_create_serial``); the default
+    ``"parallel"`` is the reference's flooding schedule."""
 
     def __init__(self, h, channel_probs, max_iter, bp_method, ms_scaling_factor, precision: int = 64,
-                 device: int | None = None, vars_per_thread: int = 0):
+                 device: int | None = None, vars_per_thread: int = 0, schedule: str = "parallel"):
         from .engine import DeviceBP
 
         self.h = h
         self.max_iter = max_iter
         self.bp_method = bp_method
+        self.schedule = schedule
         self.ms_scaling_factor = ms_scaling_factor
         self.channel_probs = np.asarray(channel_probs, dtype=np.float64)
         H = h if isinstance(h, CSR) else CSR.from_dense(h)
         self.num_checks, self.num_qubits = H.m, H.n
         self.decoder = DeviceBP(H, self.channel_probs, max_iter=_int_max_iter(max_iter, H.n), bp_method=bp_method,
                                 ms_scaling_factor=ms_scaling_factor, precision=precision, device=device,
-                                vars_per_thread=vars_per_thread)
+                                vars_per_thread=vars_per_thread, schedule=schedule)
         self.iter = 0
         self.converge = 0
 
@@ -186,23 +191,27 @@ class BPOSD_Decoder:
     """``BPOSD_Decoder(h, channel_probs, max_iter, bp_method, ms_scaling_factor, osd_method, osd_order)``
     (``src/Decoders.py:26-41``): ``bposd_decoder`` = BP, then OSD when BP does not converge.
 
-    BP runs on the GPU (engine 1 with soft output: ``qldpc_bp_decode_batch_soft``)
-    and hands its final posteriors to the native OSD stage (``qldpc_osd_decode_batch``).
+    BP runs on the GPU (engine 1 with soft output: ``qldpc_bp_decode_batch_soft``; engine 8 with
+    ``schedule="serial"``) and hands its final posteriors to the native OSD stage
+    (``qldpc_osd_decode_batch``).
     ``decode`` returns ``osdw_decoding`` like the reference; ``osd0_decoding``,
     ``bp_decoding``, ``converge``, ``iter`` and ``log_prob_ratios`` are kept.
     """
 
     def __init__(self, h, channel_probs, max_iter, bp_method, ms_scaling_factor, osd_method, osd_order,
-                 precision: int = 64, device: int | None = None, osd_threads: int = 0, use_gpu_osd: bool = True):
+                 precision: int = 64, device: int | None = None, osd_threads: int = 0, use_gpu_osd: bool = True,
+                 schedule: str = "parallel"):
         from .engine import DeviceBP, DeviceOSD, HostOSD
 
         self.h = h
+        self.schedule = schedule
         H = h if isinstance(h, CSR) else CSR.from_dense(h)
         self.num_checks, self.num_qubits = H.m, H.n
         self.channel_probs = np.asarray(channel_probs, dtype=np.float64)
         self.osd_method, self.osd_order = osd_method, osd_order
         self.decoder = DeviceBP(H, self.channel_probs, max_iter=_int_max_iter(max_iter, H.n), bp_method=bp_method,
-                                ms_scaling_factor=ms_scaling_factor, precision=precision, device=device, soft=True)
+                                ms_scaling_factor=ms_scaling_factor, precision=precision, device=device, soft=True,
+                                schedule=schedule)
         self.osd = HostOSD(H, self.channel_probs, osd_method=osd_method, osd_order=osd_order)
         # OSD on the GPU (uniform priors: popcount weights; non-uniform: soft weights); the host stage
         # stays for use_gpu_osd=False and graphs past the GPU kernel's envelope
@@ -249,11 +258,12 @@ class BP_Decoder_Class(DecoderClass):
     """``src/Decoders.py:141-172``: factory keyed by ``{'h', 'p_data'[, 'p_syndrome']}``."""
 
     def __init__(self, max_iter_ratio: int, bp_method: str, ms_scaling_factor: float, precision: int = 64,
-                 device: int | None = None):
+                 device: int | None = None, schedule: str = "parallel"):
         self.decoder_default_params = {"max_iter_ratio": max_iter_ratio, "bp_method": bp_method,
                                        "ms_scaling_factor": ms_scaling_factor}
         self.precision = precision
         self.device = device
+        self.schedule = schedule
 
     @staticmethod
     def _probs(params):
@@ -275,7 +285,7 @@ class BP_Decoder_Class(DecoderClass):
         return BPDecoder(h=p["h"], channel_probs=probs, max_iter=max_iter,
                          bp_method=self.decoder_default_params["bp_method"],
                          ms_scaling_factor=self.decoder_default_params["ms_scaling_factor"],
-                         precision=self.precision, device=self.device)
+                         precision=self.precision, device=self.device, schedule=self.schedule)
 
 
 class RelayBP_Decoder_Class(DecoderClass):
@@ -310,12 +320,13 @@ class BPOSD_Decoder_Class(DecoderClass):
     """``src/Decoders.py:100-138``: BP+OSD factory keyed like :class:`BP_Decoder_Class`."""
 
     def __init__(self, max_iter_ratio: int, bp_method: str, ms_scaling_factor: float, osd_method: str,
-                 osd_order: int, precision: int = 64, device: int | None = None):
+                 osd_order: int, precision: int = 64, device: int | None = None, schedule: str = "parallel"):
         self.decoder_default_params = {"max_iter_ratio": max_iter_ratio, "bp_method": bp_method,
                                        "ms_scaling_factor": ms_scaling_factor, "osd_method": osd_method,
                                        "osd_order": osd_order}
         self.precision = precision
         self.device = device
+        self.schedule = schedule
 
     def GetDecoder(self, code_and_noise_channel_params):
         p = code_and_noise_channel_params
@@ -326,7 +337,8 @@ class BPOSD_Decoder_Class(DecoderClass):
         max_iter = num_qubits / d["max_iter_ratio"]
         return BPOSD_Decoder(h=p["h"], channel_probs=probs, max_iter=max_iter, bp_method=d["bp_method"],
                              ms_scaling_factor=d["ms_scaling_factor"], osd_method=d["osd_method"],
-                             osd_order=d["osd_order"], precision=self.precision, device=self.device)
+                             osd_order=d["osd_order"], precision=self.precision, device=self.device,
+                             schedule=self.schedule)
 
 
 # ------------------------------------------------------------------ space-time
@@ -349,10 +361,11 @@ class ST_BP_Decoder_syndrome:
     """BP on the stacked space-time graph (``src/Decoders_SpaceTime.py:200-223``)."""
 
     def __init__(self, h, p_data: float, p_synd: float, max_iter: int, bp_method: str, ms_scaling_factor,
-                 num_rep: int, precision: int = 64, device: int | None = None):
+                 num_rep: int, precision: int = 64, device: int | None = None, schedule: str = "parallel"):
         from .engine import DeviceBP
 
         H = np.asarray(h)
+        self.schedule = schedule
         self.num_checks, self.num_qubits = H.shape
         self.h = H
         self.num_rep = int(num_rep)
@@ -362,7 +375,7 @@ class ST_BP_Decoder_syndrome:
         self.max_iter = max_iter
         self.space_decoder = DeviceBP(self.ST_csr, probs, max_iter=_int_max_iter(max_iter, self.ST_csr.n),
                                       bp_method=bp_method, ms_scaling_factor=ms_scaling_factor, precision=precision,
-                                      device=device)
+                                      device=device, schedule=schedule)
 
     @property
     def ST_h(self):
@@ -384,11 +397,12 @@ class ST_BP_Decoder_Class(DecoderClass):
     """``src/Decoders_SpaceTime.py:227-257`` (keeps quirk Q4: p_synd = p_data when p_syndrome is given)."""
 
     def __init__(self, max_iter_ratio: int, bp_method: str, ms_scaling_factor: float, precision: int = 64,
-                 device: int | None = None):
+                 device: int | None = None, schedule: str = "parallel"):
         self.decoder_default_params = {"max_iter_ratio": max_iter_ratio, "bp_method": bp_method,
                                        "ms_scaling_factor": ms_scaling_factor}
         self.precision = precision
         self.device = device
+        self.schedule = schedule
 
     def GetDecoder(self, code_and_noise_channel_params):
         p = code_and_noise_channel_params
@@ -403,7 +417,8 @@ class ST_BP_Decoder_Class(DecoderClass):
         return ST_BP_Decoder_syndrome(h=h, p_data=p_data, p_synd=p_synd, max_iter=max_iter,
                                       bp_method=self.decoder_default_params["bp_method"],
                                       ms_scaling_factor=self.decoder_default_params["ms_scaling_factor"],
-                                      num_rep=p["num_rep"], precision=self.precision, device=self.device)
+                                      num_rep=p["num_rep"], precision=self.precision, device=self.device,
+                                      schedule=self.schedule)
 
 
 # ------------------------------------------------------------------ circuit-level space-time
@@ -414,9 +429,9 @@ class ST_BP_Decoder_Circuit(BPDecoder):
     non-uniform ``channel_probs`` (the mechanisms' probabilities)."""
 
     def __init__(self, h, channel_probs, max_iter, bp_method, ms_scaling_factor, precision: int = 64,
-                 device: int | None = None):
+                 device: int | None = None, schedule: str = "parallel"):
         super().__init__(h, channel_probs, max_iter, bp_method, ms_scaling_factor, precision=precision,
-                         device=device)
+                         device=device, schedule=schedule)
         self.space_decoder = self.decoder
 
     def decode(self, synd):
@@ -434,10 +449,12 @@ class ST_BP_Decoder_Circuit_Class(DecoderClass):
     """``src/Decoders_SpaceTime.py:296-321``: keys ``h``, ``code_h``, ``channel_probs``;
     ``max_iter = int(n(code_h) / max_iter_ratio)``."""
 
-    def __init__(self, max_iter_ratio: int, bp_method: str, ms_scaling_factor: float, precision: int = 64):
+    def __init__(self, max_iter_ratio: int, bp_method: str, ms_scaling_factor: float, precision: int = 64,
+                 schedule: str = "parallel"):
         self.decoder_default_params = {"max_iter_ratio": max_iter_ratio, "bp_method": bp_method,
                                        "ms_scaling_factor": ms_scaling_factor}
         self.precision = precision
+        self.schedule = schedule
 
     def GetDecoder(self, code_and_noise_channel_params):
         p = code_and_noise_channel_params
@@ -448,7 +465,8 @@ class ST_BP_Decoder_Circuit_Class(DecoderClass):
         d = self.decoder_default_params
         return ST_BP_Decoder_Circuit(h=p["h"], channel_probs=p["channel_probs"],
                                      max_iter=int(num_qubits / d["max_iter_ratio"]), bp_method=d["bp_method"],
-                                     ms_scaling_factor=d["ms_scaling_factor"], precision=self.precision)
+                                     ms_scaling_factor=d["ms_scaling_factor"], precision=self.precision,
+                                     schedule=self.schedule)
 
 
 class ST_BPOSD_Decoder_Circuit_Class(DecoderClass):

@@ -214,6 +214,10 @@ class DeviceBP(_Handle):
     ``relay``: a :class:`RelayParams` (or a dict of its fields) makes the handle a Relay-BP decoder
     (engine 7, ``qldpc_bp_create_relay``): min-sum only, ``max_iter`` is then the chain's total.
 
+    ``schedule``: ``"parallel"`` (the reference's flooding schedule) or ``"serial"``: min-sum on the
+    serial, variable-by-variable schedule (engine 8, ``qldpc_bp_create_serial``, the law in
+    include/qldpc_hip.h), with soft output when ``soft`` is set.
+
     ``anneal_iters``: moves of the annealed V-slot placement the fp64 engine-3 families run at
     creation (host time, one core: ~0.18 us per move; default 4000 per edge capped at 2^25, memoised
     per process for the same graph).  0 keeps the greedy placement (decodes identically; the placement
@@ -224,13 +228,17 @@ class DeviceBP(_Handle):
     def __init__(self, H, channel_probs, max_iter: int = 0, bp_method="minimum_sum", ms_scaling_factor=0.625,
                  precision: int = 64, vars_per_thread: int = 0, device: int | None = None, graph: DeviceGraph | None = None,
                  min_col_slots: int = 0, soft: bool = False, hbm: bool = False, anneal_iters: int | None = None,
-                 relay=None):
+                 relay=None, schedule: str = "parallel"):
+        if schedule not in ("parallel", "serial"):
+            raise ValueError(f"schedule must be 'parallel' or 'serial', not {schedule!r}")
+        if schedule == "serial" and (bp_method_code(bp_method) != 1 or relay is not None):
+            raise ValueError("schedule='serial' is minimum_sum on its own engine, without relay legs")
         if anneal_iters is not None:  # read by qldpc_bp_create (QLDPC_M2S_ANNEAL) at creation only
             old = os.environ.get("QLDPC_M2S_ANNEAL")
             os.environ["QLDPC_M2S_ANNEAL"] = str(int(anneal_iters))
             try:
                 self.__init__(H, channel_probs, max_iter, bp_method, ms_scaling_factor, precision, vars_per_thread,
-                              device, graph, min_col_slots, soft, hbm, None, relay)
+                              device, graph, min_col_slots, soft, hbm, None, relay, schedule)
             finally:
                 if old is None:
                     os.environ.pop("QLDPC_M2S_ANNEAL", None)
@@ -246,8 +254,13 @@ class DeviceBP(_Handle):
         self.precision = int(precision)
         self.soft = bool(soft)
         self.relay = RelayParams.of(relay) if relay is not None else None
+        self.schedule = schedule
         common = (self.graph.handle, _np_ptr(self.channel_probs), self.max_iter)
-        if self.relay is not None:
+        if schedule == "serial":
+            if hbm:
+                raise NotImplementedError("the serial schedule runs on its own engine, not the HBM-resident one")
+            self._create("qldpc_bp_create_serial", *common, self.ms_scaling_factor, self.precision, int(self.soft))
+        elif self.relay is not None:
             if self.bp_method != 1 or self.soft or hbm:
                 raise NotImplementedError("Relay-BP is minimum_sum on its own engine, without soft output")
             self.max_iter = self.relay.max_iter
@@ -656,6 +669,41 @@ def relay_decode_host(H, channel_probs, relay, synd, ms_scaling_factor=0.625, pr
         c.m, c.n, _np_ptr(rp), _np_ptr(ci), _np_ptr(probs), *r.abi(ms_scaling_factor, precision), _np_ptr(s),
         _np_ptr(corr), _np_ptr(iters), _np_ptr(conv), _np_ptr(nsol), B, int(threads)), "qldpc_relay_decode_host")
     return corr.astype(np.int64), iters, conv.astype(bool), nsol
+
+
+def serial_layers(H):
+    """``qldpc_serial_layers``: the layer of every variable under the serial schedule's first-fit rule
+    (include/qldpc_hip.h) and the number of layers.  Host only: needs the library, not a GPU."""
+    c = H if isinstance(H, CSR) else CSR.from_dense(H)
+    rp = np.ascontiguousarray(c.row_ptr, dtype=np.int32)
+    ci = np.ascontiguousarray(c.col_idx, dtype=np.int32)
+    layer = np.zeros(max(c.n, 1), np.int32)
+    num = ctypes.c_int32(0)
+    _native.check(_native.lib().qldpc_serial_layers(c.m, c.n, _np_ptr(rp), _np_ptr(ci), _np_ptr(layer),
+                                                    ctypes.byref(num)), "qldpc_serial_layers")
+    return layer[:c.n], int(num.value)
+
+
+def serial_decode_host(H, channel_probs, max_iter, synd, ms_scaling_factor=0.625, precision: int = 64,
+                       threads: int = 0):
+    """``qldpc_serial_decode_host``: the serial-schedule min-sum law in plain C++ on host memory (no
+    GPU, any graph): ``synd`` [B, m] -> (corr [B, n] int64, iters [B], converged [B] bool, posteriors
+    [B, n] float64)."""
+    c = H if isinstance(H, CSR) else CSR.from_dense(H)
+    s = _syndromes(synd, c.m)
+    B = s.shape[0]
+    probs = _channel_probs(channel_probs, c.n)
+    rp = np.ascontiguousarray(c.row_ptr, dtype=np.int32)
+    ci = np.ascontiguousarray(c.col_idx, dtype=np.int32)
+    corr = np.zeros((B, c.n), np.uint8)
+    iters = np.zeros(B, np.int32)
+    conv = np.zeros(B, np.uint8)
+    post = np.zeros((B, c.n), np.float64)
+    _native.check(_native.lib().qldpc_serial_decode_host(
+        c.m, c.n, _np_ptr(rp), _np_ptr(ci), _np_ptr(probs), int(max_iter), float(ms_scaling_factor), int(precision),
+        _np_ptr(s), _np_ptr(corr), _np_ptr(iters), _np_ptr(conv), _np_ptr(post), B, int(threads)),
+        "qldpc_serial_decode_host")
+    return corr.astype(np.int64), iters, conv.astype(bool), post
 
 
 def sample_errors(n, px, py, pz, seed, shot_begin, shot_count, uniforms=None, device: int | None = None,

@@ -173,6 +173,10 @@ def _final_round_bp(decoder):
     """DeviceBP of a final-round decoder: an engine BPDecoder, or a BPOSD_Decoder whose OSD
     runs on the GPU (its soft BP then feeds qldpc_phenl_set_final_osd)."""
     if _is_bposd(decoder):
+        # (the device final round takes engine 1's posteriors: a serial-schedule BP+OSD decoder keeps
+        # the per-sample loop, which decodes through the decoder itself)
+        if getattr(decoder.decoder, "schedule", "parallel") != "parallel":
+            return None
         return decoder.decoder if getattr(decoder, "gpu_osd", None) is not None else None
     return _engine_bp(decoder)
 
@@ -245,6 +249,11 @@ class _ShotStream:
     def _lazy_seed(self):
         if self.seed is None:
             self.seed = random.getrandbits(64)
+
+    def rewind_shots(self, offset: int = 0):
+        """The next run starts at global shot ``offset`` again: with a fixed ``seed`` it redraws the
+        same samples (several configurations measured on the same errors, tools/schedule_compare.py)."""
+        self._shot_offset = int(offset)
 
     def _next_shard(self, count):
         """This rank's ``(begin, count)`` of the next ``count`` global shots; advances the offset."""
@@ -434,8 +443,9 @@ class CodeSimulator_DataError(_ShotStream):
 
             self._bposd_dev = False
             # the fused kernel is min-sum: product-sum BP+OSD decoders keep the host-assisted loop
-            if any(d.decoder.bp_method != 1 for d, need in ((self.decoder_x, need_x), (self.decoder_z, need_z))
-                   if need):
+            # and runs the flooding schedule: a serial BP+OSD decoder would otherwise be rebuilt as flooding
+            if any(d.decoder.bp_method != 1 or getattr(d.decoder, "schedule", "parallel") != "parallel"
+                   for d, need in ((self.decoder_x, need_x), (self.decoder_z, need_z)) if need):
                 return None
             bx = fast(self.decoder_x) if need_x else None
             # one fused kernel serves both sectors: the Z sector takes the X sector's geometry
@@ -983,6 +993,8 @@ class CodeSimulator_Circuit_SpaceTime(_CircuitBase):
             return None
         d2 = self.decoder2_z
         if _is_bposd(d2):
+            if getattr(d2.decoder, "schedule", "parallel") != "parallel":
+                return None  # the device loop's OSD stage takes engine 1's posteriors
             osd = getattr(d2, "gpu_osd", None) or d2.osd
             return b1, d2.decoder, osd
         b2 = _engine_bp(d2)
@@ -1107,6 +1119,8 @@ class CodeSimulator_Circuit(_CircuitBase):
         else:
             return None
         if isinstance(d2, BPOSD_Decoder):
+            if getattr(d2.decoder, "schedule", "parallel") != "parallel":
+                return None  # the device loop's OSD stage takes engine 1's posteriors
             return b1, fm, d2.decoder, (getattr(d2, "gpu_osd", None) or d2.osd)
         if isinstance(d2, BPDecoder) and _engine_bp(d2) is not None:
             return b1, fm, d2.decoder, None
