@@ -441,6 +441,64 @@ int qldpc_serial_decode_host(int32_t m, int32_t n, const int32_t *row_ptr, const
                              int32_t precision, const uint8_t *synd, uint8_t *corr, int32_t *iters, uint8_t *conv,
                              double *post, int64_t B, int32_t threads);
 
+/*
+ * Side priors: per-syndrome, per-variable priors selected by a byte, for X/Z-correlated decoding (bposd's
+ * css_decode_sim(channel_update="x->z" | "z->x")): one sector is decoded first, and the other sector's
+ * decoder is given, per shot and qubit, the prior conditioned on the first decoder's decision.
+ * THE LAW.  A decoder of engine 7 or 8 may carry two probability tables p0[n], p1[n], every entry
+ * finite and strictly inside (0, 1).  A side decode takes, beside the syndromes, d_side: uint8 [B][n],
+ * of which only bit 0 is read (0xFE counts as 0, 0x03 as 1).  For syndrome b and variable j,
+ *   L0_j = (T) log((1 - q) / q),  q = (side[b][j] & 1) ? p1[j] : p0[j],
+ * computed on the host in double with libm and cast to T, exactly as the plain handle's table.  Everything
+ * else is the engine's law above with that L0.  Engine 7: M_j <- L0_j; bias_j = ((T)1 - gam) L0_j + gam
+ * M_j; the solution weights wq_j = (int64) floor(L0_j(double) 2^32 + 0.5) come from the same selected
+ * prior (two integer weight tables).  Engine 8: the start value of b2c, and temp = L0_j in the variable
+ * pass.  q = 0.5 gives L0 = +0, and the decision rule temp <= 0 -> 1 stays as it is.  A side decode with
+ * side = 0 everywhere and p0 = channel_probs is the plain decode, bit for bit; with side = 1 everywhere it
+ * is the plain decode of a handle built on p1.
+ *
+ * qldpc_bp_set_side_probs: engines 7 and 8 only (QLDPC_ENOTSUP otherwise); QLDPC_EINVAL for an entry
+ * outside (0, 1) or non-finite; may be called again to replace the tables; touches neither the handle's
+ * ordinary priors nor any other entry point's result, nor qldpc_bp_geometry.
+ * qldpc_bp_decode_batch_side: qldpc_bp_decode_batch with d_side; QLDPC_EINVAL when no side tables are
+ * set.  No soft output.  The kernels read each side byte once per syndrome and keep its bit in bit 1 of
+ * the decision byte the decode already holds in LDS, so a side decode runs on the plain decode's LDS
+ * image and workgroup width (qldpc_bp_geometry reports one geometry for both; the persistent grid of a
+ * side decode is the side variant's own residency, at most the plain grid), and its variable pass
+ * issues the same single global load for the prior, from a two-row table.
+ * qldpc_relay_decode_host_side / qldpc_serial_decode_host_side: the law in plain C++ on host memory;
+ * the arguments of qldpc_relay_decode_host / qldpc_serial_decode_host with p0, p1, side [B][n] in the
+ * place of channel_probs (the serial form without the posteriors).
+ */
+int qldpc_bp_set_side_probs(qldpc_bp *bp, const double *p0, const double *p1);
+int qldpc_bp_decode_batch_side(qldpc_bp *bp, const uint8_t *d_synd, const uint8_t *d_side, uint8_t *d_corr,
+                               int32_t *d_iters, uint8_t *d_conv, int64_t B, void *stream);
+int qldpc_relay_decode_host_side(int32_t m, int32_t n, const int32_t *row_ptr, const int32_t *col_idx,
+                                 const double *p0, const double *p1, const uint8_t *side, int32_t pre_iter,
+                                 double pre_gamma, int32_t num_legs, int32_t leg_iter, double gamma_lo,
+                                 double gamma_hi, int32_t stop_nconv, uint64_t gamma_seed, double ms_scaling_factor,
+                                 int32_t precision, const uint8_t *synd, uint8_t *corr, int32_t *iters, uint8_t *conv,
+                                 int32_t *nsol, int64_t B, int32_t threads);
+int qldpc_serial_decode_host_side(int32_t m, int32_t n, const int32_t *row_ptr, const int32_t *col_idx,
+                                  const double *p0, const double *p1, const uint8_t *side, int32_t max_iter,
+                                  double ms_scaling_factor, int32_t precision, const uint8_t *synd, uint8_t *corr,
+                                  int32_t *iters, uint8_t *conv, int64_t B, int32_t threads);
+
+/*
+ * X/Z-correlated decoding in the staged data-error shot loop.  direction: 0 = off, 1 = "x->z", 2 =
+ * "z->x".  The X sector is the hz decoder of X components (dec_x), the Z sector the hx decoder (dec_z).
+ * Staged handles only (QLDPC_ENOTSUP otherwise; engine-7 and engine-8 decoders land there and
+ * qldpc_mc_create_staged forces it); both sector decoders and side tables on the second one are needed
+ * (QLDPC_EINVAL otherwise).  With a direction set, qldpc_mc_launch, qldpc_mc_run and
+ * qldpc_mc_launch_weight decode the direction's first sector, keep its [B][n] corrections as the side
+ * bytes, and decode the second sector with qldpc_bp_decode_batch_side.  Both sectors are then always
+ * decoded and their iteration counters tallied, whatever logical_mode; the failure tally (and the
+ * per-shot fail bits and sector_fail) follows logical_mode as without a direction.  Sampling, shot
+ * keying and the layout of every per-shot output are unchanged.  A handle with a direction set rejects
+ * qldpc_mc_set_osd, and a handle with an OSD stage rejects a direction: QLDPC_ENOTSUP.
+ */
+int qldpc_mc_set_channel_update(qldpc_mc *mc, int32_t direction);
+
 /* BP+OSD in the fused shot loop (bposd_decoder per sector, src/Decoders.py:26-41, inside
  * _single_run, src/Simulators.py:117-168): after qldpc_mc_set_osd, qldpc_mc_launch captures
  * every decode that reaches max_iter (its last-iteration posteriors, syndrome and sampled

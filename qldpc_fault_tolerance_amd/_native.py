@@ -36,6 +36,8 @@ EXPORTED = [
     "qldpc_sample_errors_weight_host",
     "qldpc_bp_create_relay", "qldpc_relay_gammas", "qldpc_relay_decode_host",
     "qldpc_bp_create_serial", "qldpc_serial_layers", "qldpc_serial_decode_host",
+    "qldpc_bp_set_side_probs", "qldpc_bp_decode_batch_side", "qldpc_relay_decode_host_side",
+    "qldpc_serial_decode_host_side", "qldpc_mc_set_channel_update",
 ]
 BUILD_EXPERIMENTAL = 1  # qldpc_build_flags(): the measured-and-not-kept kernel families are compiled in
 COMM_ID_BYTES = 128
@@ -251,6 +253,18 @@ def _declare(L):
     L.qldpc_serial_decode_host.restype = ctypes.c_int
     L.qldpc_serial_decode_host.argtypes = [_i32, _i32, _vp, _vp, _vp, _i32, _dbl, _i32, _vp, _vp, _vp, _vp, _vp, _i64,
                                            _i32]
+    L.qldpc_bp_set_side_probs.restype = ctypes.c_int
+    L.qldpc_bp_set_side_probs.argtypes = [_vp, _vp, _vp]
+    L.qldpc_bp_decode_batch_side.restype = ctypes.c_int
+    L.qldpc_bp_decode_batch_side.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]
+    L.qldpc_relay_decode_host_side.restype = ctypes.c_int
+    L.qldpc_relay_decode_host_side.argtypes = ([_i32, _i32, _vp, _vp, _vp, _vp, _vp] + relay +
+                                               [_vp, _vp, _vp, _vp, _vp, _i64, _i32])
+    L.qldpc_serial_decode_host_side.restype = ctypes.c_int
+    L.qldpc_serial_decode_host_side.argtypes = [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _dbl, _i32, _vp, _vp, _vp,
+                                                _vp, _i64, _i32]
+    L.qldpc_mc_set_channel_update.restype = ctypes.c_int
+    L.qldpc_mc_set_channel_update.argtypes = [_vp, _i32]
 
 
 def lib():

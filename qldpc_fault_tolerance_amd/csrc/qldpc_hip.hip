@@ -1708,7 +1708,7 @@ int qldpc_bp_destroy(qldpc_bp* bp) {
   if (bp->bp1) qldpc_firstmin_destroy(bp->bp1);
   for (DevBuf* d : {&bp->vchk, &bp->llr, &bp->rdeg, &bp->rowtab, &bp->perm, &bp->rperm, &bp->work, &bp->ps_rp, &bp->ps_ci, &bp->ps_cp,
                     &bp->ps_ce, &bp->ps_ws, &bp->h_rp, &bp->h_rcol, &bp->h_rcpos, &bp->h_cp, &bp->h_crpos, &bp->h_ws,
-                    &bp->rl_gam, &bp->rl_wq, &bp->sr_cr, &bp->sr_ord, &bp->sr_lp})
+                    &bp->rl_gam, &bp->rl_wq, &bp->sr_cr, &bp->sr_ord, &bp->sr_lp, &bp->side_llr, &bp->side_wq})
     d->release();
   delete bp;
   return 0;
@@ -1824,6 +1824,44 @@ int qldpc_bp_set_channel_probs(qldpc_bp* bp, const double* channel_probs) {
   if (rc) return rc;
   bp1_prepare(bp);  // rebuilt from the new priors
   return 0;
+}
+
+// Side priors of an engine-7 / engine-8 decoder: the two-row tables qldpc_bp_decode_batch_side selects
+// from per syndrome and variable.  The handle's ordinary priors and every other entry point are untouched.
+int qldpc_bp_set_side_probs(qldpc_bp* bp, const double* p0, const double* p1) {
+  if (!bp || ((!p0 || !p1) && bp->g->n > 0)) return set_err(QLDPC_EINVAL, "NULL argument");
+  if (bp->route.engine != 7 && bp->route.engine != 8)
+    return set_err(QLDPC_ENOTSUP, "side priors need a Relay-BP (engine 7) or serial-schedule (engine 8) decoder");
+  if (int rc = side_probs_check(bp->g->n, p0, p1)) return rc;
+  QLDPC_HIP(hipSetDevice(bp->g->device));
+  // (the copies are synchronous: a side decode already queued has read its tables before they change
+  // only if the caller synchronised, as for qldpc_bp_set_channel_probs)
+  const int rc = bp->route.engine == 7 ? relay_upload_side(bp, p0, p1) : serial_upload_side(bp, p0, p1);
+  if (rc) return rc;
+  // a side decode's persistent grid: what the side variant keeps resident on the plain variant's image
+  // (it may need a few more registers), never more than the workspace has slices for
+  const void* kern = bp->route.engine == 7 ? relay_kernel_ptr(bp->route.precision, bp->rl_idx, true)
+                                           : serial_kernel_ptr(bp->route.precision, bp->sr_idx, true);
+  int nb = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, bp->route.TB, bp->route.lds_bytes) != hipSuccess) nb = 1;
+  bp->side_grid = std::min<long long>(bp->ps_grid, (long long)std::max(1, nb) * bp->cus);
+  bp->side_set = true;
+  return 0;
+}
+
+int qldpc_bp_decode_batch_side(qldpc_bp* bp, const uint8_t* d_synd, const uint8_t* d_side, uint8_t* d_corr,
+                               int32_t* d_iters, uint8_t* d_conv, int64_t B, void* stream) {
+  if (!bp || (B > 0 && (!d_synd || !d_corr))) return set_err(QLDPC_EINVAL, "NULL argument");
+  if (bp->route.engine != 7 && bp->route.engine != 8)
+    return set_err(QLDPC_ENOTSUP, "a side decode needs a Relay-BP (engine 7) or serial-schedule (engine 8) decoder");
+  if (!bp->side_set) return set_err(QLDPC_EINVAL, "no side priors set (qldpc_bp_set_side_probs)");
+  if (B > 0 && !d_side && bp->g->n > 0) return set_err(QLDPC_EINVAL, "NULL side bytes");
+  if (B <= 0) return B < 0 ? set_err(QLDPC_EINVAL, "B < 0") : 0;
+  QLDPC_HIP(hipSetDevice(bp->g->device));
+  if (bp->g->n == 0) d_side = nullptr;  // no variable selects anything
+  if (bp->route.engine == 7)
+    return relay_decode_launch(bp, d_synd, d_corr, d_iters, d_conv, B, (hipStream_t)stream, d_side);
+  return serial_decode_launch(bp, d_synd, d_corr, d_iters, d_conv, nullptr, B, (hipStream_t)stream, d_side);
 }
 
 int qldpc_bp_degree3_slots(const qldpc_bp* bp, int32_t* d3k) {
@@ -2158,8 +2196,34 @@ int qldpc_mc_create(qldpc_bp* dec_x, const qldpc_graph* logical_x, qldpc_bp* dec
   return 0;
 }
 
+// X/Z-correlated decoding on a staged handle: the first sector's corrections are the side bytes of
+// the second sector's decode (qldpc_bp_decode_batch_side).  1 = x->z (hz decoder first), 2 = z->x.
+int qldpc_mc_set_channel_update(qldpc_mc* mc, int32_t direction) {
+  if (!mc) return set_err(QLDPC_EINVAL, "NULL mc");
+  if (direction < 0 || direction > 2) return set_err(QLDPC_EINVAL, "direction must be 0 (off), 1 (x->z) or 2 (z->x)");
+  if (!mc->staged) return set_err(QLDPC_ENOTSUP, "channel update needs a staged handle (qldpc_mc_create_staged)");
+  if (mc->osd[0] || mc->osd[1]) return set_err(QLDPC_ENOTSUP, "channel update does not run with the BP+OSD stage");
+  if (direction == 0) {
+    mc->chan_dir = 0;
+    return 0;
+  }
+  if (!mc->dec[0] || !mc->dec[1]) return set_err(QLDPC_EINVAL, "channel update needs both sector decoders");
+  const qldpc_bp* second = mc->dec[direction == 1 ? 1 : 0];
+  if (!second->side_set)
+    return set_err(QLDPC_EINVAL, "channel update needs side priors on the second sector's decoder "
+                                 "(qldpc_bp_set_side_probs)");
+  if (!mc->s_side.p) {
+    QLDPC_HIP(hipSetDevice(second->g->device));
+    if (int rc = mc->s_side.alloc(std::max<size_t>(1, (size_t)second->g->n * (size_t)mc->sbatch))) return rc;
+  }
+  mc->chan_dir = direction;
+  return 0;
+}
+
 int qldpc_mc_set_osd(qldpc_mc* mc, qldpc_osd_gpu* osd_x, qldpc_osd_gpu* osd_z) {
   if (!mc) return set_err(QLDPC_EINVAL, "NULL mc");
+  if (mc->chan_dir && (osd_x || osd_z))
+    return set_err(QLDPC_ENOTSUP, "BP+OSD does not run on a handle with a channel update direction set");
   qldpc_osd_gpu* o[2] = {osd_x, osd_z};
   for (int q = 0; q < 2; ++q) {
     if (!o[q]) continue;

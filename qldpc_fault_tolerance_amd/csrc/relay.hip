@@ -82,9 +82,10 @@ struct RelayArgs {
   const int32_t* ci;     // CSR columns (ascending) [E]
   const int32_t* cp;     // CSC column pointers [n+1]
   const int32_t* ce;     // CSC: edge ids (row-major numbering), rows ascending [E]
-  const void* llr;       // T [n]: L0
+  const void* llr;       // T [n]: L0 (a side decode: T [2][n], the rows of p0 and p1)
   const void* gam;       // T [num_legs + 1][n]
-  const long long* wq;   // [n] integer solution weights
+  const long long* wq;   // [n] integer solution weights (a side decode: [2][n])
+  const uint8_t* side;   // [B][n], bit 0 selects the prior's row (a side decode), else NULL
   void* ws;              // HBM message workspace (T [grid][2E]) or NULL (messages in LDS)
   const uint8_t* synd;   // [B][m]
   uint8_t* corr;         // [B][n]
@@ -100,7 +101,11 @@ struct RelayArgs {
 // I = int32_t walks the CSR / CSC in global memory: every step of a row or column walk then waits
 // on a dependent global load (index -> message address), 1.27x the time per iteration on
 // hgp_34_n1600; the staged copy is made once per workgroup, not per syndrome.
-template <typename T, typename I>
+// SIDE (qldpc_bp_decode_batch_side): variable j of syndrome b takes its prior and its solution weight
+// from row side[b][j] & 1 of the two-row tables.  The bit is read once per syndrome into bit 1 of
+// dec[j] (and travels into best[j] with it), so the image keeps its size and the variable pass still
+// issues one global load for its prior; every reader of dec / best masks bit 0.
+template <typename T, typename I, bool SIDE>
 __global__ void __launch_bounds__(kRelayMaxThreads) relay_kernel(RelayArgs A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, TB = blockDim.x;
@@ -146,12 +151,23 @@ __global__ void __launch_bounds__(kRelayMaxThreads) relay_kernel(RelayArgs A) {
   }
   const T* L0 = static_cast<const T*>(A.llr);
   const T sentinel = Sentinel<T>::v;
+  // the prior of variable j under the side bit its own thread keeps in dec[j]
+  auto prior = [&](int j) -> T {
+    if constexpr (SIDE)
+      return L0[(size_t)(dec[j] >> 1) * n + j];
+    else
+      return L0[j];
+  };
   for (long long b = blockIdx.x; b < A.B; b += gridDim.x) {
     // every per-syndrome word starts afresh: M, the flags, the weight word; nsol / bestW are registers
+    // (SIDE: and the side bit of every variable, before its prior is first read)
     for (int i = tid; i < m; i += TB) syn[i] = A.synd[b * m + i] & 1;
     for (int j = tid; j < n; j += TB) {
-      M[j] = L0[j];
-      dec[j] = 0;
+      if constexpr (SIDE)
+        dec[j] = (uint8_t)((A.side[b * n + j] & 1) << 1);
+      else
+        dec[j] = 0;
+      M[j] = prior(j);
       best[j] = 0;
     }
     if (tid == 0) {
@@ -165,7 +181,7 @@ __global__ void __launch_bounds__(kRelayMaxThreads) relay_kernel(RelayArgs A) {
       const int Tr = r == 0 ? A.pre_iter : A.leg_iter;
       const T* gam = static_cast<const T*>(A.gam) + (size_t)r * n;
       for (int j = tid; j < n; j += TB) {
-        const T bias = relay_bias<T>(gam[j], L0[j], M[j]);
+        const T bias = relay_bias<T>(gam[j], prior(j), M[j]);
         for (int k = cp[j]; k < cp[j + 1]; ++k) b2c[ce[k]] = bias;
       }
       __syncthreads();
@@ -202,14 +218,17 @@ __global__ void __launch_bounds__(kRelayMaxThreads) relay_kernel(RelayArgs A) {
         // variable pass, rows ascending: prefix sums from the bias, then suffix sums
         for (int j = tid; j < n; j += TB) {
           const int k0 = cp[j], k1 = cp[j + 1];
-          T temp = relay_bias<T>(gam[j], L0[j], M[j]);
+          T temp = relay_bias<T>(gam[j], prior(j), M[j]);
           for (int k = k0; k < k1; ++k) {
             const int e = ce[k];
             b2c[e] = temp;
             temp += c2b[e];
           }
           M[j] = temp;
-          dec[j] = temp <= 0 ? 1 : 0;
+          if constexpr (SIDE)
+            dec[j] = (uint8_t)((dec[j] & 2) | (temp <= 0 ? 1 : 0));
+          else
+            dec[j] = temp <= 0 ? 1 : 0;
           temp = (T)0;
           for (int k = k1 - 1; k >= k0; --k) {
             const int e = ce[k];
@@ -223,6 +242,7 @@ __global__ void __launch_bounds__(kRelayMaxThreads) relay_kernel(RelayArgs A) {
         for (int i = tid; i < m; i += TB) {
           uint32_t par = syn[i];
           for (int e = rp[i]; e < rp[i + 1]; ++e) par ^= dec[ci[e]];
+          if constexpr (SIDE) par &= 1u;
           if (par) *f = 1;
         }
         if (tid == 0) flag[(fc + 1) & 1] = 0;
@@ -238,8 +258,13 @@ __global__ void __launch_bounds__(kRelayMaxThreads) relay_kernel(RelayArgs A) {
       // a solution: its integer weight, summed in any order
       ++nsol;
       long long part = 0;
-      for (int j = tid; j < n; j += TB)
-        if (dec[j]) part += A.wq[j];
+      for (int j = tid; j < n; j += TB) {
+        if constexpr (SIDE) {
+          if (dec[j] & 1) part += A.wq[(size_t)(dec[j] >> 1) * n + j];
+        } else {
+          if (dec[j]) part += A.wq[j];
+        }
+      }
       if (part != 0) atomicAdd(wsum, (unsigned long long)part);
       __syncthreads();
       const long long W = (long long)*wsum;
@@ -251,7 +276,12 @@ __global__ void __launch_bounds__(kRelayMaxThreads) relay_kernel(RelayArgs A) {
       if (tid == 0) *wsum = 0ull;  // read again only after the barriers of another leg
       if (nsol >= A.stop_nconv) break;
     }
-    for (int j = tid; j < n; j += TB) A.corr[b * n + j] = nsol > 0 ? best[j] : dec[j];
+    for (int j = tid; j < n; j += TB) {
+      if constexpr (SIDE)
+        A.corr[b * n + j] = (nsol > 0 ? best[j] : dec[j]) & 1;
+      else
+        A.corr[b * n + j] = nsol > 0 ? best[j] : dec[j];
+    }
     if (tid == 0) {
       if (A.iters) A.iters[b] = total;
       if (A.conv) A.conv[b] = nsol > 0 ? 1 : 0;
@@ -423,12 +453,16 @@ void relay_decode_one(const HostGraph& g, const RelayParams& P, const RelayTable
   if (nsol_out) *nsol_out = nsol;
 }
 
+// probs1 / side non-NULL: the side law, each syndrome's L0 and weights selected from the tables of
+// probs (side bit 0) and probs1 (side bit 1) before the same per-syndrome routine runs
 template <typename T>
-void relay_decode_host_t(const HostGraph& g, const RelayParams& P, const double* probs, double pre_gamma, double lo,
-                         double hi, uint64_t seed, const uint8_t* synd, uint8_t* corr, int32_t* iters, uint8_t* conv,
-                         int32_t* nsol, int64_t B, int threads) {
-  RelayTables<T> tb;
+void relay_decode_host_t(const HostGraph& g, const RelayParams& P, const double* probs, const double* probs1,
+                         const uint8_t* side, double pre_gamma, double lo, double hi, uint64_t seed,
+                         const uint8_t* synd, uint8_t* corr, int32_t* iters, uint8_t* conv, int32_t* nsol, int64_t B,
+                         int threads) {
+  RelayTables<T> tb, tb1;
   relay_priors<T>(probs, g.n, tb.l0, tb.wq);
+  if (side) relay_priors<T>(probs1, g.n, tb1.l0, tb1.wq);
   relay_gam_table<T>(g.n, pre_gamma, P.num_legs, lo, hi, seed, tb.gam);
   std::atomic<int64_t> next(0);
   auto work = [&]() {
@@ -436,9 +470,21 @@ void relay_decode_host_t(const HostGraph& g, const RelayParams& P, const double*
     std::vector<T> b2c(E), c2b(E), M(n1);
     std::vector<int> sg(E);
     std::vector<uint8_t> dec(n1), best(n1);
-    for (int64_t b = next.fetch_add(1); b < B; b = next.fetch_add(1))
-      relay_decode_one<T>(g, P, tb, synd + (size_t)b * g.m, corr + (size_t)b * g.n, iters ? iters + b : nullptr,
-                          conv ? conv + b : nullptr, nsol ? nsol + b : nullptr, b2c, c2b, sg, M, dec, best);
+    RelayTables<T> sel;
+    if (side) sel = tb;
+    for (int64_t b = next.fetch_add(1); b < B; b = next.fetch_add(1)) {
+      if (side) {
+        const uint8_t* sb = side + (size_t)b * g.n;
+        for (int j = 0; j < g.n; ++j) {
+          const RelayTables<T>& from = (sb[j] & 1) ? tb1 : tb;
+          sel.l0[j] = from.l0[j];
+          sel.wq[j] = from.wq[j];
+        }
+      }
+      relay_decode_one<T>(g, P, side ? sel : tb, synd + (size_t)b * g.m, corr + (size_t)b * g.n,
+                          iters ? iters + b : nullptr, conv ? conv + b : nullptr, nsol ? nsol + b : nullptr, b2c, c2b,
+                          sg, M, dec, best);
+    }
   };
   const int nt = (int)std::max<int64_t>(1, std::min<int64_t>(threads, B));
   if (nt == 1) {
@@ -475,12 +521,19 @@ int relay_threads(size_t lds_bytes, int m, int n) {
   return tb;
 }
 
-const void* relay_kernel_ptr(int precision, bool lds_index) {
+const void* relay_kernel_ptr(int precision, bool lds_index, bool side) {
+  if (side) {
+    if (lds_index)
+      return precision == 32 ? reinterpret_cast<const void*>(&relay_kernel<float, uint16_t, true>)
+                             : reinterpret_cast<const void*>(&relay_kernel<double, uint16_t, true>);
+    return precision == 32 ? reinterpret_cast<const void*>(&relay_kernel<float, int32_t, true>)
+                           : reinterpret_cast<const void*>(&relay_kernel<double, int32_t, true>);
+  }
   if (lds_index)
-    return precision == 32 ? reinterpret_cast<const void*>(&relay_kernel<float, uint16_t>)
-                           : reinterpret_cast<const void*>(&relay_kernel<double, uint16_t>);
-  return precision == 32 ? reinterpret_cast<const void*>(&relay_kernel<float, int32_t>)
-                         : reinterpret_cast<const void*>(&relay_kernel<double, int32_t>);
+    return precision == 32 ? reinterpret_cast<const void*>(&relay_kernel<float, uint16_t, false>)
+                           : reinterpret_cast<const void*>(&relay_kernel<double, uint16_t, false>);
+  return precision == 32 ? reinterpret_cast<const void*>(&relay_kernel<float, int32_t, false>)
+                         : reinterpret_cast<const void*>(&relay_kernel<double, int32_t, false>);
 }
 
 int relay_check_params(int64_t n, int32_t pre_iter, double pre_gamma, int32_t num_legs, int32_t leg_iter,
@@ -505,6 +558,33 @@ int relay_upload_priors(qldpc_bp* bp) {
   return 0;
 }
 
+// the two-row L0 and weight tables of a side decode (qldpc_bp_set_side_probs): row 0 from p0, row 1 from p1
+int relay_upload_side(qldpc_bp* bp, const double* p0, const double* p1) {
+  const int n = bp->g->n;
+  const size_t ts = bp->route.precision == 32 ? 4 : 8;
+  int rc;
+  if (!bp->side_llr.p && (rc = bp->side_llr.alloc(std::max<size_t>(1, (size_t)2 * n) * ts))) return rc;
+  if (!bp->side_wq.p && (rc = bp->side_wq.alloc(std::max<size_t>(1, (size_t)2 * n) * 8))) return rc;
+  const double* rows[2] = {p0, p1};
+  for (int r = 0; r < 2 && n; ++r) {
+    std::vector<long long> wq;
+    if (bp->route.precision == 32) {
+      std::vector<float> l0;
+      relay_priors<float>(rows[r], n, l0, wq);
+      QLDPC_HIP(hipMemcpy(static_cast<float*>(bp->side_llr.p) + (size_t)r * n, l0.data(), (size_t)n * 4,
+                          hipMemcpyHostToDevice));
+    } else {
+      std::vector<double> l0;
+      relay_priors<double>(rows[r], n, l0, wq);
+      QLDPC_HIP(hipMemcpy(static_cast<double*>(bp->side_llr.p) + (size_t)r * n, l0.data(), (size_t)n * 8,
+                          hipMemcpyHostToDevice));
+    }
+    QLDPC_HIP(hipMemcpy(static_cast<long long*>(bp->side_wq.p) + (size_t)r * n, wq.data(), (size_t)n * 8,
+                        hipMemcpyHostToDevice));
+  }
+  return 0;
+}
+
 // the gamma table of bp's relay parameters, in T, on the device
 int relay_upload_gammas(qldpc_bp* bp) {
   const int n = bp->g->n, R = bp->rl_legs;
@@ -522,17 +602,26 @@ int relay_upload_gammas(qldpc_bp* bp) {
   return 0;
 }
 
+template <typename T, typename I>
+static void relay_launch(const RelayArgs& a, dim3 grid, dim3 block, size_t lds, hipStream_t stream) {
+  if (a.side)
+    hipLaunchKernelGGL((relay_kernel<T, I, true>), grid, block, lds, stream, a);
+  else
+    hipLaunchKernelGGL((relay_kernel<T, I, false>), grid, block, lds, stream, a);
+}
+
 int relay_decode_launch(const qldpc_bp* bp, const uint8_t* synd, uint8_t* corr, int32_t* iters, uint8_t* conv,
-                        int64_t B, hipStream_t stream) {
+                        int64_t B, hipStream_t stream, const uint8_t* side) {
   const qldpc_graph* g = bp->g;
   RelayArgs a;
   a.rp = static_cast<const int32_t*>(bp->ps_rp.p);
   a.ci = static_cast<const int32_t*>(bp->ps_ci.p);
   a.cp = static_cast<const int32_t*>(bp->ps_cp.p);
   a.ce = static_cast<const int32_t*>(bp->ps_ce.p);
-  a.llr = bp->llr.p;
+  a.llr = side ? bp->side_llr.p : bp->llr.p;
   a.gam = bp->rl_gam.p;
-  a.wq = static_cast<const long long*>(bp->rl_wq.p);
+  a.wq = static_cast<const long long*>(side ? bp->side_wq.p : bp->rl_wq.p);
+  a.side = side;
   a.ws = bp->ps_ws.p;
   a.synd = synd;
   a.corr = corr;
@@ -547,20 +636,21 @@ int relay_decode_launch(const qldpc_bp* bp, const uint8_t* synd, uint8_t* corr, 
   a.leg_iter = bp->rl_leg_iter;
   a.num_legs = bp->rl_legs;
   a.stop_nconv = bp->rl_stop;
-  // the workspace has one slice per workgroup of ps_grid: never launch more
-  const int grid = (int)std::max<long long>(1, std::min<long long>(B, bp->ps_grid));
+  // the workspace has one slice per workgroup of ps_grid: never launch more (side_grid <= ps_grid)
+  const int grid = (int)std::max<long long>(1, std::min<long long>(B, side ? bp->side_grid : bp->ps_grid));
   const dim3 g3(grid), b3(bp->route.TB);
   const size_t lds = bp->route.lds_bytes;
+  // (the side variants run on the plain variant's LDS image and workspace slices)
   if (bp->route.precision == 32) {
     if (bp->rl_idx)
-      hipLaunchKernelGGL((relay_kernel<float, uint16_t>), g3, b3, lds, stream, a);
+      relay_launch<float, uint16_t>(a, g3, b3, lds, stream);
     else
-      hipLaunchKernelGGL((relay_kernel<float, int32_t>), g3, b3, lds, stream, a);
+      relay_launch<float, int32_t>(a, g3, b3, lds, stream);
   } else {
     if (bp->rl_idx)
-      hipLaunchKernelGGL((relay_kernel<double, uint16_t>), g3, b3, lds, stream, a);
+      relay_launch<double, uint16_t>(a, g3, b3, lds, stream);
     else
-      hipLaunchKernelGGL((relay_kernel<double, int32_t>), g3, b3, lds, stream, a);
+      relay_launch<double, int32_t>(a, g3, b3, lds, stream);
   }
   QLDPC_HIP(hipGetLastError());
   return 0;
@@ -582,11 +672,13 @@ int qldpc_relay_gammas(int32_t n, double pre_gamma, int32_t num_legs, double gam
   return 0;
 }
 
-int qldpc_relay_decode_host(int32_t m, int32_t n, const int32_t* row_ptr, const int32_t* col_idx,
-                            const double* channel_probs, int32_t pre_iter, double pre_gamma, int32_t num_legs,
-                            int32_t leg_iter, double gamma_lo, double gamma_hi, int32_t stop_nconv,
-                            uint64_t gamma_seed, double ms_scaling_factor, int32_t precision, const uint8_t* synd,
-                            uint8_t* corr, int32_t* iters, uint8_t* conv, int32_t* nsol, int64_t B, int32_t threads) {
+// qldpc_relay_decode_host (p1 = side = NULL) and qldpc_relay_decode_host_side
+static int relay_decode_host_any(int32_t m, int32_t n, const int32_t* row_ptr, const int32_t* col_idx,
+                                 const double* channel_probs, const double* p1, const uint8_t* side, int32_t pre_iter,
+                                 double pre_gamma, int32_t num_legs, int32_t leg_iter, double gamma_lo, double gamma_hi,
+                                 int32_t stop_nconv, uint64_t gamma_seed, double ms_scaling_factor, int32_t precision,
+                                 const uint8_t* synd, uint8_t* corr, int32_t* iters, uint8_t* conv, int32_t* nsol,
+                                 int64_t B, int32_t threads) {
   if (m < 0 || n < 0 || !row_ptr || (!col_idx && row_ptr[m] > 0) || (!channel_probs && n > 0))
     return set_err(QLDPC_EINVAL, "bad graph or NULL argument");
   if (int rc = check_params(n, pre_iter, pre_gamma, num_legs, leg_iter, gamma_lo, gamma_hi, stop_nconv, precision))
@@ -624,12 +716,37 @@ int qldpc_relay_decode_host(int32_t m, int32_t n, const int32_t* row_ptr, const 
   }
   const RelayParams P{pre_iter, num_legs, leg_iter, stop_nconv, ms_scaling_factor};
   if (precision == 32)
-    relay_decode_host_t<float>(g, P, channel_probs, pre_gamma, gamma_lo, gamma_hi, gamma_seed, synd, corr, iters, conv,
-                               nsol, B, nt);
+    relay_decode_host_t<float>(g, P, channel_probs, p1, side, pre_gamma, gamma_lo, gamma_hi, gamma_seed, synd, corr,
+                               iters, conv, nsol, B, nt);
   else
-    relay_decode_host_t<double>(g, P, channel_probs, pre_gamma, gamma_lo, gamma_hi, gamma_seed, synd, corr, iters,
-                                conv, nsol, B, nt);
+    relay_decode_host_t<double>(g, P, channel_probs, p1, side, pre_gamma, gamma_lo, gamma_hi, gamma_seed, synd, corr,
+                                iters, conv, nsol, B, nt);
   return 0;
+}
+
+int qldpc_relay_decode_host(int32_t m, int32_t n, const int32_t* row_ptr, const int32_t* col_idx,
+                            const double* channel_probs, int32_t pre_iter, double pre_gamma, int32_t num_legs,
+                            int32_t leg_iter, double gamma_lo, double gamma_hi, int32_t stop_nconv,
+                            uint64_t gamma_seed, double ms_scaling_factor, int32_t precision, const uint8_t* synd,
+                            uint8_t* corr, int32_t* iters, uint8_t* conv, int32_t* nsol, int64_t B, int32_t threads) {
+  return relay_decode_host_any(m, n, row_ptr, col_idx, channel_probs, nullptr, nullptr, pre_iter, pre_gamma, num_legs,
+                               leg_iter, gamma_lo, gamma_hi, stop_nconv, gamma_seed, ms_scaling_factor, precision, synd,
+                               corr, iters, conv, nsol, B, threads);
+}
+
+int qldpc_relay_decode_host_side(int32_t m, int32_t n, const int32_t* row_ptr, const int32_t* col_idx,
+                                 const double* p0, const double* p1, const uint8_t* side, int32_t pre_iter,
+                                 double pre_gamma, int32_t num_legs, int32_t leg_iter, double gamma_lo, double gamma_hi,
+                                 int32_t stop_nconv, uint64_t gamma_seed, double ms_scaling_factor, int32_t precision,
+                                 const uint8_t* synd, uint8_t* corr, int32_t* iters, uint8_t* conv, int32_t* nsol,
+                                 int64_t B, int32_t threads) {
+  if (n > 0 && (!p0 || !p1)) return set_err(QLDPC_EINVAL, "NULL side prior table");
+  if (B > 0 && n > 0 && !side) return set_err(QLDPC_EINVAL, "NULL side bytes");
+  if (int rc = side_probs_check(n, p0, p1)) return rc;
+  // (n = 0: no variable selects anything, the plain routine serves)
+  return relay_decode_host_any(m, n, row_ptr, col_idx, p0, n > 0 ? p1 : nullptr, n > 0 ? side : nullptr, pre_iter,
+                               pre_gamma, num_legs, leg_iter, gamma_lo, gamma_hi, stop_nconv, gamma_seed,
+                               ms_scaling_factor, precision, synd, corr, iters, conv, nsol, B, threads);
 }
 
 }  // extern "C"

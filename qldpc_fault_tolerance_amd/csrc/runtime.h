@@ -10,6 +10,7 @@
 #define QLDPC_EXPERIMENTAL 0
 #endif
 
+#include <cmath>
 #include <string>
 #include <vector>
 
@@ -30,6 +31,15 @@ inline int set_err(int code, const std::string& msg) {
     hipError_t e_ = (x);                                                                    \
     if (e_ != hipSuccess) return qldpc_rt::set_err(QLDPC_EHIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
   } while (0)
+
+// the two prior tables of a side decode: every entry finite and strictly inside (0, 1)
+inline int side_probs_check(int64_t n, const double* p0, const double* p1) {
+  for (int64_t j = 0; j < n; ++j)
+    for (const double* p : {p0, p1})
+      if (!std::isfinite(p[j]) || !(p[j] > 0.0) || !(p[j] < 1.0))
+        return set_err(QLDPC_EINVAL, "side prior outside (0, 1) at variable " + std::to_string(j));
+  return 0;
+}
 
 struct DevBuf {
   void* p = nullptr;
@@ -99,6 +109,11 @@ struct qldpc_bp {
   int sr_layers = 0;
   bool sr_idx = false;   // the index arrays staged in LDS as 16-bit words
   bool sr_soft = false;  // the kernel keeps the posteriors (qldpc_bp_decode_batch_soft)
+  // engines 7 and 8, side priors (qldpc_bp_set_side_probs): L0 as T [2][n] (row 0 from p0, row 1 from
+  // p1) and, engine 7, the integer solution weights [2][n]; qldpc_bp_decode_batch_side reads them
+  qldpc_rt::DevBuf side_llr, side_wq;
+  bool side_set = false;
+  long long side_grid = 0;  // persistent grid of a side decode: the side variant's own residency, <= ps_grid
   // engine 6 (HBM-resident messages, bp_hbm.hip): uniform edge tables and the message workspace
   qldpc_rt::DevBuf h_rp, h_rcol, h_rcpos, h_cp, h_crpos, h_ws;
 };
@@ -124,6 +139,10 @@ struct qldpc_mc {
   qldpc_rt::DevBuf c_post[2], c_synd[2], c_err[2], c_shot[2], c_outw[2], c_n, c_fail;
   int sm[2] = {0, 0}, sk[2] = {0, 0};
   qldpc_rt::DevBuf s_rp[2], s_ci[2], s_cur[2], s_failw[2], s_D, s_det, s_corr, s_iters, s_conv;
+  // qldpc_mc_set_channel_update: 0 = off, 1 = x->z, 2 = z->x; s_side [sbatch][n] keeps the first
+  // sector's corrections as the side bytes of the second sector's decode
+  int chan_dir = 0;
+  qldpc_rt::DevBuf s_side;
 };
 
 
@@ -138,22 +157,25 @@ int ps_decode_launch(const qldpc_bp* bp, const uint8_t* synd, uint8_t* corr, int
 
 // engine 7 (relay.hip)
 size_t relay_lds_bytes(int precision, int m, int n, int E, bool lds_messages, bool lds_index);
-const void* relay_kernel_ptr(int precision, bool lds_index);
+const void* relay_kernel_ptr(int precision, bool lds_index, bool side = false);
 int relay_threads(size_t lds_bytes, int m, int n);
 int relay_check_params(int64_t n, int32_t pre_iter, double pre_gamma, int32_t num_legs, int32_t leg_iter,
                        double gamma_lo, double gamma_hi, int32_t stop_nconv, int32_t precision);
 int relay_upload_priors(qldpc_bp* bp);
 int relay_upload_gammas(qldpc_bp* bp);
+int relay_upload_side(qldpc_bp* bp, const double* p0, const double* p1);
+// side non-NULL: the side decode (uint8 [B][n], bit 0), on the handle's side tables
 int relay_decode_launch(const qldpc_bp* bp, const uint8_t* synd, uint8_t* corr, int32_t* iters, uint8_t* conv,
-                        int64_t B, hipStream_t stream);
+                        int64_t B, hipStream_t stream, const uint8_t* side = nullptr);
 
 // engine 8 (serial.hip)
 int serial_check_params(int64_t n, int32_t max_iter, int32_t precision);
-const void* serial_kernel_ptr(int precision, bool lds_index);
+const void* serial_kernel_ptr(int precision, bool lds_index, bool side = false);
 int serial_upload_priors(qldpc_bp* bp);
 int serial_prepare(qldpc_bp* bp, bool force_ws, bool allow_idx, int want_tb, int lds_max);
+int serial_upload_side(qldpc_bp* bp, const double* p0, const double* p1);
 int serial_decode_launch(const qldpc_bp* bp, const uint8_t* synd, uint8_t* corr, int32_t* iters, uint8_t* conv,
-                         double* post, int64_t B, hipStream_t stream);
+                         double* post, int64_t B, hipStream_t stream, const uint8_t* side = nullptr);
 
 // GPU OSD handle built on this graph? (osd.hip; qldpc_phenl_set_final_osd checks it)
 bool osd_gpu_matches(const qldpc_osd_gpu* o, const qldpc_graph* g);

@@ -94,7 +94,8 @@ struct SerialArgs {
   const int32_t* cr;    // CSC: rows [E]
   const int32_t* ord;   // the sweep order pi [n]
   const int32_t* lp;    // layer l = ord[lp[l] .. lp[l+1]) [layers + 1]
-  const void* llr;      // T [n]: L0
+  const void* llr;      // T [n]: L0 (a side decode: T [2][n], the rows of p0 and p1)
+  const uint8_t* side;  // [B][n], bit 0 selects the prior's row (a side decode), else NULL
   void* ws;             // HBM message workspace (T [grid][E]) or NULL (messages in LDS)
   const uint8_t* synd;  // [B][m]
   uint8_t* corr;        // [B][n]
@@ -109,7 +110,11 @@ struct SerialArgs {
 // LDS: [b2c: E x T when in LDS][post: n x T on a soft handle][flag: 2 x 4][dec: n][syn: m]
 //      [rp: m + 1][cp: n + 1][lp: layers + 1][ord: n][ci: E][ce: E][cr: E] as I = uint16_t when the
 //      graph's indices are staged; I = int32_t walks them in global memory.
-template <typename T, typename I>
+// SIDE (qldpc_bp_decode_batch_side): variable j of syndrome b takes its prior from row side[b][j] & 1
+// of the two-row table.  The bit is read once per syndrome into bit 1 of dec[j], so the image keeps
+// its size and the variable pass still issues one global load for its prior; every reader of dec
+// masks bit 0.
+template <typename T, typename I, bool SIDE>
 __global__ void __launch_bounds__(kSerialMaxThreads) serial_kernel(SerialArgs A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, TB = blockDim.x;
@@ -165,7 +170,17 @@ __global__ void __launch_bounds__(kSerialMaxThreads) serial_kernel(SerialArgs A)
   const T* L0 = static_cast<const T*>(A.llr);
   for (long long b = blockIdx.x; b < A.B; b += gridDim.x) {
     for (int i = tid; i < m; i += TB) syn[i] = A.synd[b * m + i] & 1;
-    for (int e = tid; e < E; e += TB) b2c[e] = L0[ci[e]];
+    if constexpr (SIDE) {
+      // the side bits of this syndrome replace the previous one's before any prior is read
+      const uint8_t* sb = A.side + b * n;
+      for (int j = tid; j < n; j += TB) dec[j] = (uint8_t)((sb[j] & 1) << 1);
+      for (int e = tid; e < E; e += TB) {
+        const int j = ci[e];
+        b2c[e] = L0[(size_t)(sb[j] & 1) * n + j];
+      }
+    } else {
+      for (int e = tid; e < E; e += TB) b2c[e] = L0[ci[e]];
+    }
     if (tid == 0) flag[0] = flag[1] = 0;
     int total = 0;
     bool converged = false;
@@ -177,7 +192,9 @@ __global__ void __launch_bounds__(kSerialMaxThreads) serial_kernel(SerialArgs A)
         for (int q = lp[l] + tid; q < q1; q += TB) {
           const int j = ord[q];
           const int k0 = cp[j], deg = cp[j + 1] - k0;
-          T temp = L0[j];
+          uint8_t sbit = 0;
+          if constexpr (SIDE) sbit = dec[j] & 2;
+          T temp = SIDE ? L0[(size_t)(sbit >> 1) * n + j] : L0[j];
           if (deg <= kSerialRegDeg) {
             T c[kSerialRegDeg], pre[kSerialRegDeg];
 #pragma unroll
@@ -221,7 +238,7 @@ __global__ void __launch_bounds__(kSerialMaxThreads) serial_kernel(SerialArgs A)
             temp = sum;
           }
           if (A.soft) pst[j] = temp;
-          dec[j] = temp <= 0 ? 1 : 0;
+          dec[j] = SIDE ? (uint8_t)(sbit | (temp <= 0 ? 1 : 0)) : (temp <= 0 ? 1 : 0);
         }
         __syncthreads();
       }
@@ -230,6 +247,7 @@ __global__ void __launch_bounds__(kSerialMaxThreads) serial_kernel(SerialArgs A)
       for (int i = tid; i < m; i += TB) {
         uint32_t par = syn[i];
         for (int e = rp[i]; e < rp[i + 1]; ++e) par ^= dec[ci[e]];
+        if constexpr (SIDE) par &= 1u;
         if (par) *f = 1;
       }
       if (tid == 0) flag[(total + 1) & 1] = 0;
@@ -245,7 +263,7 @@ __global__ void __launch_bounds__(kSerialMaxThreads) serial_kernel(SerialArgs A)
       }
     }
     for (int j = tid; j < n; j += TB) {
-      A.corr[b * n + j] = dec[j];
+      A.corr[b * n + j] = SIDE ? (dec[j] & 1) : dec[j];
       if (A.post) A.post[b * n + j] = (double)pst[j];
     }
     if (tid == 0) {
@@ -379,22 +397,32 @@ void serial_decode_one(const HostGraph& g, const std::vector<int32_t>& ord, cons
     for (int j = 0; j < n; ++j) post[j] = (double)pst[j];
 }
 
+// probs1 / side non-NULL: the side law, each syndrome's L0 selected from the tables of probs (side bit
+// 0) and probs1 (side bit 1) before the same per-syndrome routine runs
 template <typename T>
-void serial_decode_host_t(const HostGraph& g, const std::vector<int32_t>& ord, const double* probs, int max_iter,
-                          double alpha, const uint8_t* synd, uint8_t* corr, int32_t* iters, uint8_t* conv, double* post,
-                          int64_t B, int threads) {
-  std::vector<T> l0;
+void serial_decode_host_t(const HostGraph& g, const std::vector<int32_t>& ord, const double* probs,
+                          const double* probs1, const uint8_t* side, int max_iter, double alpha, const uint8_t* synd,
+                          uint8_t* corr, int32_t* iters, uint8_t* conv, double* post, int64_t B, int threads) {
+  std::vector<T> l0, l1;
   serial_priors<T>(probs, g.n, l0);
+  if (side) serial_priors<T>(probs1, g.n, l1);
   int maxdeg = 1;
   for (int j = 0; j < g.n; ++j) maxdeg = std::max(maxdeg, g.cp[j + 1] - g.cp[j]);
   std::atomic<int64_t> next(0);
   auto work = [&]() {
     std::vector<T> b2c((size_t)std::max(1, g.E)), c2b((size_t)maxdeg), pst((size_t)g.n + 1);
     std::vector<uint8_t> dec((size_t)g.n + 1);
-    for (int64_t b = next.fetch_add(1); b < B; b = next.fetch_add(1))
-      serial_decode_one<T>(g, ord, l0, max_iter, alpha, synd + (size_t)b * g.m, corr + (size_t)b * g.n,
+    std::vector<T> sel;
+    if (side) sel = l0;
+    for (int64_t b = next.fetch_add(1); b < B; b = next.fetch_add(1)) {
+      if (side) {
+        const uint8_t* sb = side + (size_t)b * g.n;
+        for (int j = 0; j < g.n; ++j) sel[j] = (sb[j] & 1) ? l1[j] : l0[j];
+      }
+      serial_decode_one<T>(g, ord, side ? sel : l0, max_iter, alpha, synd + (size_t)b * g.m, corr + (size_t)b * g.n,
                            iters ? iters + b : nullptr, conv ? conv + b : nullptr,
                            post ? post + (size_t)b * g.n : nullptr, b2c, c2b, pst, dec);
+    }
   };
   const int nt = (int)std::max<int64_t>(1, std::min<int64_t>(threads, B));
   if (nt == 1) {
@@ -417,7 +445,10 @@ size_t serial_lds(int precision, int m, int n, int E, int layers, bool soft, boo
 
 template <typename T, typename I>
 void launch(const SerialArgs& a, int grid, int tb, size_t lds, hipStream_t stream) {
-  hipLaunchKernelGGL((serial_kernel<T, I>), dim3(grid), dim3(tb), lds, stream, a);
+  if (a.side)
+    hipLaunchKernelGGL((serial_kernel<T, I, true>), dim3(grid), dim3(tb), lds, stream, a);
+  else
+    hipLaunchKernelGGL((serial_kernel<T, I, false>), dim3(grid), dim3(tb), lds, stream, a);
 }
 
 }  // namespace
@@ -426,12 +457,19 @@ namespace qldpc_rt {
 
 int serial_check_params(int64_t n, int32_t max_iter, int32_t precision) { return check_params(n, max_iter, precision); }
 
-const void* serial_kernel_ptr(int precision, bool lds_index) {
+const void* serial_kernel_ptr(int precision, bool lds_index, bool side) {
+  if (side) {
+    if (lds_index)
+      return precision == 32 ? reinterpret_cast<const void*>(&serial_kernel<float, uint16_t, true>)
+                             : reinterpret_cast<const void*>(&serial_kernel<double, uint16_t, true>);
+    return precision == 32 ? reinterpret_cast<const void*>(&serial_kernel<float, int32_t, true>)
+                           : reinterpret_cast<const void*>(&serial_kernel<double, int32_t, true>);
+  }
   if (lds_index)
-    return precision == 32 ? reinterpret_cast<const void*>(&serial_kernel<float, uint16_t>)
-                           : reinterpret_cast<const void*>(&serial_kernel<double, uint16_t>);
-  return precision == 32 ? reinterpret_cast<const void*>(&serial_kernel<float, int32_t>)
-                         : reinterpret_cast<const void*>(&serial_kernel<double, int32_t>);
+    return precision == 32 ? reinterpret_cast<const void*>(&serial_kernel<float, uint16_t, false>)
+                           : reinterpret_cast<const void*>(&serial_kernel<double, uint16_t, false>);
+  return precision == 32 ? reinterpret_cast<const void*>(&serial_kernel<float, int32_t, false>)
+                         : reinterpret_cast<const void*>(&serial_kernel<double, int32_t, false>);
 }
 
 int serial_upload_priors(qldpc_bp* bp) {
@@ -445,6 +483,29 @@ int serial_upload_priors(qldpc_bp* bp) {
     std::vector<double> l0;
     serial_priors<double>(bp->probs.data(), n, l0);
     QLDPC_HIP(hipMemcpy(bp->llr.p, l0.data(), (size_t)n * 8, hipMemcpyHostToDevice));
+  }
+  return 0;
+}
+
+// the two-row L0 table of a side decode (qldpc_bp_set_side_probs): row 0 from p0, row 1 from p1
+int serial_upload_side(qldpc_bp* bp, const double* p0, const double* p1) {
+  const int n = bp->g->n;
+  const size_t ts = bp->route.precision == 32 ? 4 : 8;
+  int rc;
+  if (!bp->side_llr.p && (rc = bp->side_llr.alloc(std::max<size_t>(1, (size_t)2 * n) * ts))) return rc;
+  const double* rows[2] = {p0, p1};
+  for (int r = 0; r < 2 && n; ++r) {
+    if (bp->route.precision == 32) {
+      std::vector<float> l0;
+      serial_priors<float>(rows[r], n, l0);
+      QLDPC_HIP(hipMemcpy(static_cast<float*>(bp->side_llr.p) + (size_t)r * n, l0.data(), (size_t)n * 4,
+                          hipMemcpyHostToDevice));
+    } else {
+      std::vector<double> l0;
+      serial_priors<double>(rows[r], n, l0);
+      QLDPC_HIP(hipMemcpy(static_cast<double*>(bp->side_llr.p) + (size_t)r * n, l0.data(), (size_t)n * 8,
+                          hipMemcpyHostToDevice));
+    }
   }
   return 0;
 }
@@ -514,7 +575,7 @@ int serial_prepare(qldpc_bp* bp, bool force_ws, bool allow_idx, int want_tb, int
 }
 
 int serial_decode_launch(const qldpc_bp* bp, const uint8_t* synd, uint8_t* corr, int32_t* iters, uint8_t* conv,
-                         double* post, int64_t B, hipStream_t stream) {
+                         double* post, int64_t B, hipStream_t stream, const uint8_t* side) {
   const qldpc_graph* g = bp->g;
   SerialArgs a;
   a.rp = static_cast<const int32_t*>(bp->ps_rp.p);
@@ -524,7 +585,8 @@ int serial_decode_launch(const qldpc_bp* bp, const uint8_t* synd, uint8_t* corr,
   a.cr = static_cast<const int32_t*>(bp->sr_cr.p);
   a.ord = static_cast<const int32_t*>(bp->sr_ord.p);
   a.lp = static_cast<const int32_t*>(bp->sr_lp.p);
-  a.llr = bp->llr.p;
+  a.llr = side ? bp->side_llr.p : bp->llr.p;
+  a.side = side;
   a.ws = bp->ps_ws.p;
   a.synd = synd;
   a.corr = corr;
@@ -539,8 +601,8 @@ int serial_decode_launch(const qldpc_bp* bp, const uint8_t* synd, uint8_t* corr,
   a.layers = bp->sr_layers;
   a.max_iter = bp->max_iter;
   a.soft = bp->sr_soft ? 1 : 0;
-  // the workspace has one slice per workgroup of ps_grid: never launch more
-  const int grid = (int)std::max<long long>(1, std::min<long long>(B, bp->ps_grid));
+  // the workspace has one slice per workgroup of ps_grid: never launch more (side_grid <= ps_grid)
+  const int grid = (int)std::max<long long>(1, std::min<long long>(B, side ? bp->side_grid : bp->ps_grid));
   const size_t lds = bp->route.lds_bytes;
   if (bp->route.precision == 32) {
     if (bp->sr_idx)
@@ -578,10 +640,11 @@ int qldpc_serial_layers(int32_t m, int32_t n, const int32_t* row_ptr, const int3
   return 0;
 }
 
-int qldpc_serial_decode_host(int32_t m, int32_t n, const int32_t* row_ptr, const int32_t* col_idx,
-                             const double* channel_probs, int32_t max_iter, double ms_scaling_factor, int32_t precision,
-                             const uint8_t* synd, uint8_t* corr, int32_t* iters, uint8_t* conv, double* post, int64_t B,
-                             int32_t threads) {
+// qldpc_serial_decode_host (p1 = side = NULL) and qldpc_serial_decode_host_side
+static int serial_decode_host_any(int32_t m, int32_t n, const int32_t* row_ptr, const int32_t* col_idx,
+                                  const double* channel_probs, const double* p1, const uint8_t* side, int32_t max_iter,
+                                  double ms_scaling_factor, int32_t precision, const uint8_t* synd, uint8_t* corr,
+                                  int32_t* iters, uint8_t* conv, double* post, int64_t B, int32_t threads) {
   if (int rc = check_csr(m, n, row_ptr, col_idx)) return rc;
   if (!channel_probs && n > 0) return set_err(QLDPC_EINVAL, "NULL channel_probs");
   if (int rc = check_params(n, max_iter, precision)) return rc;
@@ -603,10 +666,32 @@ int qldpc_serial_decode_host(int32_t m, int32_t n, const int32_t* row_ptr, const
     if (nt <= 0) nt = 1;
   }
   if (precision == 32)
-    serial_decode_host_t<float>(g, ord, channel_probs, max_iter, ms_scaling_factor, synd, corr, iters, conv, post, B, nt);
+    serial_decode_host_t<float>(g, ord, channel_probs, p1, side, max_iter, ms_scaling_factor, synd, corr, iters, conv,
+                                post, B, nt);
   else
-    serial_decode_host_t<double>(g, ord, channel_probs, max_iter, ms_scaling_factor, synd, corr, iters, conv, post, B, nt);
+    serial_decode_host_t<double>(g, ord, channel_probs, p1, side, max_iter, ms_scaling_factor, synd, corr, iters, conv,
+                                 post, B, nt);
   return 0;
+}
+
+int qldpc_serial_decode_host(int32_t m, int32_t n, const int32_t* row_ptr, const int32_t* col_idx,
+                             const double* channel_probs, int32_t max_iter, double ms_scaling_factor, int32_t precision,
+                             const uint8_t* synd, uint8_t* corr, int32_t* iters, uint8_t* conv, double* post, int64_t B,
+                             int32_t threads) {
+  return serial_decode_host_any(m, n, row_ptr, col_idx, channel_probs, nullptr, nullptr, max_iter, ms_scaling_factor,
+                                precision, synd, corr, iters, conv, post, B, threads);
+}
+
+int qldpc_serial_decode_host_side(int32_t m, int32_t n, const int32_t* row_ptr, const int32_t* col_idx,
+                                  const double* p0, const double* p1, const uint8_t* side, int32_t max_iter,
+                                  double ms_scaling_factor, int32_t precision, const uint8_t* synd, uint8_t* corr,
+                                  int32_t* iters, uint8_t* conv, int64_t B, int32_t threads) {
+  if (n > 0 && (!p0 || !p1)) return set_err(QLDPC_EINVAL, "NULL side prior table");
+  if (B > 0 && n > 0 && !side) return set_err(QLDPC_EINVAL, "NULL side bytes");
+  if (int rc = side_probs_check(n, p0, p1)) return rc;
+  // (n = 0: no variable selects anything, the plain routine serves)
+  return serial_decode_host_any(m, n, row_ptr, col_idx, p0, n > 0 ? p1 : nullptr, n > 0 ? side : nullptr, max_iter,
+                                ms_scaling_factor, precision, synd, corr, iters, conv, nullptr, B, threads);
 }
 
 }  // extern "C"

@@ -581,7 +581,7 @@ void staged_mc_release(qldpc_mc* mc) {
   for (int q = 0; q < 2; ++q) {
     mc->s_rp[q].release(); mc->s_ci[q].release(); mc->s_cur[q].release(); mc->s_failw[q].release();
   }
-  for (DevBuf* d : {&mc->s_D, &mc->s_det, &mc->s_corr, &mc->s_iters, &mc->s_conv}) d->release();
+  for (DevBuf* d : {&mc->s_D, &mc->s_det, &mc->s_corr, &mc->s_iters, &mc->s_conv, &mc->s_side}) d->release();
 }
 
 int staged_mc_prepare(qldpc_mc* mc, const qldpc_graph* logical_x, const qldpc_graph* logical_z) {
@@ -633,6 +633,10 @@ int staged_mc_launch(qldpc_mc* mc, double px, double py, double pz, uint64_t see
                      uint8_t* d_fail, uint8_t* d_err, uint8_t* d_corr, int32_t* d_iters, hipStream_t st,
                      const StagedWeight* fixed) {
   const bool need[2] = {logical_mode != 1, logical_mode != 0};
+  // channel update (qldpc_mc_set_channel_update): both sectors are decoded whatever the mode, the
+  // direction's first sector first, its corrections kept as the side bytes of the second's decode
+  const int dir = mc->chan_dir;
+  const int order[2] = {dir == 2 ? 1 : 0, dir == 2 ? 0 : 1};
   const qldpc_bp* d0 = mc->dec[0] ? mc->dec[0] : mc->dec[1];
   const int n = d0->g->n;
   auto* cnt = static_cast<unsigned long long*>(d_counters);
@@ -675,10 +679,13 @@ int staged_mc_launch(qldpc_mc* mc, double px, double py, double pz, uint64_t see
                          static_cast<const unsigned long long*>(mc->s_cur[1].p), d_err, c0, n, W, B);
       QLDPC_HIP(hipGetLastError());
     }
-    for (int q = 0; q < 2; ++q) {
-      if (!need[q]) continue;
+    for (int oq = 0; oq < 2; ++oq) {
+      const int q = order[oq];
+      if (!dir && !need[q]) continue;
       const int m = mc->sm[q];
       auto* cur = static_cast<unsigned long long*>(mc->s_cur[q].p);
+      // the first sector of a channel update decodes into the side buffer, the second reads it
+      uint8_t* corr = static_cast<uint8_t*>(dir && oq == 0 ? mc->s_side.p : mc->s_corr.p);
       hipLaunchKernelGGL(ph_syndrome, dim3(wgrid.x, (unsigned)m), dim3(kTile), 0, st,
                          static_cast<const int32_t*>(mc->s_rp[q].p), static_cast<const int32_t*>(mc->s_ci[q].p), cur,
                          nullptr, nullptr, static_cast<unsigned long long*>(mc->s_D.p), W, 0, -1);
@@ -687,22 +694,28 @@ int staged_mc_launch(qldpc_mc* mc, double px, double py, double pz, uint64_t see
                          static_cast<const unsigned long long*>(mc->s_D.p), static_cast<uint8_t*>(mc->s_det.p),
                          nullptr, 0, 0, c0, m, W, B);
       QLDPC_HIP(hipGetLastError());
-      int rc = qldpc_bp_decode_batch(mc->dec[q], static_cast<const uint8_t*>(mc->s_det.p),
-                                     static_cast<uint8_t*>(mc->s_corr.p), static_cast<int32_t*>(mc->s_iters.p),
-                                     static_cast<uint8_t*>(mc->s_conv.p), B, st);
+      int rc = dir && oq == 1
+                   ? qldpc_bp_decode_batch_side(mc->dec[q], static_cast<const uint8_t*>(mc->s_det.p),
+                                                static_cast<const uint8_t*>(mc->s_side.p), corr,
+                                                static_cast<int32_t*>(mc->s_iters.p),
+                                                static_cast<uint8_t*>(mc->s_conv.p), B, st)
+                   : qldpc_bp_decode_batch(mc->dec[q], static_cast<const uint8_t*>(mc->s_det.p), corr,
+                                           static_cast<int32_t*>(mc->s_iters.p),
+                                           static_cast<uint8_t*>(mc->s_conv.p), B, st);
       if (rc) return rc;
       hipLaunchKernelGGL(ph_iters, dim3((unsigned)((B + kTile - 1) / kTile)), dim3(kTile), 0, st,
                          static_cast<const int32_t*>(mc->s_iters.p), static_cast<const uint8_t*>(mc->s_conv.p), cnt, q,
                          B);
       QLDPC_HIP(hipGetLastError());
       if (d_corr)
-        QLDPC_HIP(hipMemcpy2DAsync(d_corr + (c0 * 2 + q) * n, (size_t)2 * n, mc->s_corr.p, (size_t)n, (size_t)n,
+        QLDPC_HIP(hipMemcpy2DAsync(d_corr + (c0 * 2 + q) * n, (size_t)2 * n, corr, (size_t)n, (size_t)n,
                                    (size_t)B, hipMemcpyDeviceToDevice, st));
       if (d_iters)
         QLDPC_HIP(hipMemcpy2DAsync(d_iters + c0 * 2 + q, 8, mc->s_iters.p, 4, 4, (size_t)B, hipMemcpyDeviceToDevice,
                                    st));
+      if (!need[q]) continue;  // (a channel update's sector outside the mode: decoded and tallied, not checked)
       hipLaunchKernelGGL(ph_fold, dim3((unsigned)((n + kTile - 1) / kTile), (unsigned)W), dim3(kTile), 0, st,
-                         static_cast<const uint8_t*>(mc->s_corr.p), cur, n, W, 1, n, n, B);
+                         static_cast<const uint8_t*>(corr), cur, n, W, 1, n, n, B);
       QLDPC_HIP(hipGetLastError());
       hipLaunchKernelGGL(ph_check, dim3(wgrid.x, (unsigned)(m + mc->sk[q])), dim3(kTile), 0, st,
                          static_cast<const int32_t*>(mc->s_rp[q].p), static_cast<const int32_t*>(mc->s_ci[q].p), cur,

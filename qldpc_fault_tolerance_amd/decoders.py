@@ -30,18 +30,51 @@ def _int_max_iter(max_iter, n):
     return mi if mi > 0 else n
 
 
+def channel_update_probs(px, py, pz, direction):
+    """The priors of X/Z-correlated decoding (bposd's ``channel_update``) for the Pauli channel
+    ``px : py : pz``: ``(p_first, p0, p1)`` = the first sector's marginal prior and the second
+    sector's priors conditioned on the first decoder's decision 0 / 1.  ``"x->z"``: first = X
+    components (``px + py``), ``p1 = P(z=1 | x=1) = py / (px + py)``, ``p0 = P(z=1 | x=0) = pz / (1 -
+    px - py)``; ``"z->x"`` symmetrically.  A value outside (0, 1) raises ``ValueError`` naming it."""
+    if direction not in ("x->z", "z->x"):
+        raise ValueError(f"direction must be 'x->z' or 'z->x', not {direction!r}")
+    px, py, pz = float(px), float(py), float(pz)
+    a, b = (px, pz) if direction == "x->z" else (pz, px)  # a: the first sector's own class, b: the second's
+    p_first = a + py
+    out = {"p_first": p_first,
+           "p0": b / (1.0 - a - py) if (1.0 - a - py) != 0.0 else math.inf,
+           "p1": py / (a + py) if (a + py) != 0.0 else math.nan}
+    for name, v in out.items():
+        if not (math.isfinite(v) and 0.0 < v < 1.0):
+            raise ValueError(f"channel update {direction} with (px, py, pz) = ({px}, {py}, {pz}): {name} = {v} "
+                             "is not inside (0, 1)")
+    return out["p_first"], out["p0"], out["p1"]
+
+
+def _set_side_probs(decoder, side_probs):
+    p0, p1 = side_probs
+    decoder.set_side_probs(p0, p1)
+
+
 class BPDecoder:
     """``BPDecoder(h, channel_probs, max_iter, bp_method, ms_scaling_factor)`` (``src/Decoders.py:77-90``).
 
     ``schedule="serial"`` (no reference counterpart; ``schedule="serial"`` of current ldpc) runs min-sum
     on the serial, variable-by-variable schedule (engine 8, ``qldpc_bp_create_serial``); the default
-    ``"parallel"`` is the reference's flooding schedule."""
+    ``"parallel"`` is the reference's flooding schedule.
+
+    ``side_probs=(p0, p1)`` makes the decoder side-capable: ``decode(synd, side)`` takes, per variable,
+    the prior ``p1`` where ``side`` is 1 and ``p0`` where it is 0 (X/Z-correlated decoding, the law in
+    include/qldpc_hip.h).  Min-sum only.  A flooding decoder is then built on engine 7 with ``pre_iter =
+    max_iter``, no memory and no legs, which the Relay law states is plain min-sum bit for bit; a
+    serial one on engine 8."""
 
     def __init__(self, h, channel_probs, max_iter, bp_method, ms_scaling_factor, precision: int = 64,
-                 device: int | None = None, vars_per_thread: int = 0, schedule: str = "parallel"):
-        from .engine import DeviceBP
+                 device: int | None = None, vars_per_thread: int = 0, schedule: str = "parallel", side_probs=None):
+        from .engine import DeviceBP, RelayParams, bp_method_code
 
         self.h = h
+        self.side_probs = side_probs
         self.max_iter = max_iter
         self.bp_method = bp_method
         self.schedule = schedule
@@ -49,20 +82,30 @@ class BPDecoder:
         self.channel_probs = np.asarray(channel_probs, dtype=np.float64)
         H = h if isinstance(h, CSR) else CSR.from_dense(h)
         self.num_checks, self.num_qubits = H.m, H.n
+        relay = None
+        if side_probs is not None:
+            if bp_method_code(bp_method) != 1:
+                raise ValueError("side_probs need bp_method 'minimum_sum': product_sum has no side decode")
+            if schedule == "parallel":
+                relay = RelayParams(pre_iter=_int_max_iter(max_iter, H.n), pre_gamma=0.0, num_legs=0)
         self.decoder = DeviceBP(H, self.channel_probs, max_iter=_int_max_iter(max_iter, H.n), bp_method=bp_method,
                                 ms_scaling_factor=ms_scaling_factor, precision=precision, device=device,
-                                vars_per_thread=vars_per_thread, schedule=schedule)
+                                vars_per_thread=vars_per_thread, schedule=schedule, relay=relay)
+        if side_probs is not None:
+            _set_side_probs(self.decoder, side_probs)
         self.iter = 0
         self.converge = 0
 
-    def decode(self, synd):
-        corr, it, conv = self.decoder.decode_batch(np.asarray(synd).reshape(1, -1))
+    def decode(self, synd, side=None):
+        corr, it, conv = self.decoder.decode_batch(np.asarray(synd).reshape(1, -1),
+                                                   None if side is None else np.asarray(side).reshape(1, -1))
         self.iter, self.converge = int(it[0]), int(conv[0])
         return corr[0]
 
-    def decode_batch(self, synd):
-        """[B, m] syndromes -> ([B, n] corrections, iterations [B], converged [B])."""
-        return self.decoder.decode_batch(synd)
+    def decode_batch(self, synd, side=None):
+        """[B, m] syndromes -> ([B, n] corrections, iterations [B], converged [B]); ``side`` [B, n]: a
+        side decode (needs ``side_probs``)."""
+        return self.decoder.decode_batch(synd, side)
 
 
 class RelayBPDecoder:
@@ -76,10 +119,11 @@ class RelayBPDecoder:
 
     def __init__(self, h, channel_probs, pre_iter, pre_gamma=0.125, num_legs=20, leg_iter=None,
                  gamma_interval=(-0.24, 0.66), stop_nconv=1, gamma_seed=0, ms_scaling_factor=0.625,
-                 precision: int = 64, device: int | None = None):
+                 precision: int = 64, device: int | None = None, side_probs=None):
         from .engine import DeviceBP, RelayParams
 
         self.h = h
+        self.side_probs = side_probs  # (p0, p1): side-capable, as BPDecoder; the chain keeps its parameters
         self.ms_scaling_factor = ms_scaling_factor
         self.channel_probs = np.asarray(channel_probs, dtype=np.float64)
         H = h if isinstance(h, CSR) else CSR.from_dense(h)
@@ -92,17 +136,21 @@ class RelayBPDecoder:
         self.max_iter = self.relay.max_iter
         self.decoder = DeviceBP(H, self.channel_probs, bp_method="minimum_sum", ms_scaling_factor=ms_scaling_factor,
                                 precision=precision, device=device, relay=self.relay)
+        if side_probs is not None:
+            _set_side_probs(self.decoder, side_probs)
         self.iter = 0
         self.converge = 0
 
-    def decode(self, synd):
-        corr, it, conv = self.decoder.decode_batch(np.asarray(synd).reshape(1, -1))
+    def decode(self, synd, side=None):
+        corr, it, conv = self.decoder.decode_batch(np.asarray(synd).reshape(1, -1),
+                                                   None if side is None else np.asarray(side).reshape(1, -1))
         self.iter, self.converge = int(it[0]), int(conv[0])
         return corr[0]
 
-    def decode_batch(self, synd):
-        """[B, m] syndromes -> ([B, n] corrections, iterations [B], converged [B])."""
-        return self.decoder.decode_batch(synd)
+    def decode_batch(self, synd, side=None):
+        """[B, m] syndromes -> ([B, n] corrections, iterations [B], converged [B]); ``side`` [B, n]: a
+        side decode (needs ``side_probs``)."""
+        return self.decoder.decode_batch(synd, side)
 
 
 class FirstMinBPDecoder:

@@ -102,6 +102,17 @@ def _channel_probs(channel_probs, n, check_length=True):
     return np.ascontiguousarray(probs)
 
 
+def _side_bytes(side, B, n):
+    """Side bytes ``[B, n]`` of a side decode as a contiguous uint8 array (only bit 0 is read)."""
+    s = np.ascontiguousarray(np.atleast_2d(np.asarray(side)), dtype=np.uint8)
+    if s.shape != (B, n):
+        raise ValueError(f"side must be [{B}, {n}], not {list(s.shape)}")
+    return s
+
+
+CHANNEL_UPDATES = {None: 0, "x->z": 1, "z->x": 2}
+
+
 def bp_method_code(bp_method) -> int:
     if isinstance(bp_method, (int, np.integer)):
         return int(bp_method)
@@ -293,6 +304,16 @@ class DeviceBP(_Handle):
                       "qldpc_bp_set_channel_probs")
         self.channel_probs = probs
 
+    def set_side_probs(self, p0, p1):
+        """Side priors (``qldpc_bp_set_side_probs``, engines 7 and 8): the two tables a side decode
+        selects from per syndrome and variable (``side`` bit 0 -> ``p0``, 1 -> ``p1``).  A scalar
+        broadcasts to ``n``."""
+        n = self.graph.n
+        a, b = _channel_probs(p0, n), _channel_probs(p1, n)
+        _native.check(_native.lib().qldpc_bp_set_side_probs(self.handle, _np_ptr(a), _np_ptr(b)),
+                      "qldpc_bp_set_side_probs")
+        self.side_probs = (a, b)
+
     def geometry(self):
         g = dict(zip(["threads", "vars_per_thread", "lds_bytes", "blocks_per_cu"],
                      self._ints("qldpc_bp_geometry", "bp_geometry", 4)))
@@ -306,20 +327,29 @@ class DeviceBP(_Handle):
                                   list(lm)))
         return g
 
-    def decode_batch_device(self, synd_dev, corr_dev, iters_dev=None, conv_dev=None, stream=None):
-        """Decode device uint8 syndromes [B, m] into device corrections [B, n] (async)."""
+    def decode_batch_device(self, synd_dev, corr_dev, iters_dev=None, conv_dev=None, stream=None, side=None):
+        """Decode device uint8 syndromes [B, m] into device corrections [B, n] (async).  ``side``: device
+        uint8 side bytes [B, n] for a side decode (``qldpc_bp_decode_batch_side``)."""
         torch = _torch()
         B = int(synd_dev.shape[0])
         assert synd_dev.dtype == torch.uint8 and synd_dev.is_contiguous() and synd_dev.shape[1] == self.m
         assert corr_dev.dtype == torch.uint8 and corr_dev.is_contiguous() and tuple(corr_dev.shape) == (B, self.n)
+        if side is not None:
+            assert side.dtype == torch.uint8 and side.is_contiguous() and tuple(side.shape) == (B, self.n)
+            _native.check(_native.lib().qldpc_bp_decode_batch_side(
+                self.handle, _ptr(synd_dev), _ptr(side), _ptr(corr_dev), _ptr(iters_dev), _ptr(conv_dev), B,
+                _stream(stream, synd_dev.device)), "qldpc_bp_decode_batch_side")
+            return
         _native.check(_native.lib().qldpc_bp_decode_batch(
             self.handle, _ptr(synd_dev), _ptr(corr_dev), _ptr(iters_dev), _ptr(conv_dev), B,
             _stream(stream, synd_dev.device)), "qldpc_bp_decode_batch")
 
-    def decode_batch(self, synd):
-        """Host convenience: ``synd`` [B, m] (0/1) -> (corr [B, n] int, iters [B], converged [B])."""
+    def decode_batch(self, synd, side=None):
+        """Host convenience: ``synd`` [B, m] (0/1) -> (corr [B, n] int, iters [B], converged [B]).
+        ``side`` [B, n]: a side decode on the handle's side priors (:meth:`set_side_probs`)."""
         torch, dev, sd, corr, iters, conv = _decode_buffers(self.graph, synd)
-        self.decode_batch_device(sd, corr, iters, conv)
+        sb = None if side is None else torch.from_numpy(_side_bytes(side, sd.shape[0], self.graph.n)).to(dev)
+        self.decode_batch_device(sd, corr, iters, conv, side=sb)
         torch.cuda.synchronize(dev)
         return corr.cpu().numpy().astype(np.int64), iters.cpu().numpy(), conv.cpu().numpy().astype(bool)
 
@@ -570,6 +600,16 @@ class DeviceMC(_Handle):
         self._osd = (osd_x, osd_z)  # keep the handles alive
         _native.check(_native.lib().qldpc_mc_set_osd(self.handle, _handle(osd_x), _handle(osd_z)), "qldpc_mc_set_osd")
 
+    def set_channel_update(self, direction):
+        """X/Z-correlated decoding (``qldpc_mc_set_channel_update``): None, ``"x->z"`` or ``"z->x"``.  The
+        first sector's corrections are the side bytes of the second sector's decode, whose decoder
+        needs side priors (:meth:`DeviceBP.set_side_probs`).  Staged handles only."""
+        if direction not in CHANNEL_UPDATES:
+            raise ValueError(f"channel update must be None, 'x->z' or 'z->x', not {direction!r}")
+        _native.check(_native.lib().qldpc_mc_set_channel_update(self.handle, CHANNEL_UPDATES[direction]),
+                      "qldpc_mc_set_channel_update")
+        self.channel_update = direction
+
     def new_counters(self):
         return _new_counters(self.device)
 
@@ -669,6 +709,46 @@ def relay_decode_host(H, channel_probs, relay, synd, ms_scaling_factor=0.625, pr
         c.m, c.n, _np_ptr(rp), _np_ptr(ci), _np_ptr(probs), *r.abi(ms_scaling_factor, precision), _np_ptr(s),
         _np_ptr(corr), _np_ptr(iters), _np_ptr(conv), _np_ptr(nsol), B, int(threads)), "qldpc_relay_decode_host")
     return corr.astype(np.int64), iters, conv.astype(bool), nsol
+
+
+def _host_side_args(H, p0, p1, synd, side):
+    c = H if isinstance(H, CSR) else CSR.from_dense(H)
+    s = _syndromes(synd, c.m)
+    B = s.shape[0]
+    return (c, s, B, _channel_probs(p0, c.n), _channel_probs(p1, c.n), _side_bytes(side, B, c.n),
+            np.ascontiguousarray(c.row_ptr, dtype=np.int32), np.ascontiguousarray(c.col_idx, dtype=np.int32))
+
+
+def relay_decode_host_side(H, p0, p1, relay, synd, side, ms_scaling_factor=0.625, precision: int = 64,
+                           threads: int = 0):
+    """``qldpc_relay_decode_host_side``: :func:`relay_decode_host` under side priors: variable j of
+    syndrome b takes its prior and solution weight from ``p1`` when ``side[b, j] & 1``, else ``p0``."""
+    c, s, B, a, b, sb, rp, ci = _host_side_args(H, p0, p1, synd, side)
+    r = RelayParams.of(relay)
+    corr = np.zeros((B, c.n), np.uint8)
+    iters = np.zeros(B, np.int32)
+    conv = np.zeros(B, np.uint8)
+    nsol = np.zeros(B, np.int32)
+    _native.check(_native.lib().qldpc_relay_decode_host_side(
+        c.m, c.n, _np_ptr(rp), _np_ptr(ci), _np_ptr(a), _np_ptr(b), _np_ptr(sb), *r.abi(ms_scaling_factor, precision),
+        _np_ptr(s), _np_ptr(corr), _np_ptr(iters), _np_ptr(conv), _np_ptr(nsol), B, int(threads)),
+        "qldpc_relay_decode_host_side")
+    return corr.astype(np.int64), iters, conv.astype(bool), nsol
+
+
+def serial_decode_host_side(H, p0, p1, max_iter, synd, side, ms_scaling_factor=0.625, precision: int = 64,
+                            threads: int = 0):
+    """``qldpc_serial_decode_host_side``: :func:`serial_decode_host` under side priors (no posteriors):
+    ``synd`` [B, m], ``side`` [B, n] -> (corr [B, n] int64, iters [B], converged [B] bool)."""
+    c, s, B, a, b, sb, rp, ci = _host_side_args(H, p0, p1, synd, side)
+    corr = np.zeros((B, c.n), np.uint8)
+    iters = np.zeros(B, np.int32)
+    conv = np.zeros(B, np.uint8)
+    _native.check(_native.lib().qldpc_serial_decode_host_side(
+        c.m, c.n, _np_ptr(rp), _np_ptr(ci), _np_ptr(a), _np_ptr(b), _np_ptr(sb), int(max_iter),
+        float(ms_scaling_factor), int(precision), _np_ptr(s), _np_ptr(corr), _np_ptr(iters), _np_ptr(conv), B,
+        int(threads)), "qldpc_serial_decode_host_side")
+    return corr.astype(np.int64), iters, conv.astype(bool)
 
 
 def serial_layers(H):

@@ -285,11 +285,21 @@ class CodeSimulator_DataError(_ShotStream):
     """Data-error simulator (``src/Simulators.py:75-188``).
 
     Extra keyword arguments (not in the reference): ``seed`` for the fused
-    path's Philox stream.
+    path's Philox stream; ``channel_update``: None, ``"x->z"`` or ``"z->x"`` (bposd's
+    ``css_decode_sim(channel_update=...)``): the first sector is decoded with its decoder as given, the
+    second with, per shot and qubit, the prior conditioned on the first decoder's decision
+    (:func:`~.decoders.channel_update_probs` of ``pauli_error_probs``).  The fused paths build the
+    second sector's side-capable handle from the user decoder's graph and parameters and run the
+    staged pipeline (``qldpc_mc_set_channel_update``); both sectors are then always decoded.  BP only:
+    BP+OSD sectors raise ``TypeError``.
     """
 
     def __init__(self, code=None, decoder_x=None, decoder_z=None, pauli_error_probs=(0.01, 0.01, 0.01),
-                 eval_logical_type="Total", seed=None):
+                 eval_logical_type="Total", seed=None, channel_update=None):
+        if channel_update not in (None, "x->z", "z->x"):
+            raise ValueError(f"channel_update must be None, 'x->z' or 'z->x', not {channel_update!r}")
+        self.channel_update = channel_update
+        self._mc_cu = None
         self.code = code
         self.decoder_z, self.decoder_x = decoder_z, decoder_x
         self.N = code.N
@@ -314,9 +324,22 @@ class CodeSimulator_DataError(_ShotStream):
         self.error_x, self.error_z = self._generate_error()
         code = self.code
         synd_z = code.hx @ self.error_z % 2
-        decoded_z = self.decoder_z.decode(synd_z)
         synd_x = code.hz @ self.error_x % 2
-        decoded_x = self.decoder_x.decode(synd_x)
+        if self.channel_update is None:
+            decoded_z = self.decoder_z.decode(synd_z)
+            decoded_x = self.decoder_x.decode(synd_x)
+        else:
+            x_first = self.channel_update == "x->z"
+            second = self.decoder_z if x_first else self.decoder_x
+            if _is_bposd(self.decoder_x) or _is_bposd(self.decoder_z) or getattr(second, "side_probs", None) is None:
+                raise TypeError(f"channel_update={self.channel_update!r} needs a BP decoder built with side_probs "
+                                "for the second sector (BP+OSD is not supported)")
+            if x_first:
+                decoded_x = self.decoder_x.decode(synd_x)
+                decoded_z = second.decode(synd_z, side=decoded_x)
+            else:
+                decoded_z = self.decoder_z.decode(synd_z)
+                decoded_x = second.decode(synd_x, side=decoded_z)
         residual_x = (self.error_x + decoded_x) % 2
         residual_z = (self.error_z + decoded_z) % 2
         X_failure, Z_failure = _css_failures(code, residual_x, residual_z)
@@ -340,12 +363,46 @@ class CodeSimulator_DataError(_ShotStream):
             self._mc = DeviceMC(self.code, bx, bz)
         return self._mc
 
+    def _channel_update_mc(self):
+        """The staged handle of a ``channel_update`` run: the first sector's engine BP as the user built
+        it, the second sector's side-capable handle (engine 7 for a flooding or relay decoder, engine 8
+        for a serial one) on the user decoder's own graph and parameters, with the conditional priors of
+        ``pauli_error_probs`` as side tables."""
+        if self._mc_cu is None:
+            from .decoders import channel_update_probs
+            from .engine import DeviceBP, DeviceMC, RelayParams
+
+            if _is_bposd(self.decoder_x) or _is_bposd(self.decoder_z):
+                raise TypeError("channel_update does not run with BP+OSD sectors")
+            bx, bz = _engine_bp(self.decoder_x), _engine_bp(self.decoder_z)
+            if bx is None or bz is None:
+                raise TypeError("channel_update decodes both sectors: it needs engine BPDecoder instances for both")
+            x_first = self.channel_update == "x->z"
+            b = bz if x_first else bx
+            if b.bp_method != 1:
+                raise ValueError("channel_update needs minimum_sum decoders: product_sum has no side decode")
+            _, p0, p1 = channel_update_probs(*self.channel_probs, self.channel_update)
+            relay = b.relay
+            if b.schedule == "parallel" and relay is None:  # plain min-sum on engine 7: no memory, no legs
+                relay = RelayParams(pre_iter=b.max_iter, pre_gamma=0.0, num_legs=0)
+            second = DeviceBP(None, b.channel_probs, max_iter=b.max_iter, bp_method="minimum_sum",
+                              ms_scaling_factor=b.ms_scaling_factor, precision=b.precision, graph=b.graph,
+                              relay=relay, schedule=b.schedule)
+            second.set_side_probs(p0, p1)
+            mc = DeviceMC(self.code, bx if x_first else second, second if x_first else bz, staged=True)
+            mc.set_channel_update(self.channel_update)
+            self._mc_cu = mc
+        return self._mc_cu
+
     def fused_counts(self, num_run: int):
         """Run ``num_run`` shots through the fused HIP path; returns the all-reduced :class:`~.engine.MCResult`."""
+        px, py, pz = self.channel_probs
+        if self.channel_update is not None:
+            return self._fused_run(self._channel_update_mc, num_run, lambda mc, b, c, cnt: mc.launch(
+                px, py, pz, self.seed, b, c, self.eval_logical_type, cnt))
         ok, bx, bz = self._engine_ready()
         if not ok:
             raise TypeError("fused path needs engine BPDecoder instances for the sectors eval_logical_type uses")
-        px, py, pz = self.channel_probs
         return self._fused_run(lambda: self._device_mc(bx, bz), num_run, lambda mc, b, c, cnt: mc.launch(
             px, py, pz, self.seed, b, c, self.eval_logical_type, cnt))
 
@@ -361,18 +418,21 @@ class CodeSimulator_DataError(_ShotStream):
         sharded over the ranks; the offset advances by ``shots_per_weight`` per stratum, so no two
         strata (or later runs) share a shot index.  Needs engine ``BPDecoder`` sectors.
         """
-        ok, bx, bz = self._engine_ready()
-        if not ok:
-            raise TypeError("FailureSpectrum needs engine BPDecoder instances for the sectors eval_logical_type "
-                            "uses (BP+OSD strata are not supported)")
         from . import _native
         from .engine import DeviceMC, _torch
 
+        if self.channel_update is not None:
+            mc = self._channel_update_mc()
+        else:
+            ok, bx, bz = self._engine_ready()
+            if not ok:
+                raise TypeError("FailureSpectrum needs engine BPDecoder instances for the sectors eval_logical_type "
+                                "uses (BP+OSD strata are not supported)")
+            if getattr(self, "_mc_staged", None) is None:
+                self._mc_staged = DeviceMC(self.code, bx, bz, staged=True)
+            mc = self._mc_staged
         torch = _torch()
         self._lazy_seed()
-        if getattr(self, "_mc_staged", None) is None:
-            self._mc_staged = DeviceMC(self.code, bx, bz, staged=True)
-        mc = self._mc_staged
         weights = [int(w) for w in weights]
         S = int(shots_per_weight)
         px, py, pz = self.channel_probs
@@ -546,6 +606,12 @@ class CodeSimulator_DataError(_ShotStream):
         return int(out[0]), int(out[1]), int(out[2])
 
     def _batch_failures(self, n: int) -> int:
+        if self.channel_update is not None:
+            if _is_bposd(self.decoder_x) or _is_bposd(self.decoder_z):
+                raise TypeError("channel_update does not run with BP+OSD sectors")
+            if _engine_bp(self.decoder_x) is not None and _engine_bp(self.decoder_z) is not None:
+                return self.fused_counts(n).failures
+            return int(np.sum([self._single_run() for _ in range(n)]))
         ok, _, _ = self._engine_ready()
         if ok:
             return self.fused_counts(n).failures
@@ -1204,14 +1270,14 @@ class _CodeFamilyBase:
         self.decoder1_class = decoder1_class
         self.decoder2_class = decoder2_class
 
-    def _data_simulator(self, eval_code, eval_p, eval_logical_type):
+    def _data_simulator(self, eval_code, eval_p, eval_logical_type, channel_update=None):
         """The ``'data'`` point: decoder2 on hz / hx with ``p_data = eval_p`` and the
         :class:`CodeSimulator_DataError` of the depolarizing channel at ``3/2 eval_p``."""
         decoder_x = self.decoder2_class.GetDecoder({"h": eval_code.hz, "p_data": eval_p})
         decoder_z = self.decoder2_class.GetDecoder({"h": eval_code.hx, "p_data": eval_p})
         return CodeSimulator_DataError(code=eval_code, decoder_x=decoder_x, decoder_z=decoder_z,
                                        pauli_error_probs=_depolarizing_probs(eval_p),
-                                       eval_logical_type=eval_logical_type)
+                                       eval_logical_type=eval_logical_type, channel_update=channel_update)
 
     def EvalSustainableThreshold(self, noise_model: str, eval_logical_type: str, eval_method: str,
                                  est_threshold: float, num_samples_per_cycle: int, num_cycles_list: list,
@@ -1247,8 +1313,13 @@ class CodeFamily(_CodeFamilyBase):
     (``'circuit'``: :class:`CodeSimulator_Circuit` on this package's own circuits and DEMs)."""
 
     def EvalWER(self, noise_model: str, eval_logical_type: str, eval_p_list: list, num_samples: int, num_cycles=1,
-                data_synd_noise_ratio=1, circuit_type="coloration", circuit_error_params=None, if_plot=True):
+                data_synd_noise_ratio=1, circuit_type="coloration", circuit_error_params=None, if_plot=True, *,
+                channel_update=None):
+        """``channel_update`` (keyword only; ``'data'`` model only): X/Z-correlated decoding, see
+        :class:`CodeSimulator_DataError`."""
         _check_eval_args(noise_model, eval_logical_type)
+        if channel_update is not None and noise_model != "data":
+            raise ValueError("channel_update applies to the 'data' noise model only")
         eval_wer_list = []
         for eval_code in self.code_list:
             for eval_p in eval_p_list:
@@ -1272,14 +1343,15 @@ class CodeFamily(_CodeFamilyBase):
                                                eval_logical_type=eval_logical_type)
                     eval_wer_list.append(sim.WordErrorRate(num_rounds=num_cycles, num_samples=num_samples)[0])
                     continue
-                sim = self._data_simulator(eval_code, eval_p, eval_logical_type)
+                sim = self._data_simulator(eval_code, eval_p, eval_logical_type, channel_update)
                 eval_wer_list.append(sim.WordErrorRate(num_samples)[0])
         eval_wer_array = np.reshape(np.array(eval_wer_list), [len(self.code_list), len(eval_p_list)])
         if if_plot:
             _plot_wer(self.code_list, eval_p_list, eval_wer_array, num_cycles)
         return eval_wer_array
 
-    def EvalWER_Stratified(self, eval_logical_type: str, eval_p_list: list, shots_per_weight: int, tail=1e-12):
+    def EvalWER_Stratified(self, eval_logical_type: str, eval_p_list: list, shots_per_weight: int, tail=1e-12, *,
+                           channel_update=None):
         """:meth:`EvalWER` for the ``'data'`` model through
         :meth:`CodeSimulator_DataError.WordErrorRate_Stratified`: the same ``p = 3/2 eval_p``
         convention and decoder construction, the same ``[codes, points]`` array; every point measures
@@ -1288,7 +1360,7 @@ class CodeFamily(_CodeFamilyBase):
         eval_wer_list = []
         for eval_code in self.code_list:
             for eval_p in eval_p_list:
-                sim = self._data_simulator(eval_code, eval_p, eval_logical_type)
+                sim = self._data_simulator(eval_code, eval_p, eval_logical_type, channel_update)
                 eval_wer_list.append(sim.WordErrorRate_Stratified(shots_per_weight, tail)[0])
         return np.reshape(np.array(eval_wer_list), [len(self.code_list), len(eval_p_list)])
 
