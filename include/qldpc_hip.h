@@ -203,6 +203,11 @@ int qldpc_osd_gpu_geometry(const qldpc_osd_gpu *osd, int32_t *row_words, int32_t
  * Shots are keyed by their global index: shot s, qubit j draws
  * u = Philox4x32-10(key = seed, ctr = (j, s_lo, s_hi, stream)) as a 53-bit
  * double, so any shot range sharded over devices reproduces the same counts.
+ * The sectors need not match: hx and hz may differ in rows and degrees, and their decoders in
+ * engine, threads, vars per thread, degree class, precision or layout family.  One fused kernel
+ * serves a pair whose routes agree (row counts, row widths and degree-3 slot counts may differ);
+ * any other pair runs the staged pipeline (qldpc_mc_create_staged), bit-identical per shot.
+ * Different code lengths or devices are QLDPC_EINVAL.
  */
 int qldpc_mc_create(qldpc_bp *dec_x, const qldpc_graph *logical_x, qldpc_bp *dec_z,
                     const qldpc_graph *logical_z, qldpc_mc **out);

@@ -2128,16 +2128,18 @@ int qldpc_mc_create(qldpc_bp* dec_x, const qldpc_graph* logical_x, qldpc_bp* dec
                       // the kernel's compile-time D3K must be each sector's own (a degree-3
                       // variable past it would run the 4-edge path and read the shared dummy slot)
                       (dec_x && dec_z && dec_x->route.m2s && dec_x->route.d3k != dec_z->route.d3k) ||
+                      // one launch shape, variant and address scale for both sectors: sectors whose
+                      // plans differ in any of them (hx and hz of unequal column degrees) decode
+                      // one after the other (code length and device stay errors: mc_create_staged)
+                      (dec_x && dec_z &&
+                       (dec_x->route.TB != dec_z->route.TB || dec_x->route.VPL != dec_z->route.VPL ||
+                        dec_x->route.DMAX != dec_z->route.DMAX || dec_x->route.precision != dec_z->route.precision ||
+                        dec_x->route.engine != dec_z->route.engine || dec_x->route.ea_shift != dec_z->route.ea_shift)) ||
                       env_int("QLDPC_MC_STAGED", 0) == 1;
   if (staged) return mc_create_staged(dec_x, logical_x, dec_z, logical_z, out);
   if (dec_x && dec_z) {
     if (dec_x->g->n != dec_z->g->n) return set_err(QLDPC_EINVAL, "sector code lengths differ");
-    if (dec_x->route.TB != dec_z->route.TB || dec_x->route.VPL != dec_z->route.VPL || dec_x->route.DMAX != dec_z->route.DMAX ||
-        dec_x->route.precision != dec_z->route.precision || dec_x->route.engine != dec_z->route.engine)
-      return set_err(QLDPC_EINVAL, "sector decoders need identical geometry/precision (same vars_per_thread)");
     if (dec_x->g->device != dec_z->g->device) return set_err(QLDPC_EINVAL, "sector decoders on different devices");
-    if (dec_x->route.m2s != dec_z->route.m2s || dec_x->route.tail != dec_z->route.tail || dec_x->route.fb != dec_z->route.fb)
-      return set_err(QLDPC_EINVAL, "sector decoders use different LDS layouts (QLDPC_M2S)");
   }
   QLDPC_HIP(hipSetDevice(d0->g->device));
   auto* mc = new qldpc_mc();
@@ -2156,8 +2158,6 @@ int qldpc_mc_create(qldpc_bp* dec_x, const qldpc_graph* logical_x, qldpc_bp* dec
   if (dec_z && (rc = build_lmask(logical_z, dec_z->g->n, mc->lmask[1], mc->kw[1]))) return fail(rc);
   // the sectors' common route: one kernel serves both
   mc->route = d0->route;
-  if (dec_x && dec_z && dec_x->route.ea_shift != dec_z->route.ea_shift)
-    return fail(set_err(QLDPC_EINVAL, "sector decoders use different LDS address scales"));
   // only slots that hold degree <= 3 variables in both sectors skip slot 4; the fused kernels have no D2K
   mc->route.d3k = std::min(dec_x ? dec_x->route.d3k : 1 << 20, dec_z ? dec_z->route.d3k : 1 << 20);
   mc->route.d2k = 0;
@@ -2175,8 +2175,15 @@ int qldpc_mc_create(qldpc_bp* dec_x, const qldpc_graph* logical_x, qldpc_bp* dec
         mc->vslots = std::max(mc->vslots, route_vslots(d->route, d->g->m));
     mc->img_bytes = (int)slot_img_bytes(mc->vslots, mc->mmax, tsize);
     if (mc->route.engine >= 3) {
-      if (!route_fits(mc->route, mc->vslots, mc->mmax))
+      if (!route_fits(mc->route, mc->vslots, mc->mmax)) {
+        // each sector's own image fits (its decoder exists); only their common image does not
+        // (no test reaches this branch: no known pair fits alone and not together)
+        if (dec_x && dec_z) {
+          fail(0);
+          return mc_create_staged(dec_x, logical_x, dec_z, logical_z, out);
+        }
         return fail(set_err(QLDPC_ENOTSUP, "sector images exceed the register engines' 64 KiB addressing (QLDPC_ENGINE=2)"));
+      }
       mc->route.NS = 1;
       mc->route.lds_bytes = (int)route_lds(mc->route, mc->vslots, mc->mmax);
     } else {
@@ -2370,11 +2377,16 @@ int qldpc_mc_launch(qldpc_mc* mc, double px, double py, double pz, uint64_t seed
     // both sectors drawing Philox errors: the first sector's pass caches each shot's classes for the
     // second (SMcArgs::cls_cache; [grid][chunk][TB] u16, one Philox draw per (shot, variable) instead of
     // two; QLDPC_CLS_CACHE=0 draws in both passes)
+    // The cache is keyed by (thread, variable slot): the second sector reads a word back as the
+    // classes of its own slots' variables, so both sectors must hold the same variable in every
+    // slot.  The degree sort gives hx and hz different slot maps whenever their columns of degree
+    // <= 3 sit at different positions; such a pair draws in both passes.
     a.cls_cache = nullptr;
     const size_t cc_need = (size_t)grid * (size_t)a.chunk * (size_t)mc->route.TB * 2;
+    const bool same_slots = a.nsec == 2 && mc->dec[0]->slot_var == mc->dec[1]->slot_var;
     // (bounded: 256 MiB covers every bundled code at the bench's launch sizes; huge launches of small
     // codes, e.g. 10^9 shots of GenBicycleA1 at 1024-shot chunks, would need ~0.7 GB: they draw twice)
-    if (a.nsec == 2 && !d_uniforms && mc->route.VPL <= 8 && env_int("QLDPC_CLS_CACHE", 1) != 0 && cc_need <= (256u << 20)) {
+    if (same_slots && !d_uniforms && mc->route.VPL <= 8 && env_int("QLDPC_CLS_CACHE", 1) != 0 && cc_need <= (256u << 20)) {
       const size_t need = cc_need;
       if (mc->cls_cache.bytes < need) {
         mc->cls_cache.release();

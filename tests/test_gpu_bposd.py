@@ -9,6 +9,7 @@ the oracle's BP followed by its literal OSD restatement.
 import numpy as np
 import pytest
 
+from bposd_ref import oracle_sector_fails as _oracle_sector_fails
 from qldpc_fault_tolerance_amd import codes
 
 pytestmark = pytest.mark.gpu
@@ -377,26 +378,6 @@ def test_final_osd_graph_mismatch_is_rejected(gpu):
     with pytest.raises(_native.QldpcError, match="different graph"):
         ph.set_final_osd(oz, ox)  # swapped sectors
     ph.set_final_osd(ox, oz)
-
-
-def _oracle_sector_fails(oracle, code, err, p, mi, order, method="osd_e"):
-    """Per shot and sector: the reference's BPOSD verdict on the engine's sampled errors —
-    oracle BP (soft), then the C OSD restatement where BP did not converge, then the
-    _single_run failure check (src/Simulators.py:135-160)."""
-    from qldpc_fault_tolerance_amd.simulators import gf2_rows
-
-    out = np.zeros((err.shape[0], 2), dtype=bool)
-    for q, H, L, k in ((0, code.hz, code.lz, "hz"), (1, code.hx, code.lx, "hx")):
-        e = ((err >> q) & 1).astype(np.uint8)
-        synd = gf2_rows(code.csr(k), e)
-        oc, _, ov, op = oracle.bp_decode_batch_soft(H, p, mi, 0.625, synd, 64)
-        x = oc.copy()
-        nc = np.flatnonzero(~ov)
-        if nc.size:
-            x[nc] = oracle.osd_decode_batch(H, p * np.ones(code.N), synd[nc], op[nc], method, order)[1]
-        r = (e ^ x).astype(np.uint8)
-        out[:, q] = gf2_rows(code.csr(k), r).any(1) | gf2_rows(code.csr("lz" if q == 0 else "lx"), r).any(1)
-    return out
 
 
 def test_bposd_shot_loop_n1600_osd_e10_matches_oracle_per_shot(gpu, oracle):

@@ -15,6 +15,7 @@ import os
 import numpy as np
 import pytest
 
+from css_cases import asymmetric_hgp
 from qldpc_fault_tolerance_amd import codes
 
 pytestmark = pytest.mark.gpu
@@ -135,33 +136,6 @@ def test_m2s_fused_mc_matches_oracle_per_shot(gpu, oracle, fam):
     for k in ("err", "iters", "corr", "fail"):
         assert np.array_equal(getattr(res, k), ref[k]), k
     assert res.failures == ref["failures"] and res.sector_iters == ref["sector_iters"]
-
-
-def _biregular(m, n, dc, dv, seed):
-    """A random (dv, dc)-regular m x n parity-check matrix (configuration model, no double edges)."""
-    rng = np.random.default_rng(seed)
-    while True:
-        stubs = np.repeat(np.arange(n), dv)
-        rng.shuffle(stubs)
-        H = np.zeros((m, n), np.uint8)
-        ok = True
-        for i in range(m):
-            for j in stubs[i * dc:(i + 1) * dc]:
-                ok = ok and not H[i, j]
-                H[i, j] = 1
-        if ok:
-            return H
-
-
-def asymmetric_hgp():
-    """HGP of a (3,4)-regular 6x8 h1 and a rank-deficient (3,3)-regular 8x8 h2: hx is all
-    degree 3 (rows of 7), hz has 64 degree-3 and 48 degree-4 columns (rows of 6).  With 4 variables per
-    thread (64 lanes) both sectors qualify for the one-word fp64 families, with different degree-3
-    slot counts (hx 4, hz 1)."""
-    from qldpc_fault_tolerance_amd import gf2
-
-    h2 = next(h for h in (_biregular(8, 8, 3, 3, 100 + s) for s in range(64)) if gf2.rank(h) < 8)
-    return codes.hgp(_biregular(6, 8, 4, 3, 7), h2, name="hgp_asym_112")
 
 
 @pytest.mark.parametrize("fam", ["m2s", "c2s"])
