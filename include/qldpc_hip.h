@@ -170,9 +170,16 @@ int qldpc_osd_gpu_decode(qldpc_osd_gpu *osd, const uint8_t *d_synd, const double
  * residual syndrome weight does not grow, at most max_iter accepted steps; the corrections are the
  * xor of the accepted steps' decisions.  One workgroup per syndrome, the whole loop on the device.
  *   create : graph g, channel_probs [n] in (0, 1), max_iter, ms_scaling_factor (0 = ldpc's
- *            1 - 2^-iter schedule at iter 1), precision 64 (ldpc's double) or 32; 2 (m + n) <= 64 KiB.
+ *            1 - 2^-iter schedule at iter 1), precision 64 (ldpc's double) or 32.  QLDPC_ENOTSUP
+ *            when 2 (m + n) bytes of arrays and the workgroup kernel's own 16 bytes of LDS exceed
+ *            64 KiB, i.e. for m + n > 32760.
  *   decode : device pointers d_synd [B][m] u8 -> d_corr [B][n] u8, d_steps [B] i32 (accepted
  *            steps, or NULL), on `stream`.
+ *   info   : the launch qldpc_firstmin_decode would make under the current environment (no
+ *            reference counterpart; tests): grid = resident workgroups of the workgroup kernel
+ *            (the wave kernel launches up to 4 grid workgroups of 4 waves), lds_bytes = LDS per
+ *            workgroup of the kernel it takes, wave = 1 for one wave per syndrome (m + n <= 8192
+ *            unless QLDPC_FM_WAVE=0), 0 for one workgroup per syndrome.  Any output may be NULL.
  * Replaces the Python loop of FirstMinBPDecoder.decode (Decoders.py:60-74).
  */
 typedef struct qldpc_firstmin qldpc_firstmin;
@@ -182,6 +189,7 @@ typedef struct qldpc_firstmin qldpc_firstmin;
 int qldpc_firstmin_create(const qldpc_graph *g, const double *channel_probs, int32_t max_iter,
                           double ms_scaling_factor, int32_t precision, qldpc_firstmin **out);
 int qldpc_firstmin_destroy(qldpc_firstmin *fm);
+int qldpc_firstmin_info(const qldpc_firstmin *fm, int32_t *grid, int32_t *lds_bytes, int32_t *wave);
 int qldpc_firstmin_decode(qldpc_firstmin *fm, const uint8_t *d_synd, uint8_t *d_corr, int32_t *d_steps, int64_t B,
                           void *stream);
 

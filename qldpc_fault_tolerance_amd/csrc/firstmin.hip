@@ -31,7 +31,8 @@ using qldpc_rt::set_err;
 
 struct qldpc_firstmin {
   int device = 0, m = 0, n = 0, E = 0, max_iter = 0, precision = 64, grid = 0;
-  size_t lds = 0;
+  size_t lds = 0;         // dynamic LDS of the workgroup kernel: 2 (m + n)
+  size_t static_lds = 0;  // that kernel's own static LDS, as the code object reports it
   qldpc_rt::DevBuf rp, ci;      // CSR: H d
   qldpc_rt::DevBuf cp, crow;    // CSC in column order (rows ascending): col_ptr [n + 1], row [E]
   qldpc_rt::DevBuf csb, cmag;   // per CSC entry: prior-sign parity of the row's other edges (u8), |c2b| (T)
@@ -309,6 +310,35 @@ void firstmin_tables(const qldpc_graph* g, const std::vector<double>& pr, double
   }
 }
 
+constexpr size_t kFmLdsLimit = 64 * 1024;  // LDS one workgroup may hold
+
+// LDS of one wave-kernel workgroup: four syndromes' arrays, each rounded up to 16 bytes
+size_t fm_wave_lds(const qldpc_firstmin* fm) {
+  return 4 * (((size_t)2 * fm->m + (size_t)2 * fm->n + 15) & ~(size_t)15);
+}
+
+// the kernel qldpc_firstmin_decode launches: one wave per syndrome when four syndromes' arrays fit
+// 64 KiB (QLDPC_FM_WAVE=0: one workgroup each)
+bool fm_takes_wave(const qldpc_firstmin* fm) {
+  const char* we = std::getenv("QLDPC_FM_WAVE");
+  return fm_wave_lds(fm) <= kFmLdsLimit && !(we && std::atoi(we) == 0);
+}
+
+// static LDS of the workgroup kernel's two instantiations (the loop and BP1) in one precision, read
+// from the code object so that it cannot drift from the kernel
+template <typename T>
+int fm_static_lds(size_t* out) {
+  size_t s = 0;
+  for (const void* kf : {reinterpret_cast<const void*>(&firstmin_kernel<T, false>),
+                         reinterpret_cast<const void*>(&firstmin_kernel<T, true>)}) {
+    hipFuncAttributes fa;
+    if (hipFuncGetAttributes(&fa, kf) != hipSuccess) return set_err(QLDPC_EHIP, "first-min kernel attributes");
+    s = std::max(s, (size_t)fa.sharedSizeBytes);
+  }
+  *out = s;
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -319,7 +349,10 @@ int qldpc_firstmin_create(const qldpc_graph* g, const double* channel_probs, int
   if (precision != 32 && precision != 64) return set_err(QLDPC_EINVAL, "precision must be 32 or 64");
   const int m = g->m, n = g->n, E = (int)g->col_idx.size();
   const size_t lds = (size_t)2 * m + (size_t)2 * n;
-  if (lds > 64 * 1024) return set_err(QLDPC_ENOTSUP, "first-min decoder: 2 (m + n) bytes of LDS > 64 KiB");
+  // the workgroup kernel holds 2 (m + n) bytes of dynamic LDS beside its own static LDS (16 bytes)
+  static const char* const kOverLds =
+      "first-min decoder: 2 (m + n) + 16 bytes of LDS (arrays + the kernel's own) > 64 KiB";
+  if (lds > kFmLdsLimit) return set_err(QLDPC_ENOTSUP, kOverLds);  // before any device call
   std::vector<double> pr(n);
   for (int j = 0; j < n; ++j) {
     const double p = channel_probs[j];
@@ -362,6 +395,9 @@ int qldpc_firstmin_create(const qldpc_graph* g, const double* channel_probs, int
     return code;
   };
   if (hipSetDevice(g->device) != hipSuccess) return fail(set_err(QLDPC_EHIP, "hipSetDevice"));
+  if (int rc = precision == 64 ? fm_static_lds<double>(&F->static_lds) : fm_static_lds<float>(&F->static_lds))
+    return fail(rc);
+  if (lds + F->static_lds > kFmLdsLimit) return fail(set_err(QLDPC_ENOTSUP, kOverLds));
   std::vector<uint8_t> esb, csb(E);
   const size_t ts = precision == 64 ? 8 : 4;
   std::vector<unsigned char> cmag((size_t)E * ts), prior((size_t)n * ts);
@@ -460,6 +496,15 @@ int qldpc_firstmin_destroy(qldpc_firstmin* fm) {
   return 0;
 }
 
+int qldpc_firstmin_info(const qldpc_firstmin* fm, int32_t* grid, int32_t* lds_bytes, int32_t* wave) {
+  if (!fm) return set_err(QLDPC_EINVAL, "NULL argument");
+  const bool w = fm_takes_wave(fm);
+  if (grid) *grid = fm->grid;
+  if (lds_bytes) *lds_bytes = (int32_t)(w ? fm_wave_lds(fm) : fm->lds + fm->static_lds);
+  if (wave) *wave = w ? 1 : 0;
+  return 0;
+}
+
 int qldpc_firstmin_decode(qldpc_firstmin* fm, const uint8_t* d_synd, uint8_t* d_corr, int32_t* d_steps, int64_t B,
                           void* stream) {
   if (!fm || (B > 0 && (!d_synd || !d_corr))) return set_err(QLDPC_EINVAL, "NULL argument");
@@ -481,15 +526,13 @@ int qldpc_firstmin_decode(qldpc_firstmin* fm, const uint8_t* d_synd, uint8_t* d_
   a.m = fm->m;
   a.n = fm->n;
   a.max_iter = fm->max_iter;
-  // one wave per syndrome when four syndromes' arrays fit 64 KiB (QLDPC_FM_WAVE=0: one workgroup each)
-  const size_t per = ((size_t)2 * fm->m + (size_t)2 * fm->n + 15) & ~(size_t)15;
-  const char* we = std::getenv("QLDPC_FM_WAVE");
-  if (4 * per <= 64 * 1024 && !(we && std::atoi(we) == 0)) {
+  if (fm_takes_wave(fm)) {
+    const size_t wl = fm_wave_lds(fm);
     const int gw = (int)std::min<long long>((B + 3) / 4, (long long)fm->grid * 4);
     if (fm->precision == 64)
-      hipLaunchKernelGGL(firstmin_wave_kernel<double>, dim3(gw), dim3(256), 4 * per, (hipStream_t)stream, a);
+      hipLaunchKernelGGL(firstmin_wave_kernel<double>, dim3(gw), dim3(256), wl, (hipStream_t)stream, a);
     else
-      hipLaunchKernelGGL(firstmin_wave_kernel<float>, dim3(gw), dim3(256), 4 * per, (hipStream_t)stream, a);
+      hipLaunchKernelGGL(firstmin_wave_kernel<float>, dim3(gw), dim3(256), wl, (hipStream_t)stream, a);
     QLDPC_HIP(hipGetLastError());
     return 0;
   }

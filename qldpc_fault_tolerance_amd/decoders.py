@@ -158,10 +158,10 @@ class FirstMinBPDecoder:
 
     ``minimum_sum`` (every reference call site) runs the whole loop on the GPU in one kernel
     (:class:`~.engine.DeviceFirstMin`, ``qldpc_firstmin_*``); ``product_sum``, and graphs past that
-    kernel's envelope (2 (m + n) > 64 KiB: ``QLDPC_ENOTSUP``), step the engine's one-iteration BP
-    from the host (one launch per first-min step for all active syndromes).  ``max_iter`` is
-    compared raw, as ``iter_counter < self.max_iter`` (``:66``): a float N/10 = 22.5 allows 23
-    accepted steps, so the device loop takes ``ceil(max_iter)``."""
+    kernel's envelope (2 (m + n) + 16 bytes of LDS > 64 KiB, i.e. m + n > 32760: ``QLDPC_ENOTSUP``),
+    step the engine's one-iteration BP from the host (one launch per first-min step for all active
+    syndromes).  ``max_iter`` is compared raw, as ``iter_counter < self.max_iter`` (``:66``): a
+    float N/10 = 22.5 allows 23 accepted steps, so the device loop takes ``ceil(max_iter)``."""
 
     def __init__(self, h, channel_probs, max_iter, bp_method, ms_scaling_factor, precision: int = 64,
                  device: int | None = None):

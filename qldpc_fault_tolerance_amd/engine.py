@@ -494,6 +494,16 @@ class DeviceFirstMin(_Handle):
         self._create("qldpc_firstmin_create", self.graph.handle, _np_ptr(self._probs), self.max_iter,
                      float(ms_scaling_factor), int(precision))
 
+    THREADS = 256  # per workgroup, in both loop kernels (csrc/firstmin.hip)
+
+    def geometry(self) -> dict:
+        """The launch ``decode_device`` would make now (``qldpc_firstmin_info``): ``grid`` resident
+        workgroups of the workgroup kernel, ``lds_bytes`` per workgroup of the kernel it takes and
+        ``wave`` (1: one wave per syndrome, 0: one workgroup; ``QLDPC_FM_WAVE`` is read per call)."""
+        g = dict(zip(("grid", "lds_bytes", "wave"), self._ints("qldpc_firstmin_info", "qldpc_firstmin_info", 3)))
+        g["threads"] = self.THREADS
+        return g
+
     def decode_device(self, synd_dev, corr_dev, steps_dev=None, stream=None):
         _native.check(_native.lib().qldpc_firstmin_decode(
             self.handle, _ptr(synd_dev), _ptr(corr_dev), _ptr(steps_dev), int(synd_dev.shape[0]),

@@ -161,7 +161,11 @@ def empty_rows(case_id: str) -> np.ndarray:
 @lru_cache(maxsize=None)
 def priors(case_id: str, kind: str, level: float = P0) -> np.ndarray:
     """Channel probabilities float64 [n] at prior level ``level``, read-only."""
-    n = CASES[case_id].n
+    return priors_of(CASES[case_id].n, kind, level)
+
+
+def priors_of(n: int, kind: str, level: float) -> np.ndarray:
+    """The prior rule of the module docstring on ``n`` variables (tests/firstmin_cases.py shares it)."""
     if kind == "uniform":
         return _ro(np.full(n, level))
     p = np.linspace(0.5 * level, 2.0 * level, n)
@@ -177,13 +181,20 @@ def priors(case_id: str, kind: str, level: float = P0) -> np.ndarray:
 def syndromes(case_id: str, level: float) -> np.ndarray:
     """The syndromes of a case at one level, uint8 [B, m], read-only (see the module docstring)."""
     c = CASES[case_id]
-    H = graph(case_id).astype(np.int64)
     if c.kind == "all":
         return _ro(((np.arange(1 << c.m)[:, None] >> np.arange(c.m)) & 1).astype(np.uint8))
-    rng = np.random.default_rng([c.seed, 1, c.levels.index(level)])
-    parts = [((rng.random((N_PER_LEVEL, c.n)) < level).astype(np.int64) @ H.T % 2).astype(np.uint8),
-             np.zeros((1, c.m), np.uint8)]
-    hole = empty_rows(case_id)
+    return syndromes_of(graph(case_id), c.seed, c.levels.index(level), level)
+
+
+def syndromes_of(H: np.ndarray, seed: int, level_index: int, level: float) -> np.ndarray:
+    """The syndrome rule of the module docstring on a graph (tests/firstmin_cases.py shares it)."""
+    m, n = H.shape
+    rng = np.random.default_rng([seed, 1, level_index])
+    # H e in float32: the counts are integers below 2^24, so the product is exact (and fast at n ~ 5000)
+    assert n < 1 << 24
+    e = (rng.random((N_PER_LEVEL, n)) < level).astype(np.float32)
+    parts = [((e @ H.T.astype(np.float32)).astype(np.int64) % 2).astype(np.uint8), np.zeros((1, m), np.uint8)]
+    hole = np.flatnonzero(H.sum(axis=1) == 0)
     if hole.size:
         s = parts[0][:1].copy()
         s[0, hole[0]] = 1
@@ -196,8 +207,13 @@ def syndromes(case_id: str, level: float) -> np.ndarray:
 def mixed(case_id: str, B: int) -> np.ndarray:
     """``B`` syndromes drawn from all levels of a case (cycled when B exceeds them), shuffled."""
     c = CASES[case_id]
-    S = np.vstack([syndromes(case_id, lv) for lv in c.levels])
-    rng = np.random.default_rng([c.seed, 2, B])
+    return mixed_of([syndromes(case_id, lv) for lv in c.levels], c.seed, B)
+
+
+def mixed_of(per_level: list, seed: int, B: int) -> np.ndarray:
+    """The ``mixed`` rule on the syndromes of each level (tests/firstmin_cases.py shares it)."""
+    S = np.vstack(per_level)
+    rng = np.random.default_rng([seed, 2, B])
     S = S[rng.permutation(len(S))]
     return _ro(np.ascontiguousarray(S[np.arange(B) % len(S)]))
 
