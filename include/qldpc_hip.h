@@ -61,10 +61,7 @@ int qldpc_abi_version(void);
 const char *qldpc_last_error(void);
 int qldpc_device_count(int *out);
 
-/* Build flags of this library: QLDPC_BUILD_EXPERIMENTAL when the measured-and-not-kept BP kernel
- * families (c2s 31103, m2v 40103, fp64 257-512 threads 303, engine 4) are compiled in
- * (-DQLDPC_EXPERIMENTAL=1); the product build leaves them out and ignores their opt-ins.  The
- * flag carries BP families only: the GPU OSD has no experimental variants. */
+/* Build flags of this library: 0.  QLDPC_BUILD_EXPERIMENTAL is a reserved bit: no build sets it. */
 #define QLDPC_BUILD_EXPERIMENTAL 1
 int qldpc_build_flags(void);
 
@@ -318,18 +315,18 @@ int qldpc_bp_geometry(const qldpc_bp *bp, int32_t *threads, int32_t *vars_per_th
 
 /* Kernel engine serving a decoder: 3 = register-resident variables (default
  * when the graph fits: column degree <= 4, <= 8 variables per thread, image
- * < 64 KiB), 2 = streamed variables, 1 = LDS-atomic check state, 4 = engine 3
- * with c2v computed by the check phase, 5 = product-sum (bp_method 0), 6 = HBM-resident
- * messages (qldpc_bp_create_hbm; automatic for images over 160 KiB), 7 = Relay-BP
- * (qldpc_bp_create_relay), 8 = serial-schedule min-sum (qldpc_bp_create_serial).
- * QLDPC_ENGINE in the environment selects 1, 2 or 4 explicitly. */
+ * < 64 KiB), 2 = streamed variables, 1 = LDS-atomic check state, 5 = product-sum
+ * (bp_method 0), 6 = HBM-resident messages (qldpc_bp_create_hbm; automatic for images over
+ * 160 KiB), 7 = Relay-BP (qldpc_bp_create_relay), 8 = serial-schedule min-sum
+ * (qldpc_bp_create_serial).  QLDPC_ENGINE in the environment selects 1, 2 or 6 explicitly
+ * (4, a removed engine, answers QLDPC_ENOTSUP). */
 int qldpc_bp_engine(const qldpc_bp *bp, int32_t *engine);
 
 /* Compile-time family of the decoder's kernels (the ENG template argument of rmc_kernel /
  * rdec_kernel as rocprofv3 prints it): engine 3 = 3, 13 (dword-scaled addresses), 103 (fp64
- * <= 256 threads), 303 (fp64 257-512 threads), 1013 (tail layout, 1024 threads), 11103 (fp64
- * m2-in-slot, rows of 3 chunks + a tail slot, 3 workgroups per CU); other engines their number.
- * row_chunks = 16-byte chunks per check row (engines 2-4). */
+ * <= 256 threads), 1013 (tail layout, 1024 threads), 11103 (fp64 m2-in-slot, rows of 3 chunks +
+ * a tail slot, 3 workgroups per CU); other engines their number.
+ * row_chunks = 16-byte chunks per check row (engines 2-3). */
 int qldpc_bp_kernel_id(const qldpc_bp *bp, int32_t *kernel_id, int32_t *row_chunks);
 
 /* The route qldpc_bp_create would take for this graph, priors and the QLDPC_* switches, decided

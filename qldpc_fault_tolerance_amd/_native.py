@@ -40,7 +40,6 @@ EXPORTED = [
     "qldpc_bp_set_side_probs", "qldpc_bp_decode_batch_side", "qldpc_relay_decode_host_side",
     "qldpc_serial_decode_host_side", "qldpc_mc_set_channel_update",
 ]
-BUILD_EXPERIMENTAL = 1  # qldpc_build_flags(): the measured-and-not-kept kernel families are compiled in
 COMM_ID_BYTES = 128
 
 
@@ -295,12 +294,6 @@ def check(rc: int, what: str = "") -> None:
     if rc != 0:
         msg = lib().qldpc_last_error().decode(errors="replace")
         raise QldpcError(f"{what} failed (rc={rc}): {msg}", rc)
-
-
-def experimental_families() -> bool:
-    """True when the library carries the opt-in c2s / m2v / 303 / engine-4 kernels
-    (built with ``-DQLDPC_EXPERIMENTAL=1``, e.g. ``tools/build_variant.py``)."""
-    return bool(lib().qldpc_build_flags() & BUILD_EXPERIMENTAL)
 
 
 def device_count() -> int:

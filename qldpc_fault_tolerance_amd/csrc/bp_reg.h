@@ -18,18 +18,6 @@
 // The LDS image puts CS first so that its byte address is the edge word's low
 // half: [CS (m+1) pairs][V: 16-byte sink + m rows][F (m+1)][lred 8][flags 2].
 // One decode in flight per workgroup; several workgroups share a CU.
-//
-// Engine 4 (same file, ENG = 4) moves the c2v arithmetic into the check phase:
-// the check thread, which holds its whole row in registers, computes every
-// edge's c2v (m2 if the edge holds m1 else m1, times ±alpha) and writes them
-// back into the row's slots; the variable phase then reads its c2v with one
-// 4-byte LDS read per edge and overwrites the slot with the new v2c.  No CS
-// array and no own-message registers remain, the random LDS reads halve in
-// width, and the image shrinks by 8 bytes per check.  Padding slots of a row
-// (logical position >= row degree) are rewritten with the sentinel, so the
-// next min pass ignores them.  Missing edges read a constant zero chunk and
-// write a sink.  Image: [V: zero chunk + m rows][F (m+1): bit0 (H x)_i, bit1
-// syndrome, bits 16.. row degree][sink 16][lred 8][flags 2].
 #pragma once
 
 #ifndef QLDPC_TID_LAUNDER
@@ -41,83 +29,26 @@
 #ifndef QLDPC_STAMPS
 #define QLDPC_STAMPS 0
 #endif
-#ifndef QLDPC_FLIP_BRANCHFREE
-#define QLDPC_FLIP_BRANCHFREE 0
-#endif
-// A/B build: the F-word xors of flipped variables after the whole variable loop (one divergent
-// region) instead of after each variable
-#ifndef QLDPC_FLIPLATE
-#define QLDPC_FLIPLATE 0
-#endif
-// A/B build: the m2s check phase derives tid from an SGPR wave base + mbcnt
-#ifndef QLDPC_M2S_MBCNT
-#define QLDPC_M2S_MBCNT 0
-#endif
-// c2s family: variables whose c2v reads are issued ahead of the current one's arithmetic
-#ifndef QLDPC_C2S_PF
-#define QLDPC_C2S_PF 2
-#endif
-// fp32 c2v in 4 VALU per edge (r_var_one); the check phases then store m2 | parity
-#ifndef QLDPC_F32_C2V4
-#define QLDPC_F32_C2V4 1
-#endif
-// fp64 c2v in 5 VALU per edge (r_var_one, two-word families); the check phases store m2 | parity
-#ifndef QLDPC_F64_C2V5
-#define QLDPC_F64_C2V5 1
-#endif
-// dword-scaled packed edge words (space-time families) hold absolute dword indices (SDWA unpack)
-#ifndef QLDPC_ABS_SH2
-#define QLDPC_ABS_SH2 1
-#endif
-// c2s check phase: the row's c2v as one 16-byte store per chunk (else 4-byte stores the
-// compiler pairs)
-#ifndef QLDPC_C2S_W128
-#define QLDPC_C2S_W128 1
-#endif
-// m2s family: one uniform prior in SGPRs instead of one per variable slot in VGPRs
-#ifndef QLDPC_M2S_UNIL
-#define QLDPC_M2S_UNIL 1
-#endif
-// m2s on dword-scaled words (space-time family 111313): the V slot address unpacked for the
-// gather is carried to the store (one SDWA per edge and iteration fewer; the backend otherwise
-// unpacks it again at the store)
-#ifndef QLDPC_M2S_KEEPVA
-#define QLDPC_M2S_KEEPVA 1
-#endif
-// m2s check phase: explicit row / tail / F / CS pointers stepped per row
-#ifndef QLDPC_M2S_RPTR
-#define QLDPC_M2S_RPTR 1
-#endif
-// two-word check phase (r_check_c): absolute LDS addresses for the rows, tails and CS stores
-#ifndef QLDPC_RC_RPTR
-#define QLDPC_RC_RPTR 1
-#endif
-// m2s check phase of the space-time family: rows in pairs, the second row's first QLDPC_M2S_ROWPAIR
-// chunks loaded before the first row is reduced (A/B build; 4 = the whole row spills).  Measured slower:
-// config 5 kernel 94.5 ms with one row at a time against 96.1-96.6 ms with 1-3 chunks ahead
-// (profiles/r06/config5/rowpair/), so 0 (one row at a time) is the product
-#ifndef QLDPC_M2S_ROWPAIR
-#define QLDPC_M2S_ROWPAIR 0
-#endif
-// m2s families: each variable slot's previous decisions as a wave lane mask (SGPRs): the flip test
-// is a scalar xor of two masks instead of a bit extract and compare per variable and iteration
-// (not the dword-scaled 1024-thread space-time family: measured 1-2% slower with it, r06g)
-#ifndef QLDPC_M2S_XMASK
-#define QLDPC_M2S_XMASK 1
-#endif
 #include "bp_slot.h"
 
 namespace qldpc {
 
-// Engine ids of this file: 3, 4, and 13 = engine 3 with dword-scaled edge
-// addresses (images of 64-256 KiB: the space-time graphs); + 100 = engine 3
-// keeping its own previous v2c in VGPRs in double precision too (the fp64
-// kernels built for <= 256-thread workgroups, whose register budget is 256).
+// Engine ids (the ENG template argument): engine 3 and its digits.
+//   units            3
+//   tens             1 = dword-scaled edge addresses (images of 64-256 KiB: the space-time graphs)
+//   hundreds         1 = own previous v2c in VGPRs in double precision too, edge addresses split and
+//                        absolute (the fp64 kernels built for <= 256-thread workgroups, whose register
+//                        budget is 256); 2 = the same with packed absolute addresses (RState::kPk);
+//                        3 = own v2c in VGPRs, addresses neither split nor packed (the fp64
+//                        space-time m2s family)
+//   thousands        1 = tail layout (eng_tail)
+//   ten thousands    1 = m2 in slot (eng_m2s), 2 = byte F (eng_fb)
+//   hundred thousands  D2K (eng_d2k)
 constexpr int eng_base(int E) { return E % 10; }
 constexpr int eng_sh(int E) { return (E / 10) % 10 ? 2 : 0; }
 constexpr bool eng_kv64(int E) { return (E / 100) % 10 != 0; }
 // + 1000 = rows of NCH chunks plus one "tail" slot per row in a separate array (rows one
-// message wider than the chunks: the fp64 space-time graphs, 8 + 1 slots), engine 3 only
+// message wider than the chunks: the fp64 space-time graphs, 8 + 1 slots)
 constexpr int eng_tail(int E) { return (E / 1000) % 10; }
 // + 10000 = "m2 in slot" (fp64 <= 256-thread family with tail rows, engine id 11103): the check
 // state is ONE word per check, CS = {m1 | parity << 63}, and the check phase stores m2 | parity in
@@ -125,31 +56,14 @@ constexpr int eng_tail(int E) { return (E / 1000) % 10; }
 // no longer holds the edge's own previous v2c (kept in VGPRs) is the argmin, and its value is m2.
 // The image shrinks by 8 bytes per check; with rows of 7 as 3 chunks + a tail slot the n1600 fp64
 // image is 52.3 KB, so 3 workgroups share a CU (168-VGPR budget).
-constexpr bool eng_m2s(int E) { return (E / 10000) % 10 == 1 || (E / 10000) % 10 == 4; }
-// + 40000 = m2s with variable-major v2c slots ("m2v", engine id 40103): edge (k, d) of lane t owns
-// V slot (ecnt(k) + d) * LB + t (the last variable slot: ecnt * LB + d * NL + t), so the variable
-// phase reads and writes its slots lane-linearly (conflict-free, one base VGPR and immediate
-// offsets), and the check phase gathers its row's 7 slots from a per-thread register table
-constexpr bool eng_m2v(int E) { return (E / 10000) % 10 == 4; }
 // m2s + tail + dword-scaled packed addresses + 300 (own v2c in VGPRs, neither split nor byte-packed)
 // = engine id 11313 (+ 100000 * D2K): the fp64 space-time family (rows of 4 chunks + a tail slot,
 // 1024-thread workgroups, 128-VGPR budget, kern_r_f64_m2st.hip), round 6
-// edge slots of variable slots 0..k-1 (degree-3 slots k < D3K keep 3)
-template <int D3K>
-__host__ __device__ constexpr int m2v_ecnt(int k) { return 3 * (k < D3K ? k : D3K) + 4 * (k > D3K ? k - D3K : 0); }
-// rows per thread the m2v check phase keeps in its register table (host-enforced m <= 4 * TB)
-constexpr int kM2vRows = 4;
+constexpr bool eng_m2s(int E) { return (E / 10000) % 10 == 1; }
 // + 20000 = byte F ("fb": the per-check flags F as one byte per check instead of a word, flips
 // xored into the containing word at the byte's shift): the fp32 space-time tail family for 512-thread
 // workgroups (engine id 21013), whose 79.6 KB image lets 2 decodes share a CU
 constexpr bool eng_fb(int E) { return (E / 10000) % 10 == 2; }
-// + 30000 = "c2v in slot" (fp64 <= 256-thread family with tail rows, engine id 31103): the check
-// phase writes each edge's c2v into the edge's own V slot (alpha * m1 with the edge's sign for
-// every edge, then one ds_xor_b64 turns the argmin edge's word into alpha * m2 with its sign), so
-// the variable phase reads one word per edge and keeps neither a check-state array nor its own
-// previous v2c; the F word addresses of the edges are held in VGPRs instead of the CS addresses.
-// Every row must hold exactly 2 * NCH + 1 edges (no padding slot is overwritten).
-constexpr bool eng_c2s(int E) { return (E / 10000) % 10 == 3; }
 // + 100000 * D2K (byte-F family): slots k < D2K hold variables of column degree <= 2 (the
 // space-time graphs' measurement variables, host-sorted first): no third edge slot kept
 constexpr int eng_d2k(int E) { return (E / 100000) % 10; }
@@ -161,25 +75,22 @@ constexpr int eng_d2k(int E) { return (E / 100000) % 10; }
 // CS[0] / the shared V dummy, unused): branches around them too split the variable phase into basic
 // blocks the scheduler cannot overlap (+2.7 % instead of the edge count's 7.7 %, twice the SALU, 3x
 // the branches; one variable phase compiled per narrow mask instead spills, profiles/r06/config5/)
-constexpr bool eng_nw(int E) { return eng_m2s(E) && !eng_m2v(E) && eng_tail(E) && eng_sh(E) == 2; }
+constexpr bool eng_nw(int E) { return eng_m2s(E) && eng_tail(E) && eng_sh(E) == 2; }
 constexpr int kNwSlots = 2;
-// edge slot t of variable slot k is compile-time absent (m2s / c2s / byte-F kernels)
+// edge slot t of variable slot k is compile-time absent (m2s / byte-F kernels)
 template <int ENG, int D3K>
 __device__ constexpr bool no_edge(int k, int t) {
-  return (eng_m2s(ENG) || eng_c2s(ENG) || eng_fb(ENG)) && ((k < D3K && t >= 3) || (k < eng_d2k(ENG) && t >= 2));
+  return (eng_m2s(ENG) || eng_fb(ENG)) && ((k < D3K && t >= 3) || (k < eng_d2k(ENG) && t >= 2));
 }
-// the one-word / no-word check-state families share the register layout and the shot setup
-constexpr bool eng_m2x(int E) { return eng_m2s(E) || eng_c2s(E); }
 // launch bounds: LB threads per workgroup at most; 256-thread fp64 kernels are
 // built for 2 workgroups per CU (2 waves per SIMD: up to 256 VGPRs, no spills)
 template <typename T, int ENG>
 constexpr int lb_waves(int LB) {
-  // engine 4 fp64 images (no CS array) fit 3 workgroups per CU: <= 168 VGPRs
-  // (the fp64 512-thread family: 2 workgroups of 8 waves per CU, 128 VGPRs)
+  // (the one-word family, m2s: 3 workgroups per CU, <= 168 VGPRs)
   // (the one-word family with packed addresses, engine id 10203: 4 workgroups per CU, 128 VGPRs)
-  return LB <= 256 ? (sizeof(T) == 8 ? (eng_m2s(ENG) && (ENG / 100) % 10 == 2 ? 4
-                                        : (eng_base(ENG) == 4 || eng_m2x(ENG)) ? 3 : 2) : 4)
-                   : (LB <= 512 && (eng_kv64(ENG) || eng_fb(ENG))) ? 4 : 1;
+  // (the byte-F family: 2 workgroups of 8 waves per CU, 128 VGPRs)
+  return LB <= 256 ? (sizeof(T) == 8 ? (eng_m2s(ENG) ? ((ENG / 100) % 10 == 2 ? 4 : 3) : 2) : 4)
+                   : (LB <= 512 && eng_fb(ENG)) ? 4 : 1;
 }
 __device__ inline unsigned long long qstamp() {
 #if QLDPC_STAMPS
@@ -198,19 +109,22 @@ template <int ENG>
 __device__ inline uint32_t ea_v(uint32_t ea) { return (ea >> 16) << eng_sh(ENG); }
 
 struct RLayout {
-  uint32_t v, t, f, sink, lred, total;  // byte offsets (engine 3: CS at 0; engine 4: V at 0)
+  uint32_t v, t, f, lred, total;  // byte offsets (CS at 0)
 };
 
-// [CS][V][tail: one slot per row label (tail layouts only)][F][sink][lred]
-// (m2s = 1: CS entries of one message word instead of two; m2s = 2, c2s: no CS array)
+// [CS][V][tail: one slot per row label (tail layouts only)][F][lred]
+// (m2s: CS entries of one message word instead of two)
+// `eng` is always 3.  It and its arm are what is left of the removed engine 4 (no CS array): with
+// them folded away the compiler orders the layout arithmetic of the kernel prologues differently in
+// the two translation units that hold two engine ids (kern_r_f64_m2s8.hip, kern_r_f64_st.hip), and
+// they stay so that every kernel's code stays what it was
 __host__ __device__ inline RLayout r_layout(int eng, int vslots, int mmax, int tsize, int tail = 0, int m2s = 0,
                                             int fb = 0) {
   RLayout L;
-  L.v = eng == 4 ? 0u : (uint32_t)a16((size_t)(mmax + 1) * (m2s == 2 ? 0 : m2s ? 1 : 2) * tsize);
+  L.v = eng == 4 ? 0u : (uint32_t)a16((size_t)(mmax + 1) * (m2s ? 1 : 2) * tsize);
   L.t = L.v + (uint32_t)a16((size_t)vslots * tsize);
   L.f = L.t + (tail ? (uint32_t)a16((size_t)mmax * tsize) : 0u);
-  L.sink = L.f + (uint32_t)a16((size_t)(mmax + 1) * (fb ? 1 : 4));
-  L.lred = L.sink + (eng == 4 ? 16u : 0u);
+  L.lred = L.f + (uint32_t)a16((size_t)(mmax + 1) * (fb ? 1 : 4));
   L.total = L.lred + 48;
   return L;
 }
@@ -277,37 +191,13 @@ __device__ inline void lds_st(unsigned char* smem, uint32_t a, X v) {
     lds_at<X>(smem, a) = v;
   }
 }
-// LDS atomic xor (no return) at an absolute address
-__device__ inline void lds_xor_abs(uint32_t a, uint32_t v) {
-  __hip_atomic_fetch_xor((LdsPtr<uint32_t>)(uintptr_t)a, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
-// canonical bits: |v| with the sign bit := (v <= 0).  Only +0 differs from the
-// raw bits (-0 and negatives already carry the sign bit; NaN never occurs).
-// Branch- and VCC-free form: b | ((b - 1) & ~b & sign) sets the sign bit only
-// for b == 0 (one add and one three-input bit op; no compare hazard nops).
-template <typename T>
-__device__ inline typename FT<T>::U canon2(T v) {
-  using U = typename FT<T>::U;
-  const U b = FT<T>::bits(v);
-  if constexpr (sizeof(T) == 8) {
-    // hi | (hi(b - 1) & sign): `& ~b` is implied (a set sign bit is kept anyway);
-    // one 64-bit add and one v_and_or
-    const U bm = b - (U)1;
-    uint32_t hi;
-    asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(hi) : "v"((uint32_t)(bm >> 32)), "v"(0x80000000u), "v"((uint32_t)(b >> 32)));
-    return ((U)hi << 32) | (uint32_t)b;
-  } else {
-    return b | ((b - (U)1) & ~b & FT<T>::kSign);
-  }
-}
 
 // Engine 3 keeps its messages NEGATED ("w domain"): w = -v for every prior, v2c and c2v,
 // except that a zero prior is +0.  Then every w is either exactly -v (v != 0) or +0 (v
 // == 0: an exact cancellation rounds to +0, and a sum is -0 only when all its leaves are
 // -0, which a +0-or-nonzero prior rules out), so the sign bit of w is exactly NOT the
 // canonical sign (v <= 0) the min-sum parity needs: the v2c leave-one-out sums are stored
-// as they come out of the adds (no canon2 per edge), the decision is w >= 0, and the
+// as they come out of the adds (no canon per edge, bp_slot.h), the decision is w >= 0, and the
 // check phase flips its parity by the row degree (F bit 2, folded into the syndrome bit it
 // keeps per row), which turns the xor of the w signs back into the xor of the canonical
 // ones.  -w is the c2v product with the same sign rule, so the c2v arithmetic is unchanged.
@@ -334,21 +224,12 @@ __device__ inline uint32_t wave_xor_u32(uint32_t v) {
 __device__ inline bool is_zero(float x) { return __builtin_amdgcn_classf(x, 0x60); }
 __device__ inline bool is_zero(double x) { return __builtin_amdgcn_class(x, 0x60); }
 
-// median of three (the backend selects v_med3_u32 for this pattern)
-__device__ inline uint32_t med3u(uint32_t a, uint32_t b, uint32_t c) {
-  const uint32_t lo = a < b ? a : b, hi = a < b ? b : a;
-  const uint32_t h2 = hi < c ? hi : c;
-  return lo > h2 ? lo : h2;
-}
-
-// Register state of one thread in one sector pass.  Edge words: engine 3 =
-// CS address | V slot address << 16; engine 4 = read address | write address
-// << 16 (equal for real edges; zero chunk / sink for missing ones).
+// Register state of one thread in one sector pass.  Edge words: CS address | V slot
+// address << 16.
 template <typename T, int DMAX, int VPL, int ENG = 3>
 struct RState {
   using U = typename FT<T>::U;
-  static constexpr bool kKeepV =
-      eng_base(ENG) == 3 && (sizeof(T) == 4 || eng_kv64(ENG)) && !eng_c2s(ENG);  // own v2c in VGPRs
+  static constexpr bool kKeepV = sizeof(T) == 4 || eng_kv64(ENG);  // own v2c in VGPRs
   // the fp64 <= 256-thread family (256-VGPR budget) keeps the two addresses of an edge
   // unpacked and absolute (ea = CS address, ev = V slot address): no unpack / base add
   // per access, 2 VALU per edge and iteration fewer
@@ -356,40 +237,19 @@ struct RState {
   // + 200 instead of + 100 on the one-word family (engine id 10203): the edge's CS and V slot byte
   // addresses packed absolute into one VGPR (images < 64 KiB), unpacked by one VALU each per access:
   // 16 fewer VGPRs for 16 edges per thread (LP L30: 4 workgroups per CU instead of 3)
-  static constexpr bool kPk = (ENG / 100) % 10 == 2 && sizeof(T) == 8 && eng_m2s(ENG) && !eng_m2v(ENG);
+  static constexpr bool kPk = (ENG / 100) % 10 == 2 && sizeof(T) == 8 && eng_m2s(ENG);
   // absolute LDS addresses: split words, or (dword-scaled packed words: the space-time families
   // 13 / 1013 / 21013) absolute dword indices, unpacked by one SDWA shift per access and used
   // without a base add
-  static constexpr bool kAbs = kSplit || kPk || (eng_sh(ENG) == 2 && QLDPC_ABS_SH2);
-  // m2s with QLDPC_M2S_UNIL: one prior for every variable (uniform channel_probs, host-checked),
-  // loaded by a scalar load: 2 SGPRs instead of 2 * VPL VGPRs
-  static constexpr bool kUniL = eng_m2x(ENG) && QLDPC_M2S_UNIL;
-  static constexpr bool kM2v = eng_m2v(ENG);
+  static constexpr bool kAbs = kSplit || kPk || eng_sh(ENG) == 2;
+  // m2s: one prior for every variable (uniform channel_probs, host-checked), loaded by a scalar
+  // load: 2 SGPRs instead of 2 * VPL VGPRs
+  static constexpr bool kUniL = eng_m2s(ENG);
   uint32_t ea[VPL][DMAX];
-  uint32_t ev[kSplit && !kM2v ? VPL : 1][kSplit && !kM2v ? DMAX : 1];
+  uint32_t ev[kSplit ? VPL : 1][kSplit ? DMAX : 1];
   T L[kUniL ? 1 : VPL];
   U ov[kKeepV ? VPL : 1][kKeepV ? DMAX : 1];
-  // m2v: lane base of the V slots and the last variable slot's per-edge addresses
-  uint32_t vlane;
-  uint32_t vl[kM2v ? DMAX : 1];
 };
-// m2v row table of one thread: row q (check tid + q * TB) = 7 16-bit slot offsets from the V base,
-// two per word; loaded from global memory before the barrier that precedes each check phase
-// (registers live across that barrier only)
-struct M2vRows {
-  uint4 w[kM2vRows];
-};
-__device__ inline void m2v_rows_load(const SSector& S, int tid, int TB, int m, M2vRows& r) {
-#pragma unroll
-  for (int q = 0; q < kM2vRows; ++q)
-    if (q * TB < m) r.w[q] = reinterpret_cast<const uint4*>(S.rows)[(size_t)q * TB + tid];
-}
-// m2v: absolute V slot address of edge (k, t) (immediate offsets from the lane base)
-template <typename T, int DMAX, int VPL, int ENG, int D3K, int LB>
-__device__ inline uint32_t m2v_va(const RState<T, DMAX, VPL, ENG>& R, int k, int t) {
-  if (k < VPL - 1) return R.vlane + (uint32_t)((m2v_ecnt<D3K>(k) + t) * LB * 8);
-  return R.vl[RState<T, DMAX, VPL, ENG>::kM2v ? t : 0];
-}
 // 4 * (16-bit half h of w) in one VALU (SDWA word select feeding the shift)
 template <int H, int SH>
 __device__ inline uint32_t sdwa_shl(uint32_t w) {
@@ -436,12 +296,9 @@ __device__ inline void r_load(const SSector& S, RState<T, DMAX, VPL, ENG>& R, co
     for (int t = 0; t < DMAX; ++t) {
       const uint32_t e = S.edges[(k * DMAX + t) * TB + tid];
       const uint32_t va = Ly.v + eslot(e) * (uint32_t)sizeof(T);
-      if (eng_base(ENG) == 4) {
-        R.ea[k][t] = e == kNoEdgeS ? (Ly.v | (Ly.sink << 16)) : (va | (va << 16));
-      } else if constexpr (RState<T, DMAX, VPL, ENG>::kSplit) {
-        // c2s: the absolute address of the edge's F word (entry = check label + 1)
-        R.ea[k][t] = eng_c2s(ENG) ? sbase + Ly.f + 4u * echk(e) : sbase + echk(e) * (uint32_t)((eng_m2s(ENG) ? 1 : 2) * sizeof(T));
-        if constexpr (!RState<T, DMAX, VPL, ENG>::kM2v) R.ev[k][t] = sbase + va;
+      if constexpr (RState<T, DMAX, VPL, ENG>::kSplit) {
+        R.ea[k][t] = sbase + echk(e) * (uint32_t)((eng_m2s(ENG) ? 1 : 2) * sizeof(T));
+        R.ev[k][t] = sbase + va;
       } else if constexpr (RState<T, DMAX, VPL, ENG>::kPk) {  // absolute byte addresses, packed
         R.ea[k][t] = (sbase + echk(e) * (uint32_t)sizeof(T)) | ((sbase + va) << 16);
       } else if constexpr (RState<T, DMAX, VPL, ENG>::kAbs) {  // absolute dword indices
@@ -453,40 +310,19 @@ __device__ inline void r_load(const SSector& S, RState<T, DMAX, VPL, ENG>& R, co
     }
     if constexpr (!RState<T, DMAX, VPL, ENG>::kUniL) {
       const T l = (S.perm[k * TB + tid] >= 0) ? llr[k * TB + tid] : (T)1;
-      R.L[k] = eng_base(ENG) == 3 ? w_prior<T>(l) : l;  // engine 3: w domain
+      R.L[k] = w_prior<T>(l);  // w domain
     }
   }
   // uniform prior (slot 0 of lane 0 holds a real variable); padding lanes take it too (their
   // results are never read)
   if constexpr (RState<T, DMAX, VPL, ENG>::kUniL) R.L[0] = w_prior<T>(llr[0]);
-  if constexpr (RState<T, DMAX, VPL, ENG>::kM2v) {
-    // lane base (LDS addresses are < 64 KiB: the mask makes the sign bit known, so the per-edge
-    // offsets fold into the DS instructions' offset fields); the last variable slot strides S.vnl
-    R.vlane = (sbase + Ly.v + 8u * (uint32_t)tid) & 0xFFFFu;
-    const uint32_t last = (uint32_t)S.vlast * 8u;  // byte offset of the last slot's first edge
-#pragma unroll
-    for (int t = 0; t < DMAX; ++t) R.vl[t] = R.vlane + last + (uint32_t)t * (uint32_t)S.vnl * 8u;
-  }
 }
 template <typename T, int DMAX, int VPL, int ENG>
 __device__ inline T r_prior(const RState<T, DMAX, VPL, ENG>& R, int k) {
   return R.L[RState<T, DMAX, VPL, ENG>::kUniL ? 0 : k];
 }
 
-// F word of an edge.  Engine 3: from the CS address.  Engine 4: from the row
-// of the read address (rows start 16 bytes into V, row stride 1 << rsh); the
-// zero chunk maps to row -1, i.e. the F[0] sink.
-struct FMap {
-  uint32_t fbase;   // engine 3: Ly.f; engine 4: Ly.f + 4
-  uint32_t rstart;  // engine 4: Ly.v + 16
-  int rsh;          // engine 4: log2(row stride)
-};
-template <typename T, int ENG>
-__device__ inline uint32_t f_addr(uint32_t ea, const FMap& M) {
-  if (eng_base(ENG) == 4) return M.fbase + 4u * (uint32_t)((int)((ea & 0xFFFFu) - M.rstart) >> M.rsh);
-  return (ea_cs<ENG>(ea) >> (sizeof(T) == 4 ? 1 : 2)) + M.fbase;
-}
-// F entry access (engine 3): entry e (= check label + 1) at byte Ly.f + 4e, or Ly.f + e in byte-F
+// F entry access: entry e (= check label + 1) at byte Ly.f + 4e, or Ly.f + e in byte-F
 // kernels, whose xors go to the containing word at the byte's shift (order-free, so still atomic
 // and commutative) and whose plain stores are byte stores (one owner per byte)
 template <int ENG>
@@ -513,7 +349,7 @@ __device__ inline void f_xor(unsigned char* smem, uint32_t off, uint32_t v) {
     atomicXor(&lds_at<uint32_t>(smem, off), v);
 }
 
-// F word offset of edge (k, t) (engine 3); split addresses are absolute: fbase is then
+// F word offset of edge (k, t); split addresses are absolute: fbase is then
 // Ly.f - (LDS base >> 2)
 template <typename T, int DMAX, int VPL, int ENG>
 __device__ inline uint32_t r_fa(const RState<T, DMAX, VPL, ENG>& R, int k, int t, uint32_t fbase) {
@@ -544,8 +380,7 @@ __device__ inline void r_launder(RState<T, DMAX, VPL, ENG>& R) {
     for (int t = 0; t < DMAX; ++t) {
       if (no_edge<ENG, D3K>(k, t)) continue;
       asm volatile("" : "+v"(R.ea[k][t]));
-      if constexpr (RState<T, DMAX, VPL, ENG>::kSplit && !RState<T, DMAX, VPL, ENG>::kM2v)
-        asm volatile("" : "+v"(R.ev[k][t]));
+      if constexpr (RState<T, DMAX, VPL, ENG>::kSplit) asm volatile("" : "+v"(R.ev[k][t]));
     }
 }
 
@@ -573,27 +408,20 @@ __device__ inline bool r_var_one(unsigned char* smem, RState<T, DMAX, VPL, ENG>&
                                  const typename FT<T>::U (&o)[DMAX], uint32_t fdelta, T alpha, bool xprev,
                                  double* post, const int32_t* perm) {
   using U = typename FT<T>::U;
-  constexpr U kS = FT<T>::kSign;
   constexpr bool KV = RState<T, DMAX, VPL, ENG>::kKeepV;
   T c[ND];
 #pragma unroll
   for (int t = 0; t < ND; ++t) {
     const U a = pr[t].a;
-    const U d = a ^ o[t];
     // min over the other edges: m2 if this edge holds m1 (|own| == m1), else m1;
-    // sign = parity of the others and the syndrome = sign bit of d
-    // (m2 carries no sign bit, so masking after the select is the same value;
-    // masking `a` before it trips an instruction-selection crash in this LLVM).
-    // |d| == 0 is tested with v_cmp_class (+-0 only): one instruction instead of
-    // mask + compare (bit patterns of any class, denormals and NaNs included).
-    U sel;
-    if constexpr (sizeof(T) == 4 && QLDPC_F32_C2V4) {
-      // 4 VALU: |own| == |m1| by v_cmp_eq_f32 on the absolute values (the magnitude-bits test of
-      // the class form: denormals compare exactly, no flush; NaN never occurs), select m1 | parity
-      // or m2 | parity (the check phase stores both with the parity), and the own sign rides on
-      // alpha: (alpha ^ own sign) * sel has sign parity ^ own and magnitude |sel| * alpha
-      // (sign-symmetric rounding), the value of the class form bit for bit, zeros included
-      (void)d;
+    // sign = parity of the others and the syndrome = sign bit of a ^ own
+    if constexpr (sizeof(T) == 4) {
+      // 4 VALU: |own| == |m1| by v_cmp_eq_f32 on the absolute values (a magnitude-bits test:
+      // denormals compare exactly, no flush; NaN never occurs), select m1 | parity or m2 | parity
+      // (the check phase stores both with the parity), and the own sign rides on alpha:
+      // (alpha ^ own sign) * sel has sign parity ^ own and magnitude |sel| * alpha (sign-symmetric
+      // rounding), zeros included
+      U sel;
       asm("v_cmp_eq_f32 vcc, |%1|, |%2|\n\ts_nop 1\n\tv_cndmask_b32 %0, %3, %4, vcc"
           : "=v"(sel)
           : "v"(a), "v"(o[t]), "v"(a), "v"(pr[t].b)
@@ -603,21 +431,10 @@ __device__ inline bool r_var_one(unsigned char* smem, RState<T, DMAX, VPL, ENG>&
           : "=v"(as)
           : "v"((uint32_t)o[t]), "v"(FT<T>::bits(alpha)), "v"(0x80000000u));
       c[t] = FT<T>::val(sel) * FT<T>::val(as);
-    } else if constexpr (sizeof(T) == 4) {
-      // v_cmp_class (+-0) feeding v_cndmask; LLVM would rewrite the class test as
-      // mask + integer compare.  s_nop 1: the VALU-writes-VCC -> VALU-reads-VCC
-      // hazard the compiler itself pads on gfx950.
-      asm("v_cmp_class_f32 vcc, %1, %2\n\ts_nop 1\n\tv_cndmask_b32 %0, %3, %4, vcc"
-          : "=v"(sel)
-          : "v"(d), "v"(0x60u), "v"(a), "v"(pr[t].b)
-          : "vcc");
-      sel &= ~kS;
-      c[t] = FT<T>::val(FT<T>::bits(FT<T>::val(sel) * alpha) ^ (d & kS));
-    } else if constexpr (QLDPC_F64_C2V5) {
-      // double in 5 VALU (the class form takes 7: the 64-bit xor is 2): |own| == |m1| by
-      // v_cmp_eq_f64 on absolute values, two cndmasks select m1 | parity or m2 | parity, and the
-      // own sign rides on alpha's high word: (alpha ^ own sign) * sel, the same bits
-      (void)d;
+    } else {
+      // double in 5 VALU: |own| == |m1| by v_cmp_eq_f64 on absolute values, two cndmasks select
+      // m1 | parity or m2 | parity, and the own sign rides on alpha's high word:
+      // (alpha ^ own sign) * sel
       uint32_t slo, shi;
       asm("v_cmp_eq_f64 vcc, |%2|, |%3|\n\ts_nop 1\n\tv_cndmask_b32 %0, %4, %5, vcc\n\tv_cndmask_b32 %1, %6, %7, vcc"
           : "=&v"(slo), "=&v"(shi)
@@ -630,23 +447,6 @@ __device__ inline bool r_var_one(unsigned char* smem, RState<T, DMAX, VPL, ENG>&
           : "=v"(ahs)
           : "v"((uint32_t)(o[t] >> 32)), "v"((uint32_t)(ab >> 32)), "v"(0x80000000u));
       c[t] = FT<T>::val(((U)shi << 32) | slo) * FT<T>::val(((U)ahs << 32) | (uint32_t)ab);
-    } else {
-      // double: the same class test on the 64-bit pair and two cndmasks; |sel| folds
-      // into v_mul_f64's source modifier; sign = hi(product) ^ (hi(d) & sign bit) in
-      // one v_bitop3 (truth table 0x6c = S1 ^ (S0 & S2))
-      uint32_t slo, shi;
-      asm("v_cmp_class_f64 vcc, %2, %3\n\ts_nop 1\n\tv_cndmask_b32 %0, %4, %5, vcc\n\tv_cndmask_b32 %1, %6, %7, vcc"
-          : "=&v"(slo), "=&v"(shi)
-          : "v"(FT<T>::val(d)), "v"(0x60u), "v"((uint32_t)a), "v"((uint32_t)pr[t].b), "v"((uint32_t)(a >> 32)),
-            "v"((uint32_t)(pr[t].b >> 32))
-          : "vcc");
-      sel = ((U)shi << 32) | slo;
-      const U pb = FT<T>::bits(__builtin_fabs(FT<T>::val(sel)) * alpha);
-      uint32_t hi;
-      asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0x6c"
-          : "=v"(hi)
-          : "v"((uint32_t)(d >> 32)), "v"((uint32_t)(pb >> 32)), "v"(0x80000000u));
-      c[t] = FT<T>::val(((U)hi << 32) | (uint32_t)pb);
     }
   }
   // ldpc column pass: forward partial sums from the prior, then backward
@@ -664,7 +464,7 @@ __device__ inline bool r_var_one(unsigned char* smem, RState<T, DMAX, VPL, ENG>&
   }
   T b = c[ND - 1];
   U nv[ND];
-  nv[ND - 1] = FT<T>::bits(f[ND - 1]);  // w domain: stored as computed (no canon2)
+  nv[ND - 1] = FT<T>::bits(f[ND - 1]);  // w domain: stored as computed (no canon)
 #pragma unroll
   for (int t = ND - 2; t >= 0; --t) {
     nv[t] = FT<T>::bits(f[t] + b);
@@ -675,18 +475,10 @@ __device__ inline bool r_var_one(unsigned char* smem, RState<T, DMAX, VPL, ENG>&
     lds_st<U, RState<T, DMAX, VPL, ENG>::kAbs>(smem, r_va(R, k, t), nv[t]);
     if (KV) R.ov[KV ? k : 0][KV ? t : 0] = nv[t];
   }
-#if QLDPC_FLIPLATE
-  (void)xprev;  // flips applied by r_var after the loop
-#elif QLDPC_FLIP_BRANCHFREE
-  // diagnostic variant: every edge xors (x != xprev) into its check's F word, no branch
-#pragma unroll
-  for (int t = 0; t < ND; ++t) f_xor<ENG>(smem, r_fa(R, k, t, fdelta), (uint32_t)(x != xprev));
-#else
   if (x != xprev) {
 #pragma unroll
     for (int t = 0; t < ND; ++t) f_xor<ENG>(smem, r_fa(R, k, t, fdelta), 1u);
   }
-#endif
   return x;
 }
 
@@ -758,18 +550,6 @@ __device__ inline uint32_t r_var(unsigned char* smem, RState<T, DMAX, VPL, ENG>&
                                     : r_var_one<T, DMAX, VPL, DMAX, ENG>(smem, R, k, pr, o, fdelta, alpha, xp, post, pk);
     xbits |= (x ? 1u : 0u) << k;
   }
-#if QLDPC_FLIPLATE
-  const uint32_t fl = xbits ^ xprev;
-#pragma unroll
-  for (int k = 0; k < VPL; ++k) {
-    if ((fl >> k) & 1u) {
-      const int nd = k < eng_d2k(ENG) ? 2 : k < D3K ? N3 : DMAX;
-#pragma unroll
-      for (int t = 0; t < DMAX; ++t)
-        if (t < nd) f_xor<ENG>(smem, r_fa(R, k, t, fdelta), 1u);
-    }
-  }
-#endif
   return xbits;
 }
 
@@ -844,7 +624,7 @@ __device__ inline int r_check(unsigned char* smem, const RLayout& Ly, int m, int
     (void)alpha_next;
     typename CSEntry<T>::type st;
     st.a = m1 | (px & kS);
-    st.b = m2 | ((sizeof(T) == 4 ? QLDPC_F32_C2V4 : QLDPC_F64_C2V5) ? (px & kS) : (U)0);  // m2 | parity too
+    st.b = m2 | (px & kS);  // m2 | parity too (r_var_one's c2v)
     lds_at<typename CSEntry<T>::type>(smem, (uint32_t)(i + 1) * (uint32_t)(2 * sizeof(T))) = st;
   }
   return mism;
@@ -886,9 +666,9 @@ __device__ inline int r_check_c(unsigned char* smem, const RLayout& Ly, int m, i
 #pragma unroll
   for (int c = 0; c < NCH; ++c) coff[c] = kRot ? (((uint32_t)c + rot) & (uint32_t)(NCH - 1)) * 16u : (uint32_t)c * 16u;
   // rows are loaded PFC (1 or 2) rows ahead of the one being reduced
-  // (QLDPC_RC_RPTR: absolute LDS row / tail / CS addresses, as the m2s check phase's pointers; fp64
-  // only: the two-word tail family +1.5 %, the fp32 families -0.6 %, profiles/r06/rc_rptr/)
-  constexpr bool RP = QLDPC_RC_RPTR != 0 && sizeof(T) == 8;
+  // (absolute LDS row / tail / CS addresses, as the m2s check phase's pointers; fp64 only: the
+  // two-word tail family +1.5 %, the fp32 families -0.6 %, profiles/r06/rc_rptr/)
+  constexpr bool RP = sizeof(T) == 8;
   const uint32_t sbase = RP ? lds_base(smem) : 0u;
   auto load = [&](int r, VT (&v)[NCH], T& tv, uint32_t& fv) {
     if (r < m) {
@@ -958,7 +738,7 @@ __device__ inline int r_check_c(unsigned char* smem, const RLayout& Ly, int m, i
         px ^= (uint32_t)(FT<T>::bits(tcur) >> 32);
       }
       st.a = FT<T>::bits(f1) | ((U)(px & 0x80000000u) << 32);
-      st.b = FT<T>::bits(f2) | (QLDPC_F64_C2V5 ? ((U)(px & 0x80000000u) << 32) : (U)0);  // m2 | parity
+      st.b = FT<T>::bits(f2) | ((U)(px & 0x80000000u) << 32);  // m2 | parity
     } else {
       float f1 = FT<T>::val(FT<T>::kSent), f2 = f1;
       uint32_t px = s ? kS : 0u;
@@ -982,7 +762,7 @@ __device__ inline int r_check_c(unsigned char* smem, const RLayout& Ly, int m, i
         px ^= (uint32_t)FT<T>::bits(tcur);
       }
       st.a = FT<T>::bits(f1) | (px & kS);
-      st.b = FT<T>::bits(f2) | (QLDPC_F32_C2V4 ? (px & kS) : 0u);  // m2 | parity (r_var_one's 4-VALU c2v)
+      st.b = FT<T>::bits(f2) | (px & kS);  // m2 | parity (r_var_one's 4-VALU c2v)
     }
     if constexpr (RP) {
       lds_st<typename CSEntry<T>::type, true>(nullptr, sbase + (uint32_t)(i + 1) * (uint32_t)(2 * sizeof(T)), st);
@@ -1016,26 +796,28 @@ __device__ inline int r_check_c(unsigned char* smem, const RLayout& Ly, int m, i
 // v2c" marks the argmin and c2v = alpha * m2, else alpha * m1.  Same values as ldpc's "m2 if
 // |own| == m1 else m1": with a tie m1 == m2; a slot equal to the own word by chance has
 // m2 == m1 and the own sign == parity, i.e. the same c2v either way.
-constexpr bool m_xmask(int eng) { return QLDPC_M2S_XMASK && eng_sh(eng) != 2; }
+// each variable slot's previous decisions as a wave lane mask (SGPRs): the flip test is a scalar
+// xor of two masks instead of a bit extract and compare per variable and iteration (not the
+// dword-scaled 1024-thread space-time family: measured 1-2% slower with it, r06g)
+constexpr bool m_xmask(int eng) { return eng_sh(eng) != 2; }
 
-// the V slot address a gather computed is kept for the store (m_keepva): the sdwa unpack is an asm
-// statement, which the backend cannot rematerialize once the value passes through an opaque copy
+// dword-scaled words (space-time family 111313): the V slot address a gather computed is kept for
+// the store (one SDWA per edge and iteration fewer): the sdwa unpack is an asm statement, which the
+// backend cannot rematerialize once the value passes through an opaque copy
 template <typename T, int DMAX, int VPL, int ENG>
 constexpr bool m_keepva() {
-  return QLDPC_M2S_KEEPVA && eng_m2s(ENG) && !eng_m2v(ENG) && !eng_c2s(ENG) && eng_sh(ENG) == 2 &&
+  return eng_m2s(ENG) && eng_sh(ENG) == 2 &&
          RState<T, DMAX, VPL, ENG>::kAbs && !RState<T, DMAX, VPL, ENG>::kSplit && !RState<T, DMAX, VPL, ENG>::kPk;
 }
 
-template <typename T, int DMAX, int VPL, int ND, int ENG, int D3K = 0, int LB = 256>
+template <typename T, int DMAX, int VPL, int ND, int ENG>
 __device__ inline void m_gather(const RState<T, DMAX, VPL, ENG>& R, int k, typename FT<T>::U (&an)[DMAX],
                                 typename FT<T>::U (&vn)[DMAX], uint32_t (&va)[DMAX]) {
   using U = typename FT<T>::U;
 #pragma unroll
   for (int t = 0; t < ND; ++t) {
-    if constexpr (!eng_c2s(ENG)) an[t] = lds_ld<U, true>(nullptr, r_csa(R, k, t));  // (c2s: ea = F word)
-    if constexpr (eng_m2v(ENG)) {
-      vn[t] = lds_ld<U, true>(nullptr, m2v_va<T, DMAX, VPL, ENG, D3K, LB>(R, k, t));
-    } else if constexpr (m_keepva<T, DMAX, VPL, ENG>()) {
+    an[t] = lds_ld<U, true>(nullptr, r_csa(R, k, t));
+    if constexpr (m_keepva<T, DMAX, VPL, ENG>()) {
       uint32_t a = r_va(R, k, t);
       asm volatile("" : "+v"(a));
       va[t] = a;
@@ -1046,23 +828,18 @@ __device__ inline void m_gather(const RState<T, DMAX, VPL, ENG>& R, int k, typen
   }
 }
 
-template <typename T, int DMAX, int VPL, int ND, int ENG, int D3K = 0, int LB = 256>
+template <typename T, int DMAX, int VPL, int ND, int ENG>
 __device__ inline bool m_var_one(unsigned char* smem, RState<T, DMAX, VPL, ENG>& R, int k,
                                  const typename FT<T>::U (&an)[DMAX],
                                  const typename FT<T>::U (&vn)[DMAX], const uint32_t (&va)[DMAX], uint32_t fdelta,
                                  T alpha, bool xprev, uint64_t& xmk, double* post, const int32_t* perm) {
   using U = typename FT<T>::U;
-  constexpr bool KV1 = RState<T, DMAX, VPL, ENG>::kKeepV;
-  static_assert(sizeof(T) == 8 && RState<T, DMAX, VPL, ENG>::kAbs && (RState<T, DMAX, VPL, ENG>::kKeepV || eng_c2s(ENG)),
-                "m2s / c2s: fp64 absolute-address families only");
+  static_assert(sizeof(T) == 8 && RState<T, DMAX, VPL, ENG>::kAbs && RState<T, DMAX, VPL, ENG>::kKeepV,
+                "m2s: fp64 absolute-address families only");
   T c[ND];
 #pragma unroll
   for (int t = 0; t < ND; ++t) {
-    if constexpr (eng_c2s(ENG)) {  // the slot holds this edge's c2v (c2s_check)
-      c[t] = FT<T>::val(vn[t]);
-      continue;
-    }
-    const U o = R.ov[KV1 ? k : 0][KV1 ? t : 0];
+    const U o = R.ov[k][t];
     // argmin edge <=> its slot no longer holds our own previous v2c: m2 | parity, else m1 | parity
     const U sel = vn[t] != o ? vn[t] : an[t];
     // sign(sel) = parity; sel * alpha is exactly +-(|sel| * alpha) (IEEE rounding is sign-symmetric),
@@ -1097,13 +874,11 @@ __device__ inline bool m_var_one(unsigned char* smem, RState<T, DMAX, VPL, ENG>&
   }
 #pragma unroll
   for (int t = 0; t < ND; ++t) {
-    if constexpr (eng_m2v(ENG))
-      lds_st<U, true>(nullptr, m2v_va<T, DMAX, VPL, ENG, D3K, LB>(R, k, t), nv[t]);
-    else if constexpr (m_keepva<T, DMAX, VPL, ENG>())
+    if constexpr (m_keepva<T, DMAX, VPL, ENG>())
       lds_st<U, true>(nullptr, va[t], nv[t]);
     else
       lds_st<U, true>(nullptr, r_va(R, k, t), nv[t]);
-    if constexpr (KV1) R.ov[k][t] = nv[t];
+    R.ov[k][t] = nv[t];
   }
   bool flip;
   if constexpr (m_xmask(ENG)) {  // (every lane active here: the variable phase is not divergent)
@@ -1115,17 +890,12 @@ __device__ inline bool m_var_one(unsigned char* smem, RState<T, DMAX, VPL, ENG>&
   }
   if (flip) {
 #pragma unroll
-    for (int t = 0; t < ND; ++t) {
-      if constexpr (eng_c2s(ENG))
-        lds_xor_abs(R.ea[k][t], 1u);
-      else
-        atomicXor(&lds_at<uint32_t>(smem, r_fa(R, k, t, fdelta)), 1u);
-    }
+    for (int t = 0; t < ND; ++t) atomicXor(&lds_at<uint32_t>(smem, r_fa(R, k, t, fdelta)), 1u);
   }
   return x;
 }
 
-template <typename T, int DMAX, int VPL, int D3K, int ENG, int LB = 256>
+template <typename T, int DMAX, int VPL, int D3K, int ENG>
 __device__ inline uint32_t m_var(unsigned char* smem, RState<T, DMAX, VPL, ENG>& R, uint32_t fdelta, T alpha, uint32_t xprev,
                                  uint64_t (&xm)[VPL], bool last_live, double* post = nullptr, const int32_t* perm = nullptr,
                                  int TB = 0, uint32_t nwm = 0) {
@@ -1133,8 +903,7 @@ __device__ inline uint32_t m_var(unsigned char* smem, RState<T, DMAX, VPL, ENG>&
   constexpr int N3 = DMAX > 3 ? 3 : DMAX;
   // gathers one variable ahead: two ahead needs 32 more VGPRs than the 168 of 3 workgroups per
   // CU and spills (n1600: 849k vs 1.13M shots/s, profiles/r03/m2s_ab/)
-  // c2s keeps no own v2c (48 VGPRs fewer): QLDPC_C2S_PF variables ahead
-  constexpr int PF0 = eng_c2s(ENG) ? QLDPC_C2S_PF : QLDPC_PF >= 1 ? QLDPC_PF : 1;
+  constexpr int PF0 = QLDPC_PF >= 1 ? QLDPC_PF : 1;
   constexpr int PF = PF0 < VPL ? PF0 : VPL;
   r_launder<T, DMAX, VPL, ENG, D3K>(R);
   uint32_t xbits = 0;
@@ -1142,11 +911,11 @@ __device__ inline uint32_t m_var(unsigned char* smem, RState<T, DMAX, VPL, ENG>&
   uint32_t vab[PF][DMAX];
   auto gk = [&](int k, U (&an)[DMAX], U (&vn)[DMAX], uint32_t (&va)[DMAX]) {
     if (k < eng_d2k(ENG))  // (the space-time family's measurement variables: two edge slots)
-      m_gather<T, DMAX, VPL, 2, ENG, D3K, LB>(R, k, an, vn, va);
+      m_gather<T, DMAX, VPL, 2, ENG>(R, k, an, vn, va);
     else if (k < D3K)
-      m_gather<T, DMAX, VPL, N3, ENG, D3K, LB>(R, k, an, vn, va);
+      m_gather<T, DMAX, VPL, N3, ENG>(R, k, an, vn, va);
     else
-      m_gather<T, DMAX, VPL, DMAX, ENG, D3K, LB>(R, k, an, vn, va);
+      m_gather<T, DMAX, VPL, DMAX, ENG>(R, k, an, vn, va);
   };
 #pragma unroll
   for (int k = 0; k < PF; ++k) gk(k, ab[k], vb[k], vab[k]);
@@ -1167,13 +936,13 @@ __device__ inline uint32_t m_var(unsigned char* smem, RState<T, DMAX, VPL, ENG>&
     bool x;
     // (narrow waves: bit k of the wave-uniform nwm = this wave computes slot k one edge slot narrower)
     if (eng_nw(ENG) && k < kNwSlots && ((nwm >> k) & 1u))
-      x = k < eng_d2k(ENG) ? m_var_one<T, DMAX, VPL, 1, ENG, D3K, LB>(smem, R, k, an, vn, va, fdelta, alpha, xp, xm[k], post, pk)
-          : k < D3K        ? m_var_one<T, DMAX, VPL, (N3 > 1 ? N3 - 1 : 1), ENG, D3K, LB>(smem, R, k, an, vn, va, fdelta, alpha, xp, xm[k], post, pk)
-                           : m_var_one<T, DMAX, VPL, (DMAX > 1 ? DMAX - 1 : 1), ENG, D3K, LB>(smem, R, k, an, vn, va, fdelta, alpha, xp, xm[k], post, pk);
+      x = k < eng_d2k(ENG) ? m_var_one<T, DMAX, VPL, 1, ENG>(smem, R, k, an, vn, va, fdelta, alpha, xp, xm[k], post, pk)
+          : k < D3K        ? m_var_one<T, DMAX, VPL, (N3 > 1 ? N3 - 1 : 1), ENG>(smem, R, k, an, vn, va, fdelta, alpha, xp, xm[k], post, pk)
+                           : m_var_one<T, DMAX, VPL, (DMAX > 1 ? DMAX - 1 : 1), ENG>(smem, R, k, an, vn, va, fdelta, alpha, xp, xm[k], post, pk);
     else
-      x = k < eng_d2k(ENG) ? m_var_one<T, DMAX, VPL, 2, ENG, D3K, LB>(smem, R, k, an, vn, va, fdelta, alpha, xp, xm[k], post, pk)
-          : k < D3K        ? m_var_one<T, DMAX, VPL, N3, ENG, D3K, LB>(smem, R, k, an, vn, va, fdelta, alpha, xp, xm[k], post, pk)
-                           : m_var_one<T, DMAX, VPL, DMAX, ENG, D3K, LB>(smem, R, k, an, vn, va, fdelta, alpha, xp, xm[k], post, pk);
+      x = k < eng_d2k(ENG) ? m_var_one<T, DMAX, VPL, 2, ENG>(smem, R, k, an, vn, va, fdelta, alpha, xp, xm[k], post, pk)
+          : k < D3K        ? m_var_one<T, DMAX, VPL, N3, ENG>(smem, R, k, an, vn, va, fdelta, alpha, xp, xm[k], post, pk)
+                           : m_var_one<T, DMAX, VPL, DMAX, ENG>(smem, R, k, an, vn, va, fdelta, alpha, xp, xm[k], post, pk);
     if constexpr (!m_xmask(ENG)) xbits |= (x ? 1u : 0u) << k;
   }
   return xbits;
@@ -1183,24 +952,17 @@ __device__ inline uint32_t m_var(unsigned char* smem, RState<T, DMAX, VPL, ENG>&
 // as r_check_c plus the row's argmin slot (first strict minimum); CS[i+1] = m1 | parity and
 // V[argmin] = m2 | parity.  Any edge holding m1 would do as the argmin: with a tie m2 == m1.
 template <typename T, bool FIRST, int NCH, int TAIL>
-__device__ inline int m_check(unsigned char* smem, const RLayout& Ly, int m, int wbase, int wtid, int TB, uint32_t& sbits) {
+__device__ inline int m_check(unsigned char* smem, const RLayout& Ly, int m, int wtid, int TB, uint32_t& sbits) {
   using U = typename FT<T>::U;
   using VT = typename V16<T>::type;
   constexpr int NV = V16<T>::N;
   static_assert(sizeof(T) == 8, "m2s: fp64 only");
   int mism = 0;
   int q = 0;
-#if QLDPC_M2S_MBCNT
-  // tid from the wave's base (an SGPR) and the lane's mbcnt: no VGPR holds tid across the
-  // variable phase (A/B build: the register allocator then spills elsewhere)
-  const int tid = wbase + (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-#else
   // opaque tid: the row / F / tail offsets are recomputed per pass instead of being hoisted out
   // of the iteration loop (where they outlive the variable phase and spill)
   int tid = wtid;
   asm volatile("" : "+v"(tid));
-  (void)wbase;
-#endif
   const uint32_t rstride = (uint32_t)NCH * 16u;
   // chunk rotation for power-of-two rows (as r_check_c); rows of 3 chunks are conflict-free
   constexpr int kRows256 = 256 / (16 * NCH) > 0 ? 256 / (16 * NCH) : 1;
@@ -1209,42 +971,37 @@ __device__ inline int m_check(unsigned char* smem, const RLayout& Ly, int m, int
   uint32_t coff[NCH];
 #pragma unroll
   for (int c = 0; c < NCH; ++c) coff[c] = kRot ? (((uint32_t)c + rot) & (uint32_t)(NCH - 1)) * 16u : (uint32_t)c * 16u;
-  // explicit absolute row pointers (QLDPC_M2S_RPTR): one row base stepped per row (opaque, so the
-  // backend neither splits it into one induction variable per chunk nor re-adds the region offset
-  // per row) plus the tail, F and CS pointers; the argmin is selected as an offset from the row base
-  constexpr bool AP = QLDPC_M2S_RPTR;
-  const uint32_t sb = AP ? lds_base(smem) : 0u;
+  // explicit absolute row pointers: one row base stepped per row (opaque, so the backend neither
+  // splits it into one induction variable per chunk nor re-adds the region offset per row) plus
+  // the tail, F and CS pointers; the argmin is selected as an offset from the row base
+  const uint32_t sb = lds_base(smem);
   uint32_t rb = sb + Ly.v + 16u + (uint32_t)tid * rstride;
   uint32_t tp = sb + Ly.t + (uint32_t)tid * (uint32_t)sizeof(T);
   uint32_t fp = sb + Ly.f + 4u * (uint32_t)(tid + 1);
   uint32_t cp = sb + (uint32_t)(tid + 1) * (uint32_t)sizeof(T);
-  // one row: its loads, then its reduction and stores (kept apart so that rows can be loaded in pairs)
+  // one row: its loads, then its reduction and stores
   struct RowIn {
     VT cur[NCH];
     T tcur;
     uint32_t fcur, roff, toff, fo, co;
   };
-  // (c0..c1: the chunks to load; the tail and F word with the last chunk)
-  auto load_row = [&](RowIn& r, int i, uint32_t rb_, uint32_t tp_, uint32_t fp_, uint32_t cp_, int c0 = 0, int c1 = NCH) {
-    r.roff = AP ? rb_ : Ly.v + 16u + (uint32_t)i * rstride;
-    r.toff = AP ? tp_ : Ly.t + (uint32_t)i * (uint32_t)sizeof(T);
-    r.fo = AP ? fp_ : Ly.f + 4u * (uint32_t)(i + 1);
-    r.co = AP ? cp_ : (uint32_t)(i + 1) * (uint32_t)sizeof(T);
+  auto load_row = [&](RowIn& r, uint32_t rb_, uint32_t tp_, uint32_t fp_, uint32_t cp_) {
+    r.roff = rb_;
+    r.toff = tp_;
+    r.fo = fp_;
+    r.co = cp_;
 #pragma unroll
-    for (int c = 0; c < NCH; ++c)
-      if (c >= c0 && c < c1) r.cur[c] = lds_ld<VT, AP>(smem, r.roff + coff[c]);
-    if (c1 == NCH) {
-      r.tcur = (T)0;
-      if (TAIL) r.tcur = lds_ld<T, AP>(smem, r.toff);
-      r.fcur = lds_ld<uint32_t, AP>(smem, r.fo);
-    }
+    for (int c = 0; c < NCH; ++c) r.cur[c] = lds_ld<VT, true>(nullptr, r.roff + coff[c]);
+    r.tcur = (T)0;
+    if (TAIL) r.tcur = lds_ld<T, true>(nullptr, r.toff);
+    r.fcur = lds_ld<uint32_t, true>(nullptr, r.fo);
   };
   auto reduce_row = [&](const RowIn& r, int qq) {
     uint32_t s;
     if (FIRST) {
       s = ((r.fcur >> 1) ^ (r.fcur >> 2)) & 1u;
       sbits |= s << qq;
-      lds_st<uint32_t, AP>(smem, r.fo, (r.fcur & 4u) | ((r.fcur >> 2) & 1u));
+      lds_st<uint32_t, true>(nullptr, r.fo, (r.fcur & 4u) | ((r.fcur >> 2) & 1u));
     } else {
       s = (sbits >> qq) & 1u;
       mism |= (int)((r.fcur ^ s) & 1u);
@@ -1280,349 +1037,37 @@ __device__ inline int m_check(unsigned char* smem, const RLayout& Ly, int m, int
       px ^= (uint32_t)(FT<T>::bits(r.tcur) >> 32);
     }
     const U par = (U)(px & 0x80000000u) << 32;
-    lds_st<U, AP>(smem, r.co, FT<T>::bits(f1) | par);
-    lds_st<U, AP>(smem, amin, FT<T>::bits(f2) | par);
+    lds_st<U, true>(nullptr, r.co, FT<T>::bits(f1) | par);
+    lds_st<U, true>(nullptr, amin, FT<T>::bits(f2) | par);
   };
   const uint32_t drb = (uint32_t)TB * rstride, dtp = (uint32_t)TB * (uint32_t)sizeof(T), dfp = 4u * (uint32_t)TB,
                  dcp = (uint32_t)TB * (uint32_t)sizeof(T);
-  // QLDPC_M2S_ROWPAIR (the space-time family: one decode per CU, 1-2 rows per thread): both rows' loads
-  // are issued before the first row is reduced (their addresses never alias: distinct rows, tails, F
-  // words and CS entries), so the second row's LDS latency hides under the first row's arithmetic
-  if constexpr (QLDPC_M2S_ROWPAIR > 0 && TAIL && NCH == 4) {
-    for (int i = tid; i < m; i += 2 * TB, q += 2) {
-      if constexpr (AP) asm volatile("" : "+v"(rb));
-      RowIn a, b;
-      load_row(a, i, rb, tp, fp, cp);
-      const bool hb = i + TB < m;
-      // the second row's first QLDPC_M2S_ROWPAIR chunks ahead, the rest after the first row (VGPRs)
-      constexpr int PC = QLDPC_M2S_ROWPAIR < NCH ? QLDPC_M2S_ROWPAIR : NCH;
-      if (hb) load_row(b, i + TB, rb + drb, tp + dtp, fp + dfp, cp + dcp, 0, PC);
-      reduce_row(a, q);
-      if (hb) {
-        if constexpr (PC < NCH) load_row(b, i + TB, rb + drb, tp + dtp, fp + dfp, cp + dcp, PC, NCH);
-        reduce_row(b, q + 1);
-      }
-      rb += 2 * drb;
-      tp += 2 * dtp;
-      fp += 2 * dfp;
-      cp += 2 * dcp;
-    }
-  } else {
-    for (int i = tid; i < m; i += TB, ++q) {
-      if constexpr (AP) asm volatile("" : "+v"(rb));
-      RowIn a;
-      load_row(a, i, rb, tp, fp, cp);
-      reduce_row(a, q);
-      rb += drb;
-      tp += dtp;
-      fp += dfp;
-      cp += dcp;
-    }
-  }
-  return mism;
-}
-
-// m2v check phase (fp64): row q of this thread (check i = tid + q * TB) gathers its 7 V slots
-// through the register table (scattered ds_read_b64), then min / second min / parity / argmin as
-// m_check: CS[i+1] = m1 | parity, V[argmin] = m2 | parity.  Rows of fewer edges point their unused
-// entries at a slot that holds the sentinel forever (never the argmin: no edge is below it).
-template <typename T, bool FIRST>
-__device__ inline int m2v_check(unsigned char* smem, const RLayout& Ly, int m, int tid, int TB, uint32_t& sbits,
-                                const M2vRows& RW, uint32_t vbase) {
-  using U = typename FT<T>::U;
-  static_assert(sizeof(T) == 8, "m2v: fp64 only");
-  int mism = 0;
-#pragma unroll
-  for (int q = 0; q < kM2vRows; ++q) {
-    const int i = tid + q * TB;
-    if (i >= m) break;
-    const uint32_t wd[4] = {RW.w[q].x, RW.w[q].y, RW.w[q].z, RW.w[q].w};
-    uint32_t a[7];
-#pragma unroll
-    for (int e = 0; e < 7; ++e) a[e] = vbase + ((e & 1) ? (wd[e >> 1] >> 16) : (wd[e >> 1] & 0xFFFFu));
-    double x[7];
-#pragma unroll
-    for (int e = 0; e < 7; ++e) x[e] = FT<T>::val(lds_ld<U, true>(nullptr, a[e]));
-    const uint32_t fo = Ly.f + 4u * (uint32_t)(i + 1);
-    const uint32_t fcur = lds_at<uint32_t>(smem, fo);
-    uint32_t s;
-    if (FIRST) {
-      s = ((fcur >> 1) ^ (fcur >> 2)) & 1u;
-      sbits |= s << q;
-      lds_at<uint32_t>(smem, fo) = (fcur & 4u) | ((fcur >> 2) & 1u);
-    } else {
-      s = (sbits >> q) & 1u;
-      mism |= (int)((fcur ^ s) & 1u);
-    }
-    double f1 = FT<T>::val(FT<T>::kSent), f2 = f1;
-    uint32_t px = s ? 0x80000000u : 0u;
-    uint32_t amin = a[0];
-#pragma unroll
-    for (int e = 0; e < 7; ++e) {
-      amin = __builtin_fabs(x[e]) < f1 ? a[e] : amin;
-      double t;
-      asm("v_max_f64 %0, %1, |%2|" : "=v"(t) : "v"(f1), "v"(x[e]));
-      asm("v_min_f64 %0, %1, %2" : "=v"(f2) : "v"(f2), "v"(t));
-      asm("v_min_f64 %0, %1, |%2|" : "=v"(f1) : "v"(f1), "v"(x[e]));
-    }
-#pragma unroll
-    for (int e = 0; e + 1 < 7; e += 2) {
-      uint32_t p;
-      asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0x96"
-          : "=v"(p)
-          : "v"(px), "v"((uint32_t)(FT<T>::bits(x[e]) >> 32)), "v"((uint32_t)(FT<T>::bits(x[e + 1]) >> 32)));
-      px = p;
-    }
-    px ^= (uint32_t)(FT<T>::bits(x[6]) >> 32);
-    const U par = (U)(px & 0x80000000u) << 32;
-    lds_at<U>(smem, (uint32_t)(i + 1) * (uint32_t)sizeof(T)) = FT<T>::bits(f1) | par;
-    lds_st<U, true>(nullptr, amin, FT<T>::bits(f2) | par);
-  }
-  return mism;
-}
-
-// c2s check phase (rows of exactly 2 * NCH + TAIL edges; fp64): min / second min / parity / argmin
-// as m_check, then the c2v of the NEXT variable phase into the row's own slots: every edge gets
-// alpha * m1 with sign parity ^ own sign, written as {lo(a1), hi(a1) ^ parity ^ (own hi & sign)}
-// (one v_bitop3 per edge, the low word shared), and one ds_xor_b64 of bits(a1) ^ bits(a2) turns the
-// argmin's word into alpha * m2 with the same sign.  alpha * m with the sign applied afterwards is
-// bit-identical to ldpc's (+-m) * alpha (IEEE rounding is sign-symmetric); with a tie m1 == m2 and
-// the xor is zero.
-template <typename T, bool FIRST, int NCH, int TAIL>
-__device__ inline int c2s_check(unsigned char* smem, const RLayout& Ly, int m, int wtid, int TB, uint32_t& sbits,
-                                T alpha) {
-  using U = typename FT<T>::U;
-  using VT = typename V16<T>::type;
-  constexpr int NV = V16<T>::N;
-  static_assert(sizeof(T) == 8, "c2s: fp64 only");
-  int mism = 0;
-  int q = 0;
-  int tid = wtid;  // opaque: the row offsets are re-derived per pass (as m_check)
-  asm volatile("" : "+v"(tid));
-  const uint32_t rstride = (uint32_t)NCH * 16u;
   for (int i = tid; i < m; i += TB, ++q) {
-    const uint32_t roff = Ly.v + 16u + (uint32_t)i * rstride;
-    VT cur[NCH];
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) cur[c] = *reinterpret_cast<const VT*>(smem + roff + 16u * (uint32_t)c);
-    const uint32_t toff = Ly.t + (uint32_t)i * (uint32_t)sizeof(T);
-    T tcur = (T)0;
-    if (TAIL) tcur = lds_at<T>(smem, toff);
-    const uint32_t fcur = lds_at<uint32_t>(smem, Ly.f + 4u * (uint32_t)(i + 1));
-    uint32_t s;
-    if (FIRST) {
-      s = ((fcur >> 1) ^ (fcur >> 2)) & 1u;
-      sbits |= s << q;
-      lds_at<uint32_t>(smem, Ly.f + 4u * (uint32_t)(i + 1)) = (fcur & 4u) | ((fcur >> 2) & 1u);
-    } else {
-      s = (sbits >> q) & 1u;
-      mism |= (int)((fcur ^ s) & 1u);
-    }
-    double f1 = FT<T>::val(FT<T>::kSent), f2 = f1;
-    uint32_t px = s ? 0x80000000u : 0u;
-    uint32_t amin = roff;  // argmin slot (byte offset)
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-#pragma unroll
-      for (int k = 0; k < NV; ++k) {
-        const double x = V16<T>::get(cur[c], k);
-        amin = __builtin_fabs(x) < f1 ? roff + 16u * (uint32_t)c + 8u * (uint32_t)k : amin;
-        double t;
-        asm("v_max_f64 %0, %1, |%2|" : "=v"(t) : "v"(f1), "v"(x));
-        asm("v_min_f64 %0, %1, %2" : "=v"(f2) : "v"(f2), "v"(t));
-        asm("v_min_f64 %0, %1, |%2|" : "=v"(f1) : "v"(f1), "v"(x));
-      }
-      uint32_t p;
-      asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0x96"
-          : "=v"(p)
-          : "v"(px), "v"((uint32_t)(FT<T>::bits(cur[c].x) >> 32)), "v"((uint32_t)(FT<T>::bits(cur[c].y) >> 32)));
-      px = p;
-    }
-    if (TAIL) {
-      const double x = (double)tcur;
-      amin = __builtin_fabs(x) < f1 ? toff : amin;
-      double t;
-      asm("v_max_f64 %0, %1, |%2|" : "=v"(t) : "v"(f1), "v"(x));
-      asm("v_min_f64 %0, %1, %2" : "=v"(f2) : "v"(f2), "v"(t));
-      asm("v_min_f64 %0, %1, |%2|" : "=v"(f1) : "v"(f1), "v"(x));
-      px ^= (uint32_t)(FT<T>::bits(tcur) >> 32);
-    }
-    const U a1 = FT<T>::bits(f1 * alpha);
-    const U a2 = FT<T>::bits(f2 * alpha);
-    const uint32_t lo = (uint32_t)a1;
-    const uint32_t ah = (uint32_t)(a1 >> 32) ^ (px & 0x80000000u);
-    auto hiw = [&](double x) {
-      uint32_t hi;
-      asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0x6c"
-          : "=v"(hi)
-          : "v"((uint32_t)(FT<T>::bits(x) >> 32)), "v"(ah), "v"(0x80000000u));
-      return hi;
-    };
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const uint32_t off = roff + 16u * (uint32_t)c;
-      if (QLDPC_C2S_W128) {  // one 16-byte store per chunk (conflict-free at the 48-byte row stride)
-        typename LdsWord<16>::type w;
-        w.x = lo;
-        w.y = hiw(cur[c].x);
-        w.z = lo;
-        w.w = hiw(cur[c].y);
-        *reinterpret_cast<typename LdsWord<16>::type*>(smem + off) = w;
-      } else {
-        lds_at<uint32_t>(smem, off) = lo;
-        lds_at<uint32_t>(smem, off + 4u) = hiw(cur[c].x);
-        lds_at<uint32_t>(smem, off + 8u) = lo;
-        lds_at<uint32_t>(smem, off + 12u) = hiw(cur[c].y);
-      }
-    }
-    if (TAIL) {
-      lds_at<uint32_t>(smem, toff) = lo;
-      lds_at<uint32_t>(smem, toff + 4u) = hiw((double)tcur);
-    }
-    atomicXor(reinterpret_cast<unsigned long long*>(&lds_at<U>(smem, amin)), (unsigned long long)(a1 ^ a2));
-  }
-  return mism;
-}
-
-// Engine-4 variable phase: c2v from the slots, ldpc's column pass, v2c back.
-// Variable VPL-1 is skipped by waves whose lanes are all padding.
-template <typename T, int DMAX, int VPL>
-__device__ inline uint32_t c_var(unsigned char* smem, RState<T, DMAX, VPL, 4>& R, const FMap& M, bool last_live) {
-  using U = typename FT<T>::U;
-  r_launder(R);
-  uint32_t xbits = 0;
-  T cn[DMAX];
-#pragma unroll
-  for (int t = 0; t < DMAX; ++t) cn[t] = lds_at<T>(smem, R.ea[0][t] & 0xFFFFu);
-#pragma unroll
-  for (int k = 0; k < VPL; ++k) {
-    T c[DMAX];
-#pragma unroll
-    for (int t = 0; t < DMAX; ++t) c[t] = cn[t];
-    if (k + 1 < VPL) {  // next variable's reads go out before this one's arithmetic
-#pragma unroll
-      for (int t = 0; t < DMAX; ++t) cn[t] = lds_at<T>(smem, R.ea[k + 1][t] & 0xFFFFu);
-    }
-    if (k == VPL - 1 && !last_live) break;
-    T f[DMAX];
-    T acc = R.L[k];
-#pragma unroll
-    for (int t = 0; t < DMAX; ++t) {
-      f[t] = acc;
-      acc = acc + c[t];
-    }
-    const bool x = acc <= (T)0;
-    xbits |= (x ? 1u : 0u) << k;
-    T b = c[DMAX - 1];
-    U nv[DMAX];
-    nv[DMAX - 1] = canon2<T>(f[DMAX - 1]);
-#pragma unroll
-    for (int t = DMAX - 2; t >= 0; --t) {
-      nv[t] = canon2<T>(f[t] + b);
-      if (t > 0) b = b + c[t];
-    }
-#pragma unroll
-    for (int t = 0; t < DMAX; ++t) lds_at<U>(smem, R.ea[k][t] >> 16) = nv[t];
-    if (x) {
-#pragma unroll
-      for (int t = 0; t < DMAX; ++t) atomicXor(&lds_at<uint32_t>(smem, f_addr<T, 4>(R.ea[k][t], M)), 1u);
-    }
-  }
-  return xbits;
-}
-
-// Engine-4 check phase over rows with NCH 16-byte chunks: syndrome / (H x)
-// test as r_check, then every slot of the row receives its c2v for the next
-// variable phase (computed with `alpha`); padding slots get the sentinel.
-template <typename T, bool FIRST, int NCH>
-__device__ inline int c_check(unsigned char* smem, const RLayout& Ly, int m, int tid, int TB, uint32_t& sbits,
-                              T alpha) {
-  using U = typename FT<T>::U;
-  using VT = typename V16<T>::type;
-  constexpr int NV = V16<T>::N;
-  constexpr U kS = FT<T>::kSign;
-  int mism = 0;
-  int q = 0;
-  for (int i = tid; i < m; i += TB, ++q) {
-    VT* row = reinterpret_cast<VT*>(smem + Ly.v + 16 + (uint32_t)i * (uint32_t)(NCH * 16));
-    uint32_t& F = lds_at<uint32_t>(smem, Ly.f + 4u * (uint32_t)(i + 1));
-    const uint32_t f = F;
-    uint32_t s;
-    if (FIRST) {
-      s = (f >> 1) & 1u;
-      sbits |= s << q;
-    } else {
-      s = (sbits >> q) & 1u;
-      mism |= (int)((f ^ s) & 1u);
-    }
-    F = f & 0xFFFF0000u;  // keep the row degree
-    const int deg = (int)(f >> 16);
-    U xb[NCH * NV];
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const VT v = row[c];
-#pragma unroll
-      for (int k = 0; k < NV; ++k) xb[c * NV + k] = FT<T>::bits(V16<T>::get(v, k));
-    }
-    U m1 = FT<T>::kSent, m2 = FT<T>::kSent;
-    U px = s ? kS : (U)0;
-#pragma unroll
-    for (int e = 0; e < NCH * NV; ++e) {
-      const U a = xb[e] & ~kS;
-      if constexpr (sizeof(U) == 4) {
-        m2 = med3u(m1, m2, a);
-      } else {
-        const U hi = m1 > a ? m1 : a;
-        m2 = m2 < hi ? m2 : hi;
-      }
-      m1 = m1 < a ? m1 : a;
-      px ^= xb[e];
-    }
-    // chunk swizzle of build_slot_edges (qldpc_hip.hip): physical chunk c holds logical chunk c ^ swz
-    const int swz = NCH == 2 ? ((i >> 3) & 1) : NCH == 4 ? ((i >> 2) & 3) : 0;
-    const T sm1 = FT<T>::val(m1) * alpha, sm2 = FT<T>::val(m2) * alpha;
-    const U b1 = FT<T>::bits(sm1), b2 = FT<T>::bits(sm2);
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const int lim = deg - (c ^ swz) * NV;  // slots k < lim of this chunk are real edges
-      U o[NV];
-#pragma unroll
-      for (int k = 0; k < NV; ++k) {
-        const U x = xb[c * NV + k];
-        const U sel = ((x & ~kS) == m1) ? b2 : b1;  // |c2v| = alpha * (min over the other edges)
-        const U cv = sel ^ ((px ^ x) & kS);         // sign = parity of the others and the syndrome
-        o[k] = k < lim ? cv : FT<T>::kSent;
-      }
-      VT w;
-      if constexpr (NV == 4) {
-        w = make_float4(FT<T>::val(o[0]), FT<T>::val(o[1]), FT<T>::val(o[2]), FT<T>::val(o[3]));
-      } else {
-        w = make_double2(FT<T>::val(o[0]), FT<T>::val(o[1]));
-      }
-      row[c] = w;
-    }
+    asm volatile("" : "+v"(rb));
+    RowIn a;
+    load_row(a, rb, tp, fp, cp);
+    reduce_row(a, q);
+    rb += drb;
+    tp += dtp;
+    fp += dfp;
+    cp += dcp;
   }
   return mism;
 }
 
 template <typename T, int ENG>
-__device__ inline void r_fill(const SSector& S, unsigned char* smem, const RLayout& Ly, int vslots, int mmax, int tid,
-                              int TB) {
+__device__ inline void r_fill(const SSector& S, unsigned char* smem, const RLayout& Ly, int mmax, int tid, int TB) {
   using VT = typename V16<T>::type;
   VT* V4 = reinterpret_cast<VT*>(smem + Ly.v);
   const VT s = V16<T>::splat(FT<T>::val(FT<T>::kSent));
-  // engine 4: the first chunk is the zero chunk missing edges read
-  (void)vslots;
   const int nchunks = (int)((Ly.f - Ly.v) / 16u);  // V rows and (tail layouts) the tail slots
-  for (int i = tid; i < nchunks; i += TB) V4[i] = (eng_base(ENG) == 4 && i == 0) ? V16<T>::splat((T)0) : s;
-  // engine 4: row degree in the high half; engine 3: row-degree parity in bit 2 (w domain)
+  for (int i = tid; i < nchunks; i += TB) V4[i] = s;
+  // row-degree parity in bit 2 (w domain)
   for (int i = tid; i <= mmax; i += TB)
-    f_st<ENG>(smem, f_off<ENG>(Ly, i),
-              (i >= 1 && i <= S.m) ? (eng_base(ENG) == 4 ? ((uint32_t)S.rdeg[i - 1] << 16) : (((uint32_t)S.rdeg[i - 1] & 1u) << 2))
-                                   : 0u);
+    f_st<ENG>(smem, f_off<ENG>(Ly, i), (i >= 1 && i <= S.m) ? (((uint32_t)S.rdeg[i - 1] & 1u) << 2) : 0u);
   uint32_t* lred = reinterpret_cast<uint32_t*>(smem + Ly.lred);
   if (tid < 10) lred[tid] = 0;  // lred[0..7], flags[0..1]
-  if (eng_base(ENG) == 3 && tid == 0) {
+  if (tid == 0) {
     // missing-edge dummy: c2v = ±0 (an opaque zero: a hoisted zero pair outlives the loops)
     uint32_t zz = 0;
     asm volatile("" : "+v"(zz));
@@ -1633,21 +1078,10 @@ __device__ inline void r_fill(const SSector& S, unsigned char* smem, const RLayo
   }
 }
 
-// Engine 4 lays every row out as 8 slots (row degree <= 8): 2 chunks in fp32,
-// 4 in fp64 (one compile-time row width keeps the check phase's VGPRs low).
-template <typename T>
-constexpr int kRowChunks4 = 8 * (int)sizeof(T) / 16;
-template <typename T, bool FIRST>
-__device__ inline int c_check_any(unsigned char* smem, const RLayout& Ly, int m, int nch, int tid, int TB,
-                                  uint32_t& sbits, T alpha) {
-  (void)nch;  // == kRowChunks4<T> (host-enforced)
-  return c_check<T, FIRST, kRowChunks4<T>>(smem, Ly, m, tid, TB, sbits, alpha);
-}
-
 // One sector pass over `cn` shots (chunk-relative), one decode in flight.
 template <typename T, int DMAX, int VPL, bool MC, int ENG, int D3K, int NCH = 0>
 __device__ void r_pass(const SSector& S, int q, long long c0, int cn, unsigned char* smem, const RLayout& Ly,
-                       int vslots, int mmax, uint32_t* failmap, unsigned long long* cnt, const SMcArgs* A,
+                       int mmax, uint32_t* failmap, unsigned long long* cnt, const SMcArgs* A,
                        const SDecArgs* D, int tid, int TB) {
   using U = typename FT<T>::U;
   constexpr bool KV = RState<T, DMAX, VPL, ENG>::kKeepV;
@@ -1659,20 +1093,14 @@ __device__ void r_pass(const SSector& S, int q, long long c0, int cn, unsigned c
   asm volatile("" : "+v"(tidp));
 #endif
   RState<T, DMAX, VPL, ENG> R;
-  constexpr bool SP = RState<T, DMAX, VPL, ENG>::kSplit;
-  const int wbase = (int)__builtin_amdgcn_readfirstlane((uint32_t)tid) & ~63;  // (m2s check phase)
+  const int wbase = (int)__builtin_amdgcn_readfirstlane((uint32_t)tid) & ~63;  // (narrow waves)
   const uint32_t sbase = lds_base(smem);
   r_load<T, DMAX, VPL, ENG>(S, R, Ly, tidp, TB, sbase);
-  r_fill<T, ENG>(S, smem, Ly, vslots, mmax, tidp, TB);
-  FMap M;
-  M.fbase = eng_base(ENG) == 4 ? Ly.f + 4u : Ly.f;
-  M.rstart = Ly.v + 16u;
-  M.rsh = 4 + __builtin_ctz((unsigned)nch);
-  // absolute CS addresses (split or kAbs; 16-byte aligned base): fbase absorbs the base
+  r_fill<T, ENG>(S, smem, Ly, mmax, tidp, TB);
+  // F base of r_fa; absolute CS addresses (split or kAbs; 16-byte aligned base): it absorbs the base
   constexpr bool AB = RState<T, DMAX, VPL, ENG>::kAbs;
-  if (AB) M.fbase = Ly.f - (sbase >> (eng_fb(ENG) ? 3 : (sizeof(T) == 4 || eng_m2s(ENG)) ? 1 : 2));
-  const uint32_t fdelta = eng_base(ENG) == 4 ? Ly.f : M.fbase;
-  // waves whose lanes all hold padding variables skip the last variable (engine 4)
+  const uint32_t fdelta = AB ? Ly.f - (sbase >> (eng_fb(ENG) ? 3 : (sizeof(T) == 4 || eng_m2s(ENG)) ? 1 : 2)) : Ly.f;
+  // waves whose lanes all hold padding variables skip the last variable
   // (the fp64 space-time m2s family places its waves over the SIMDs: a mask, not a prefix)
   const bool last_live = eng_nw(ENG) ? ((S.live_last >> ((uint32_t)wbase >> 6)) & 1u) != 0
                                      : uni((VPL - 1) * TB + (tid & ~63) < S.npos ? 1 : 0) != 0;
@@ -1710,14 +1138,7 @@ __device__ void r_pass(const SSector& S, int q, long long c0, int cn, unsigned c
 #pragma unroll
         for (int t = 0; t < DMAX; ++t) {
           if (no_edge<ENG, D3K>(k, t)) continue;  // (no dummy edge kept)
-          if constexpr (eng_m2v(ENG)) {  // (m2v: 256-thread workgroups, host-enforced)
-            // lanes past the last variable slot's S.vnl own no slots there (their lane-linear
-            // addresses would run into the next edge's slots and past the V region)
-            if (k == VPL - 1 && tidl >= S.vnl) continue;
-            lds_st<U, true>(smem, m2v_va<T, DMAX, VPL, ENG, D3K, 256>(R, k, t), cl);
-          }
-          else
-            lds_st<U, AB>(smem, r_va(R, k, t), cl);
+          lds_st<U, AB>(smem, r_va(R, k, t), cl);
           if (KV) R.ov[KV ? k : 0][KV ? t : 0] = cl;
         }
       }
@@ -1763,12 +1184,7 @@ __device__ void r_pass(const SSector& S, int q, long long c0, int cn, unsigned c
 #pragma unroll
               for (int t = 0; t < DMAX; ++t) {
                 if (no_edge<ENG, D3K>(k, t)) continue;
-                if constexpr (eng_base(ENG) == 4)
-                  atomicXor(&lds_at<uint32_t>(smem, f_addr<T, ENG>(R.ea[k][t], M)), 2u);
-                else if constexpr (eng_c2s(ENG))
-                  lds_xor_abs(R.ea[k][t], 2u);
-                else
-                  f_xor<ENG>(smem, r_fa(R, k, t, M.fbase), 2u);
+                f_xor<ENG>(smem, r_fa(R, k, t, fdelta), 2u);
               }
             }
           }
@@ -1776,11 +1192,11 @@ __device__ void r_pass(const SSector& S, int q, long long c0, int cn, unsigned c
         if (cc && !cc_read) *cc = (uint16_t)cw;
       } else {
         const uint8_t* srow = D->synd + (c0 + sh) * (long long)m;
-        for (int i = tidl; i < m; i += TB) {  // i = check label (engine 3: S.rperm maps it to the check)
+        for (int i = tidl; i < m; i += TB) {  // i = check label (S.rperm maps it to the check)
           const uint32_t fo = f_off<ENG>(Ly, i + 1);
           const uint32_t F = f_ld<ENG>(smem, fo);
           const int oi = S.rperm ? S.rperm[i] : i;
-          f_st<ENG>(smem, fo, (eng_base(ENG) == 4 ? (F & 0xFFFF0000u) : (F & 4u)) | ((uint32_t)(srow[oi] & 1u) << 1));
+          f_st<ENG>(smem, fo, (F & 4u) | ((uint32_t)(srow[oi] & 1u) << 1));
         }
       }
     }
@@ -1789,9 +1205,6 @@ __device__ void r_pass(const SSector& S, int q, long long c0, int cn, unsigned c
       st_acc[4] += t - st_a;
       st_a = t;
     }
-    M2vRows rwv;  // m2v: this thread's rows, loaded ahead of each check phase's barrier
-    if constexpr (eng_m2v(ENG))
-      if (have) m2v_rows_load(S, tid, TB, m, rwv);
     __syncthreads();
     // ---------------------------------------------------------- finish the previous decode
     if (pshot >= 0) {
@@ -1823,15 +1236,9 @@ __device__ void r_pass(const SSector& S, int q, long long c0, int cn, unsigned c
       st_acc[8] += t - st_a;
       st_a = t;
     }
-    // ---------------------------------------------------------- first check pass (CS / c2v from priors)
-    if constexpr (eng_base(ENG) == 4)
-      c_check_any<T, true>(smem, Ly, m, nch, tid, TB, sb, adaptive ? (T)0.5 : alpha_fixed);
-    else if constexpr (eng_c2s(ENG))
-      c2s_check<T, true, NCH, eng_tail(ENG)>(smem, Ly, m, tid, TB, sb, adaptive ? (T)0.5 : alpha_fixed);
-    else if constexpr (eng_m2v(ENG))
-      m2v_check<T, true>(smem, Ly, m, tid, TB, sb, rwv, sbase + Ly.v);
-    else if constexpr (eng_m2s(ENG))
-      m_check<T, true, NCH, eng_tail(ENG)>(smem, Ly, m, wbase, tid, TB, sb);
+    // ---------------------------------------------------------- first check pass (CS from priors)
+    if constexpr (eng_m2s(ENG))
+      m_check<T, true, NCH, eng_tail(ENG)>(smem, Ly, m, tid, TB, sb);
     else if constexpr (NCH > 0)
       r_check_c<T, true, NCH, eng_tail(ENG), QLDPC_PFC, ENG>(smem, Ly, m, tid, TB, sb);
     else
@@ -1848,14 +1255,14 @@ __device__ void r_pass(const SSector& S, int q, long long c0, int cn, unsigned c
     int it = 1;
     bool conv = false;
     uint32_t xb = 0;
-    uint64_t xm[VPL];  // (m2s families, QLDPC_M2S_XMASK: decisions as wave lane masks)
+    uint64_t xm[VPL];  // (m2s families, m_xmask: decisions as wave lane masks)
 #pragma unroll
     for (int k = 0; k < VPL; ++k) xm[k] = 0;
     long long cslot = -1;  // BP+OSD capture slot of this decode (claimed at its last iteration)
     while (true) {
       int mism;
       double* cpost = nullptr;
-      if constexpr (MC && eng_base(ENG) == 3) {
+      if constexpr (MC) {
         if (A->c_n && A->c_post[q] && it >= S.max_iter) {  // uniform: the last iteration may end unconverged
           // (lred word 11: no static LDS in these kernels, so the dynamic image starts at address 0
           // and its offsets fold into the LDS instructions)
@@ -1866,52 +1273,39 @@ __device__ void r_pass(const SSector& S, int q, long long c0, int cn, unsigned c
           if (cslot < A->c_cap) cpost = A->c_post[q] + cslot * (long long)n;
         }
       }
-      if constexpr (eng_base(ENG) == 4) {
-        xb = c_var<T, DMAX, VPL>(smem, R, M, last_live);
-        __syncthreads();
-        // c2v for iteration it + 1 (wasted if this one converged)
-        const T alpha = adaptive ? (T)(1.0 - ldexp(1.0, -(it + 1))) : alpha_fixed;
-        mism = c_check_any<T, false>(smem, Ly, m, nch, tid, TB, sb, alpha);
-      } else {
-        const T alpha = adaptive ? (T)(1.0 - ldexp(1.0, -it)) : alpha_fixed;
-        // (the 1024-thread tail family runs one workgroup per CU: nothing to take priority over)
-        constexpr int kPV = (eng_tail(ENG) && !eng_m2x(ENG) && !eng_fb(ENG)) ? 0 : QLDPC_PRIO_V;
-        if (kPV) __builtin_amdgcn_s_setprio(kPV);
-        if constexpr (eng_m2x(ENG))
-          xb = m_var<T, DMAX, VPL, D3K, ENG>(smem, R, fdelta, alpha, xb, xm, last_live, cpost, S.perm + tidl, TB, nwm);
-        else
-          xb = r_var<T, DMAX, VPL, D3K, ENG>(smem, R, fdelta, alpha, xb, last_live, cpost, S.perm + tidl, TB);
-        if (kPV) __builtin_amdgcn_s_setprio(0);
-        if constexpr (eng_m2v(ENG)) m2v_rows_load(S, tid, TB, m, rwv);
-        unsigned long long t1 = 0;
-        if (QLDPC_STAMPS) {
-          t1 = qstamp();
-          st_acc[0] += t1 - st_a;
-        }
-        __syncthreads();
-        if (QLDPC_STAMPS) {
-          st_a = qstamp();
-          st_acc[1] += st_a - t1;
-        }
-        // check state for iteration it + 1 (float: pre-scaled by its alpha)
-        const T alpha_next = adaptive ? (T)(1.0 - ldexp(1.0, -(it + 1))) : alpha_fixed;
-        if (QLDPC_PRIO_C) __builtin_amdgcn_s_setprio(QLDPC_PRIO_C);
-        if constexpr (eng_c2s(ENG))
-          mism = c2s_check<T, false, NCH, eng_tail(ENG)>(smem, Ly, m, tid, TB, sb, alpha_next);
-        else if constexpr (eng_m2v(ENG))
-          mism = m2v_check<T, false>(smem, Ly, m, tid, TB, sb, rwv, sbase + Ly.v);
-        else if constexpr (eng_m2s(ENG))
-          mism = m_check<T, false, NCH, eng_tail(ENG)>(smem, Ly, m, wbase, tid, TB, sb);
-        else if constexpr (NCH > 0)
-          mism = r_check_c<T, false, NCH, eng_tail(ENG), QLDPC_PFC, ENG>(smem, Ly, m, tid, TB, sb);
-        else
-          mism = r_check<T, false>(smem, Ly, m, nch, tid, TB, sb, alpha_next);
-        if (QLDPC_PRIO_C) __builtin_amdgcn_s_setprio(0);
-        if (QLDPC_STAMPS) {
-          const unsigned long long t = qstamp();
-          st_acc[2] += t - st_a;
-          st_a = t;
-        }
+      const T alpha = adaptive ? (T)(1.0 - ldexp(1.0, -it)) : alpha_fixed;
+      // (the 1024-thread tail family runs one workgroup per CU: nothing to take priority over)
+      constexpr int kPV = (eng_tail(ENG) && !eng_m2s(ENG) && !eng_fb(ENG)) ? 0 : QLDPC_PRIO_V;
+      if (kPV) __builtin_amdgcn_s_setprio(kPV);
+      if constexpr (eng_m2s(ENG))
+        xb = m_var<T, DMAX, VPL, D3K, ENG>(smem, R, fdelta, alpha, xb, xm, last_live, cpost, S.perm + tidl, TB, nwm);
+      else
+        xb = r_var<T, DMAX, VPL, D3K, ENG>(smem, R, fdelta, alpha, xb, last_live, cpost, S.perm + tidl, TB);
+      if (kPV) __builtin_amdgcn_s_setprio(0);
+      unsigned long long t1 = 0;
+      if (QLDPC_STAMPS) {
+        t1 = qstamp();
+        st_acc[0] += t1 - st_a;
+      }
+      __syncthreads();
+      if (QLDPC_STAMPS) {
+        st_a = qstamp();
+        st_acc[1] += st_a - t1;
+      }
+      // check state for iteration it + 1 (float: pre-scaled by its alpha)
+      const T alpha_next = adaptive ? (T)(1.0 - ldexp(1.0, -(it + 1))) : alpha_fixed;
+      if (QLDPC_PRIO_C) __builtin_amdgcn_s_setprio(QLDPC_PRIO_C);
+      if constexpr (eng_m2s(ENG))
+        mism = m_check<T, false, NCH, eng_tail(ENG)>(smem, Ly, m, tid, TB, sb);
+      else if constexpr (NCH > 0)
+        mism = r_check_c<T, false, NCH, eng_tail(ENG), QLDPC_PFC, ENG>(smem, Ly, m, tid, TB, sb);
+      else
+        mism = r_check<T, false>(smem, Ly, m, nch, tid, TB, sb, alpha_next);
+      if (QLDPC_PRIO_C) __builtin_amdgcn_s_setprio(0);
+      if (QLDPC_STAMPS) {
+        const unsigned long long t = qstamp();
+        st_acc[2] += t - st_a;
+        st_a = t;
       }
       if (__any(mism) && (tid & 63) == 0) flags[it & 1] = 1u;
       __syncthreads();
@@ -1927,7 +1321,7 @@ __device__ void r_pass(const SSector& S, int q, long long c0, int cn, unsigned c
       if (conv || it >= S.max_iter) break;
       ++it;
     }
-    if constexpr (eng_m2x(ENG) && eng_base(ENG) != 4 && m_xmask(ENG)) {
+    if constexpr (eng_m2s(ENG) && m_xmask(ENG)) {
       xb = 0;
 #pragma unroll
       for (int k = 0; k < VPL; ++k) xb |= (__builtin_amdgcn_inverse_ballot_w64(xm[k]) ? 1u : 0u) << k;
@@ -2015,7 +1409,7 @@ __global__ __launch_bounds__(LB, (lb_waves<T, ENG>(LB))) void rmc_kernel(SMcArgs
   const int tid = threadIdx.x, TB = blockDim.x;
   const int CH = A.chunk;
   const int fw = (CH + 31) / 32;
-  const RLayout Ly = r_layout(eng_base(ENG), A.vslots, A.mmax, (int)sizeof(T), eng_tail(ENG), eng_m2s(ENG) ? 1 : eng_c2s(ENG) ? 2 : 0, eng_fb(ENG));
+  const RLayout Ly = r_layout(eng_base(ENG), A.vslots, A.mmax, (int)sizeof(T), eng_tail(ENG), eng_m2s(ENG) ? 1 : 0, eng_fb(ENG));
   uint32_t* fm0 = reinterpret_cast<uint32_t*>(smem + Ly.total);
   uint32_t* fm1 = fm0 + ((fw + 3) & ~3);
   unsigned long long* cnt = reinterpret_cast<unsigned long long*>(fm1 + ((fw + 3) & ~3));
@@ -2045,7 +1439,7 @@ __global__ __launch_bounds__(LB, (lb_waves<T, ENG>(LB))) void rmc_kernel(SMcArgs
     for (int qi = 0; qi < A.nsec; ++qi) {
       const SSector S = pick_ssector(A, qi);
       const int q = qi == 0 ? A.sec_id0 : A.sec_id1;
-      r_pass<T, DMAX, VPL, true, ENG, D3K, NCH>(S, q, c0, cn, smem, Ly, A.vslots, A.mmax, q == 0 ? fm0 : fm1, cnt, &A, nullptr,
+      r_pass<T, DMAX, VPL, true, ENG, D3K, NCH>(S, q, c0, cn, smem, Ly, A.mmax, q == 0 ? fm0 : fm1, cnt, &A, nullptr,
                                  tid, TB);
     }
     // combine the sectors per shot (eval_logical_type, src/Simulators.py:162-168)
@@ -2073,7 +1467,7 @@ __global__ __launch_bounds__(LB, (lb_waves<T, ENG>(LB))) void rdec_kernel(SDecAr
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, TB = blockDim.x;
   const int CH = D.chunk;
-  const RLayout Ly = r_layout(eng_base(ENG), D.vslots, D.mmax, (int)sizeof(T), eng_tail(ENG), eng_m2s(ENG) ? 1 : eng_c2s(ENG) ? 2 : 0, eng_fb(ENG));
+  const RLayout Ly = r_layout(eng_base(ENG), D.vslots, D.mmax, (int)sizeof(T), eng_tail(ENG), eng_m2s(ENG) ? 1 : 0, eng_fb(ENG));
   const long long nchunks = (D.B + CH - 1) / CH;
   // the chunk queue's next index in lred words 10-11 (r_pass clears words 0-9 only; no static LDS)
   long long* s_next = reinterpret_cast<long long*>(smem + Ly.lred + 40);
@@ -2086,7 +1480,7 @@ __global__ __launch_bounds__(LB, (lb_waves<T, ENG>(LB))) void rdec_kernel(SDecAr
   while (ch < nchunks) {
     const long long c0 = ch * CH;
     const int cn = (int)(D.B - c0 < CH ? D.B - c0 : CH);
-    r_pass<T, DMAX, VPL, false, ENG, D3K, NCH>(D.sec, 0, c0, cn, smem, Ly, D.vslots, D.mmax, nullptr, nullptr, nullptr, &D, tid,
+    r_pass<T, DMAX, VPL, false, ENG, D3K, NCH>(D.sec, 0, c0, cn, smem, Ly, D.mmax, nullptr, nullptr, nullptr, &D, tid,
                                 TB);
     if (D.work) {  // r_pass ends with a barrier: every thread has read s_next
       if (tid == 0) *s_next = (long long)atomicAdd(D.work, 1u);

@@ -43,14 +43,13 @@ struct SSector {
   const uint32_t* edges;            // [VPL][DMAX][TB]
   const void* llr;                  // T [VPL][TB]
   const unsigned long long* lmask;  // [n][kw] logical-row masks per column (MC only)
-  const uint8_t* rdeg;              // [m] row degrees by check label (engines 3, 4)
-  const int32_t* perm;              // [VPL][TB] variable of each slot, -1 = padding (engines 3/4)
+  const uint8_t* rdeg;              // [m] row degrees by check label (engine 3)
+  const int32_t* perm;              // [VPL][TB] variable of each slot, -1 = padding (engine 3)
   const int32_t* rperm;             // [m] original check of each check label (engine 3), NULL = identity
   int m, n, kw, max_iter, nch, vpl; // nch = 16-byte chunks per row; vpl = variables per thread
   int d3k;                          // engine 3: slots k < d3k hold variables of degree <= 3 only
   double alpha;                     // 0 => 1 - 2^-iter
-  // m2v (variable-major V slots): the check phase's row table [kM2vRows][4][TB] (two 16-bit slot
-  // byte offsets from the V base per word), the last variable slot's first V slot and per-edge stride
+  // reserved (no kernel reads them; the host leaves them zero)
   const uint32_t* rows;
   int vlast, vnl;
   int npos;                         // 1 + the last slot position holding a variable (= n unless the

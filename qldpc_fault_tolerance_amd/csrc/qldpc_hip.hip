@@ -61,8 +61,7 @@ SVariant get_svariant(int precision, int dmax, int ns) {
   return dmax == 4 ? get_svariant_f64_d4(ns) : get_svariant_f64_d8(ns);
 }
 
-SVariant get_rvariant(int engine, int precision, int vpl, int d3k, int dmax) {
-  if (engine == 4) return precision == 32 ? get_r4variant_f32(vpl) : get_r4variant_f64(vpl);
+SVariant get_rvariant(int precision, int vpl, int d3k, int dmax) {
   if (precision == 32 && dmax == 5) return get_rvariant_f32_d5(vpl, d3k);
   if (precision == 32 && dmax == 6) return get_rvariant_f32_d6(vpl, d3k);
   return precision == 32 ? get_rvariant_f32(vpl, d3k) : get_rvariant_f64(vpl);
@@ -95,13 +94,7 @@ unsigned long long* debug_stamps_buffer() {
 }
 #endif
 
-// fp64 engine-3 kernels for 257-512-thread workgroups (engine id 303, VPL 3-4); opt-in QLDPC_F64X=1
-bool use_f64x(const Route& r) {
-  return r.engine == 3 && r.precision == 64 && r.DMAX == 4 && r.ea_shift == 0 && r.TB > 256 && r.TB <= 512 && r.VPL >= 3 &&
-         r.VPL <= 4 && QLDPC_EXPERIMENTAL && env_int("QLDPC_F64X", 0) != 0;
-}
-
-// Slot-family kernels of an engine (2, 3 or 4).
+// Slot-family kernels of an engine (2 or 3).
 SVariant slot_variant(const Route& r) {
   const SVariant none{nullptr, nullptr, nullptr, nullptr};
   const bool e3 = r.engine == 3, f64 = r.precision == 64;
@@ -114,16 +107,13 @@ SVariant slot_variant(const Route& r) {
   if (r.m2s) {
     // the fp64 space-time graphs: rows of 4 chunks + a tail slot, dword-scaled addresses, 1024
     // threads (engine id 111313, round 6)
-    if (r.m2s == 1 && e3 && f64 && r.DMAX == 4 && r.ea_shift == 2 && r.nch == 4 && r.tail && r.TB >= 512)
+    if (e3 && f64 && r.DMAX == 4 && r.ea_shift == 2 && r.nch == 4 && r.tail && r.TB >= 512)
       return get_rvariant_f64_m2st(r.VPL, r.d3k, r.d2k);
     // rows of 8 (4 chunks, no tail array), column degree 5, 256 threads (128 / 192 for small graphs): engine id 10103
-    if (r.m2s == 1 && e3 && f64 && r.DMAX == 5 && r.ea_shift == 0 && r.nch == 4 && !r.tail && r.TB <= 256)
+    if (e3 && f64 && r.DMAX == 5 && r.ea_shift == 0 && r.nch == 4 && !r.tail && r.TB <= 256)
       return r.m2s_pk ? get_rvariant_f64_m2s8pk(r.VPL, r.d3k) : get_rvariant_f64_m2s8(r.VPL, r.d3k);
     const bool ok = e3 && f64 && r.DMAX == 4 && r.ea_shift == 0 && r.nch == 3 && r.tail && r.TB <= 256;
-    if (r.m2s == 3)  // variable-major V slots: no tail array, 256 threads
-      return (e3 && f64 && r.DMAX == 4 && r.ea_shift == 0 && r.TB == 256) ? get_rvariant_f64_m2v(r.VPL, r.d3k) : none;
-    if (!ok) return none;
-    return r.m2s == 2 ? get_rvariant_f64_c2s(r.VPL, r.d3k) : get_rvariant_f64_m2s(r.VPL, r.d3k);
+    return ok ? get_rvariant_f64_m2s(r.VPL, r.d3k) : none;
   }
   // fp64 tail layout (rows of 4 chunks + a tail slot, dword-scaled addresses, 1024 threads)
   if (r.tail) {
@@ -132,11 +122,9 @@ SVariant slot_variant(const Route& r) {
     return f64 ? get_rvariant_f64_st(r.VPL, r.d3k, r.d2k) : get_rvariant_f32_st(r.VPL, r.d3k);
   }
   if (use_f64w(r)) return r.DMAX == 5 ? get_rvariant_f64_w_d5(r.VPL, r.d3k, r.nch) : get_rvariant_f64_w(r.VPL, r.d3k, r.nch);
-  if (use_f64x(r)) return get_rvariant_f64_x(r.VPL, r.d3k);
   if (use_f32w(r)) return get_rvariant_f32_w(r.VPL, r.d3k);
-  if (r.engine == 4 && f64 && r.TB <= 256 && r.VPL >= 4) return get_r4variant_f64_w(r.VPL);
   if (e3 && r.ea_shift == 2) return (!f64 && r.DMAX == 4) ? get_rvariant_f32_big(r.VPL, r.d3k) : none;
-  return r.engine >= 3 ? get_rvariant(r.engine, r.precision, r.VPL, r.d3k, r.DMAX) : get_svariant(r.precision, r.DMAX, r.NS);
+  return e3 ? get_rvariant(r.precision, r.VPL, r.d3k, r.DMAX) : get_svariant(r.precision, r.DMAX, r.NS);
 }
 
 // The id the handles report for that kernel (qldpc_bp_kernel_id): the engine, or the engine-3 family
@@ -144,11 +132,10 @@ SVariant slot_variant(const Route& r) {
 int route_kernel_id(const Route& r) {
   if (r.engine != 3) return r.engine;
   if (r.m2s)
-    return r.m2s == 2 ? 31103 : r.m2s == 3 ? 40103 : (r.tail && r.nch == 4) ? 11313 + 100000 * std::min(r.d2k, 1)
-           : r.tail ? 11103 : r.m2s_pk ? 10203 : 10103;
+    return (r.tail && r.nch == 4) ? 11313 + 100000 * std::min(r.d2k, 1) : r.tail ? 11103 : r.m2s_pk ? 10203 : 10103;
   if (r.fb) return 21013 + ((r.d3k >= 8 && r.d2k > 0) ? 100000 * std::min(r.d2k, 4) : 0);  // + D2K digit
   if (r.tail) return 1013 + ((r.precision == 64 && r.VPL == 6 && r.d2k >= 1 && r.d3k >= 1) ? 100000 : 0);
-  return use_f64w(r) ? 103 : use_f64x(r) ? 303 : r.ea_shift == 2 ? 13 : 3;
+  return use_f64w(r) ? 103 : r.ea_shift == 2 ? 13 : 3;
 }
 
 int round_up(int x, int a) { return (x + a - 1) / a * a; }
@@ -246,7 +233,7 @@ int choose_rgeometry(int n, int m, int requested_vpl, int& TB, int& VPL, int pre
   return 0;
 }
 
-// The engine-3/4 LDS image of a route over `vslots` V slots and `mmax` checks (the graph's own, or
+// The engine-3 LDS image of a route over `vslots` V slots and `mmax` checks (the graph's own, or
 // the larger of two sectors'), and a workgroup's LDS bytes with it.
 RLayout route_layout(const Route& r, int vslots, int mmax) {
   return r_layout(r.engine, vslots, mmax, r.precision == 32 ? 4 : 8, r.tail, r.m2s, r.fb);
@@ -255,8 +242,8 @@ size_t route_lds(const Route& r, int vslots, int mmax) {
   return r_lds_bytes((int)route_layout(r, vslots, mmax).total, kChunkMax);
 }
 
-// Engines 3 and 4 address their image with 16-bit byte offsets; engine 3 with
-// dword-scaled offsets (kernel id 13, ea_shift 2) reaches 256 KiB.
+// Engine 3 addresses its image with 16-bit byte offsets; with dword-scaled offsets
+// (kernel id 13, ea_shift 2) it reaches 256 KiB.
 bool route_fits(const Route& r, int vslots, int mmax) {
   return route_layout(r, vslots, mmax).lred <= (65536u << r.ea_shift) && route_lds(r, vslots, mmax) <= (size_t)kLdsMax;
 }
@@ -294,7 +281,7 @@ int qldpc_abi_version(void) { return QLDPC_ABI_VERSION; }
 
 const char* qldpc_last_error(void) { return qldpc_rt::g_err.c_str(); }
 
-int qldpc_build_flags(void) { return QLDPC_EXPERIMENTAL ? QLDPC_BUILD_EXPERIMENTAL : 0; }
+int qldpc_build_flags(void) { return 0; }
 
 int qldpc_device_count(int* out) {
   if (!out) return set_err(QLDPC_EINVAL, "out is NULL");
@@ -439,7 +426,7 @@ static int leading_slots(const qldpc_graph* g, const std::vector<int32_t>& slot_
 // per v2c store instruction of the variable phase (slot (k, t), 32-lane half
 // wave), to spread its 32 stores over the 32 banks: at most 2 per bank, which
 // ds_write_b32 absorbs for free (MI355X_MICROARCH.md §LDS).  vbase_dw < 0
-// keeps the ascending-column order (engine 4 relies on it).
+// keeps the ascending-column order.
 //
 // `lab` (engine 3, may be empty = identity) relabels the checks: check i keeps
 // its CS entry at lab[i] + 1 and its row at position lab[i] of V (see
@@ -524,7 +511,7 @@ static StPlan st_plan(const qldpc_graph* g, int tb, int vpl, int DM, bool narrow
   return P;
 }
 
-// `m2s`: place for the families whose variable phase also reads each edge's V slot (r.m2s == 1).
+// `m2s`: place for the families whose variable phase also reads each edge's V slot (r.m2s).
 static void build_slot_edges(const qldpc_graph* g, const Route& r, const std::vector<int32_t>& slot_var,
                              std::vector<uint32_t>& out, int vbase_dw, const std::vector<int>& lab, int m2s, int dummy0,
                              int* ndummy, int anneal, int anneal_iters = -1, int tail_base = -1) {
@@ -776,7 +763,7 @@ static void build_slot_edges(const qldpc_graph* g, const Route& r, const std::ve
 // / SQ_LDS_IDX_ACTIVE (tools/lds_model.py).
 static void lds_model_var_phase(const std::vector<uint32_t>& edges, const Route& r, uint32_t vbase, int64_t* out) {
   const int TB = r.TB, VPL = r.VPL, DM = r.DMAX, d3k = r.d3k;
-  const bool m2s = r.m2s == 1;
+  const bool m2s = r.m2s != 0;
   static const int kB128[4][16] = {{0, 1, 2, 3, 12, 13, 14, 15, 20, 21, 22, 23, 24, 25, 26, 27},
                                    {4, 5, 6, 7, 8, 9, 10, 11, 16, 17, 18, 19, 28, 29, 30, 31},
                                    {32, 33, 34, 35, 44, 45, 46, 47, 52, 53, 54, 55, 56, 57, 58, 59},
@@ -1185,7 +1172,7 @@ static void admit_tail(const qldpc_graph* g, int vars_per_thread, Route& r) {
 // The headline hgp_34_n1600 image drops from 65.0 KB to 52.3 KB: 3 workgroups per CU instead
 // of 2.  The kernel keeps no dummy edges for real variables, so every column degree must be
 // 3 or 4 with the degree-3 variables filling whole variable slots (host degree sort).
-// (`uniform`: QLDPC_M2S_UNIL kernels hold one prior for every variable)
+// (`uniform`: the kernels hold one prior for every variable)
 static void admit_m2s(const qldpc_graph* g, bool uniform, int vars_per_thread, Route& r) {
   if (!(r.engine == 3 && r.precision == 64 && r.DMAX == 4 && !r.tail && g->max_row >= 1 && g->max_row <= 7 &&
         env_int("QLDPC_M2S", 1) != 0 && env_int("QLDPC_DEGSORT", 1) != 0))
@@ -1205,31 +1192,6 @@ static void admit_m2s(const qldpc_graph* g, bool uniform, int vars_per_thread, R
       !(n3 % tb == 0 || n3 == g->n) || !fits(c, g))
     return;
   r = c;
-  // "c2v in slot" (bp_reg.h eng_c2s, kern_r_f64_c2s.hip, opt-in QLDPC_C2S=1): the check phase
-  // writes the c2v of every edge into the row's slots, so no row may have a padding slot:
-  // every row exactly 7 edges (the headline HGP graphs).  No CS array (n1600 52.3 -> 46.2 KB)
-  // and 25 % fewer VALU, but its check phase stores 7 words per row where m2s stores 2, and
-  // LDS stores cost 3x the cycles of reads per byte: 1.141 M vs 1.189 M shots/s
-  // (profiles/r03/c2s/), so m2s stays the default
-  bool full = true;
-  for (int i = 0; i < g->m && full; ++i) full = g->row_ptr[i + 1] - g->row_ptr[i] == 7;
-  c.m2s = 2;
-  if (full && QLDPC_EXPERIMENTAL && env_int("QLDPC_C2S", 0) != 0 && fits(c, g)) r.m2s = 2;
-  // variable-major V slots (bp_reg.h eng_m2v, kern_r_f64_m2v.hip): edge (k, d) of lane t at
-  // slot (ecnt(k) + d) * 256 + t, the last variable slot at ecnt * 256 + d * NL + t, then one
-  // sentinel slot; the check phase's rows come from a register table (m <= 4 * 256)
-  const int d3 = n3 == g->n ? vpl : n3 / 256;
-  const int nlast = g->n - (vpl - 1) * 256, NL = (nlast + 63) & ~63;
-  const int ecl = 3 * std::min(vpl - 1, d3) + 4 * std::max(0, vpl - 1 - d3);
-  Route v = r;
-  v.m2s = 3;
-  v.tail = 0;
-  v.vslots_m2v = ecl * 256 + (vpl - 1 < d3 ? 3 : 4) * NL + 1;
-  v.m2v_vlast = ecl * 256;
-  v.m2v_nl = NL;
-  if (r.m2s == 1 && tb == 256 && g->m <= 4 * 256 && v.vslots_m2v * 8 < 65536 && QLDPC_EXPERIMENTAL &&
-      env_int("QLDPC_M2V", 0) != 0 && fits(v, g))
-    r = v;
 }
 
 // fp64 space-time graphs on the tail layout (rows of 8 / 9 as 4 chunks + a tail slot, 1024 threads,
@@ -1329,17 +1291,16 @@ static void admit_m2s8(const qldpc_graph* g, bool uniform, int pref, int vmax, i
   r.m2s_pk = env_int("QLDPC_M2S8_PK", 1) != 0 && vpl <= 5 && 4 * route_lds(c, route_vslots(c, g->m), g->m) <= (size_t)kLdsMax;
 }
 
-// The route of a min-sum decoder and its slot map (engines 2-4: the variable of every (k, t) slot,
+// The route of a min-sum decoder and its slot map (engines 2-3: the variable of every (k, t) slot,
 // -1 = padding), from the graph, whether the priors are uniform, and the QLDPC_* switches.
 static int plan_route(const qldpc_graph* g, bool uniform, int precision, int vars_per_thread, int min_col_slots,
                       int forced_engine, Route& r, std::vector<int32_t>& slot_var) {
   const int want_engine = forced_engine ? forced_engine : env_int("QLDPC_ENGINE", 3);
-  if (want_engine == 4 && !QLDPC_EXPERIMENTAL)
-    return set_err(QLDPC_ENOTSUP, "engine 4 is built only with -DQLDPC_EXPERIMENTAL=1 (tools/build_variant.py)");
+  if (want_engine == 4) return set_err(QLDPC_ENOTSUP, "engine 4 (c2v computed by the check phase) was removed");
   r = Route();
   slot_var.clear();
   r.precision = precision;
-  r.engine = ((want_engine >= 1 && want_engine <= 4) || want_engine == 6) ? want_engine : 3;
+  r.engine = ((want_engine >= 1 && want_engine <= 3) || want_engine == 6) ? want_engine : 3;
   // column degree > 8: beyond the LDS engines' edge slots -> engine 6 (row and column degree <= 12); soft BP stays engine 1
   if ((g->max_col > 8 || min_col_slots > 8) && r.engine != 6) {
     if (r.engine == 1) return set_err(QLDPC_ENOTSUP, "column degree > 8");
@@ -1359,8 +1320,7 @@ static int plan_route(const qldpc_graph* g, bool uniform, int precision, int var
     r.lds_bytes = (int)lds_for(precision, g->m);
     return get_variant(precision, r.VPL, r.DMAX).dec_k ? 0 : set_err(QLDPC_ENOTSUP, "no kernel variant");
   }
-  if (r.engine == 4 && g->max_row > 8) r.engine = 3;  // engine 4 rows are 8 slots wide
-  r.nch = r.engine == 4 ? 8 * tsize / 16 : (std::max(1, g->max_row) * tsize + 15) / 16;
+  r.nch = (std::max(1, g->max_row) * tsize + 15) / 16;
   // no LDS image addresses this many slots: HBM-resident messages (engine 6)
   if (route_vslots(r, g->m) >= 0xFFFF)
     return to_hbm(g, r, slot_var, "V image exceeds 65535 message slots (QLDPC_HBM_FALLBACK=0)");
@@ -1376,7 +1336,7 @@ static int plan_route(const qldpc_graph* g, bool uniform, int precision, int var
   admit_m2st(g, uniform, vars_per_thread, r);
   admit_d5_256(g, r, pref, vars_per_thread, vmax);
   admit_m2s8(g, uniform, pref, vmax, vars_per_thread, r);
-  if (r.engine >= 3 && ((r.DMAX != 4 && !(r.engine == 3 && (r.DMAX == 5 || r.DMAX == 6))) ||
+  if (r.engine == 3 && ((r.DMAX != 4 && r.DMAX != 5 && r.DMAX != 6) ||
                         (!r.fb && choose_rgeometry(g->n, g->m, vars_per_thread, r.TB, r.VPL, pref, vmax)) || !fits(r, g) ||
                         (precision == 64 && r.DMAX == 5 && !r.m2s && !use_f64w(r)))) {
     r.ea_shift = r.tail = r.m2s = r.vslots_dummy = r.m2s_pk = r.fb = 0;
@@ -1385,7 +1345,7 @@ static int plan_route(const qldpc_graph* g, bool uniform, int precision, int var
     if (r.DMAX == 5 || r.DMAX == 6) r.DMAX = 8;  // engine 2 kernels come in 4 and 8 slots
   }
   const int vslots = route_vslots(r, g->m);
-  if (r.engine >= 3) {
+  if (r.engine == 3) {
     r.NS = 1;
     r.lds_bytes = (int)route_lds(r, vslots, g->m);
   } else {
@@ -1413,7 +1373,7 @@ static int plan_route(const qldpc_graph* g, bool uniform, int precision, int var
   // byte-F kernels also keep degree <= 2 variables (the space-time measurement columns) in
   // compile-time 2-edge slots: those go first
   const bool sort2 = sort3 && (r.fb || (r.tail && precision == 64 && (!r.m2s || r.nch == 4))) && env_int("QLDPC_D2K", 1) != 0;
-  if (r.engine == 3 && precision == 64 && r.tail && r.m2s == 1 && r.nch == 4) {
+  if (r.engine == 3 && precision == 64 && r.tail && r.m2s && r.nch == 4) {
     // (the fp64 space-time m2s family: st_plan's order, degree classes 1 / 2 / 3 / 4 with narrow waves)
     slot_var = st_plan(g, r.TB, r.VPL, r.DMAX, env_int("QLDPC_NW", 1) != 0, env_int("QLDPC_NW_BAL", 1) != 0).slots;
   } else {
@@ -1423,161 +1383,22 @@ static int plan_route(const qldpc_graph* g, bool uniform, int precision, int var
   r.d3k = sort3 ? leading_slots(g, slot_var, r.TB, r.VPL, 3) : 0;
   r.d2k = sort2 ? leading_slots(g, slot_var, r.TB, r.VPL, 2) : 0;
   // fp64 engine-3 kernels are built with D3K = 0 only, except the <= 256-thread family
-  if (precision != 32 && !use_f64w(r) && !use_f64x(r) && !r.tail && !r.m2s) r.d3k = 0;
+  if (precision != 32 && !use_f64w(r) && !r.tail && !r.m2s) r.d3k = 0;
   if (slot_variant(r).dec_k) return 0;
-  // no kernel compiled for this engine-3/4 geometry (e.g. fp32 images past 64 KiB at 8 variables per
+  // no kernel compiled for this engine-3 geometry (e.g. fp32 images past 64 KiB at 8 variables per
   // thread, GenBicycleA4 over five rounds): the HBM-resident engine serves any graph
-  return (r.engine == 3 || r.engine == 4) ? to_hbm(g, r, slot_var, "no kernel variant") : set_err(QLDPC_ENOTSUP, "no kernel variant");
+  return r.engine == 3 ? to_hbm(g, r, slot_var, "no kernel variant") : set_err(QLDPC_ENOTSUP, "no kernel variant");
 }
 
 // ------------------------------------------------------------ host tables
 struct HostTables {
-  std::vector<uint32_t> edges;   // engine 1: packed u16 check ids; engines 2-4: edge words
-  std::vector<int> lab;          // engine 3: label of each check (empty = identity)
-  std::vector<uint8_t> rdeg;     // engines 3/4: row degrees by check label
-  std::vector<uint32_t> rowtab;  // m2v: the check phase's row table
+  std::vector<uint32_t> edges;  // engine 1: packed u16 check ids; engines 2-3: edge words
+  std::vector<int> lab;         // engine 3: label of each check (empty = identity)
+  std::vector<uint8_t> rdeg;    // engine 3: row degrees by check label
 };
 
-// m2v lane search (opt-in QLDPC_M2V_PERM=1: measured 1.6 % slower): a variable's V slots sit in its
-// lane's bank pair (slot mod 32 = lane mod 32), so which lane a variable occupies inside its slot k
-// sets the banks of the check phase's gathers.  A seeded local search swaps two variables of one
-// slot k (same degree class) whenever that does not raise Σ_{row group of 32, bank} load² (the
-// check gathers; a group whose bank loads are all <= 7 admits conflict-free gather orders) +
-// Σ_{32-lane group, edge, bank} count² of the variable phase's CS gathers (bank pair = (check + 1)
-// mod 32).  Storage only.
-static void m2v_lane_search(const qldpc_graph* g, const Route& r, std::vector<int32_t>& slot_var) {
-  const int TBm = r.TB, VPLm = r.VPL, DM = r.DMAX, M = g->m;
-  const int ng = (M + 31) / 32;
-  std::vector<int> L((size_t)ng * 32, 0);                       // check groups x banks
-  std::vector<int> C((size_t)VPLm * DM * (TBm / 32) * 32, 0);   // CS gather groups x banks
-  auto cidx = [&](int k, int d, int h, int b) { return (((size_t)k * DM + d) * (TBm / 32) + h) * 32 + b; };
-  auto add = [&](int j, int pos, int sg) {
-    const int k = pos / TBm, t = pos % TBm, b = t % 32, h = t / 32;
-    const auto& rows = g->col_rows[j];
-    for (int d = 0; d < (int)rows.size(); ++d) {
-      L[(size_t)(rows[d] / 32) * 32 + b] += sg;
-      C[cidx(k, d, h, (rows[d] + 1) % 32)] += sg;
-    }
-  };
-  auto sq = [&](int j, int pos) {  // Σ of the counts this variable's entries see (for the delta)
-    const int k = pos / TBm, t = pos % TBm, b = t % 32, h = t / 32;
-    long long v = 0;
-    const auto& rows = g->col_rows[j];
-    for (int d = 0; d < (int)rows.size(); ++d) v += 2 * L[(size_t)(rows[d] / 32) * 32 + b] + C[cidx(k, d, h, (rows[d] + 1) % 32)];
-    return v;
-  };
-  for (int pos = 0; pos < VPLm * TBm; ++pos)
-    if (slot_var[pos] >= 0) add(slot_var[pos], pos, +1);
-  uint64_t rs = 0xD1B54A32D192ED03ull;
-  auto rnd = [&]() { rs ^= rs << 13; rs ^= rs >> 7; rs ^= rs << 17; return rs; };
-  const int iters = env_int("QLDPC_M2V_PERM_IT", 400000);
-  for (int it = 0; it < iters; ++it) {
-    const int k = (int)(rnd() % (uint64_t)VPLm);
-    const int pa = k * TBm + (int)(rnd() % (uint64_t)TBm), pb = k * TBm + (int)(rnd() % (uint64_t)TBm);
-    const int ja = slot_var[pa], jb = slot_var[pb];
-    if (ja < 0 || jb < 0 || pa == pb || (pa % 32) == (pb % 32) && (pa / 32) == (pb / 32)) continue;
-    if (g->col_rows[ja].size() != g->col_rows[jb].size()) continue;
-    // cost change: remove both, measure, add swapped, measure (counts are small integers)
-    add(ja, pa, -1);
-    add(jb, pb, -1);
-    const long long before = sq(ja, pa) + sq(jb, pb);
-    const long long after = sq(ja, pb) + sq(jb, pa);
-    if (after <= before) {
-      slot_var[pa] = jb;
-      slot_var[pb] = ja;
-      add(jb, pa, +1);
-      add(ja, pb, +1);
-    } else {
-      add(ja, pa, +1);
-      add(jb, pb, +1);
-    }
-  }
-}
-
-// m2v row table (bp_reg.h M2vRows): row i = q * TB + t -> uint4 (q * TB + t): the byte offsets
-// from the V base of its edges' variable-major slots, two 16-bit offsets per word, the unused
-// entries at the sentinel slot
-static int m2v_row_table(const qldpc_graph* g, const Route& r, const std::vector<int32_t>& slot_var,
-                         std::vector<uint32_t>& tab) {
-  const int TBm = r.TB, VPLm = r.VPL, d3 = std::min(r.d3k, VPLm);
-  auto ecnt = [&](int k) { return 3 * std::min(k, d3) + 4 * std::max(0, k - d3); };
-  if (ecnt(VPLm - 1) * TBm != r.m2v_vlast) return set_err(QLDPC_ENOTSUP, "m2v layout mismatch");
-  const uint32_t sent = (uint32_t)(r.vslots_m2v - 1) * 8u;
-  std::vector<std::vector<uint32_t>> roff(g->m);
-  for (int k = 0; k < VPLm; ++k)
-    for (int t = 0; t < TBm; ++t) {
-      const int j = slot_var[(size_t)k * TBm + t];
-      if (j < 0) continue;
-      const auto& rows = g->col_rows[j];
-      for (int d = 0; d < (int)rows.size(); ++d) {
-        const int vs = k < VPLm - 1 ? (ecnt(k) + d) * TBm + t : r.m2v_vlast + d * r.m2v_nl + t;
-        roff[rows[d]].push_back((uint32_t)vs * 8u);
-      }
-    }
-  for (int i = 0; i < g->m; ++i) {
-    if (roff[i].size() > 7) return set_err(QLDPC_ENOTSUP, "m2v row wider than 7");
-    while (roff[i].size() < 8) roff[i].push_back(sent);
-  }
-  // The check phase gathers entry e of its rows with one ds_read_b64 per e: 32-lane groups,
-  // bank pair = slot mod 32 (MI355X_MICROARCH.md §LDS).  The order of a row's entries is
-  // free: per group of 32 rows, a seeded local search swaps two entries of a row whenever that
-  // does not raise Σ_e Σ_bank count² (the sentinel broadcasts: not counted).  Host work only.
-  if (env_int("QLDPC_M2V_ORDER", 1) != 0) {
-    uint64_t rs = 0x9E3779B97F4A7C15ull;
-    auto rnd = [&]() { rs ^= rs << 13; rs ^= rs >> 7; rs ^= rs << 17; return rs; };
-    for (int q = 0; q < 4; ++q)
-      for (int g0 = 0; g0 < TBm; g0 += 32) {
-        std::vector<int> rr;
-        for (int l = 0; l < 32; ++l)
-          if (q * TBm + g0 + l < g->m) rr.push_back(q * TBm + g0 + l);
-        if (rr.size() < 2) continue;
-        int cnt[7][32] = {{0}};
-        auto bk = [&](uint32_t o) { return (int)((o / 8u) % 32u); };
-        for (int i : rr)
-          for (int e = 0; e < 7; ++e)
-            if (roff[i][e] != sent) cnt[e][bk(roff[i][e])]++;
-        for (int it = 0; it < 4000; ++it) {
-          const int i = rr[rnd() % rr.size()], a = (int)(rnd() % 7), b = (int)(rnd() % 7);
-          const uint32_t oa = roff[i][a], ob = roff[i][b];
-          if (a == b || oa == ob) continue;
-          auto term = [&](int e, uint32_t o, int dlt) {  // change of count^2 when o enters (+1) / leaves (-1) e
-            if (o == sent) return 0;
-            const int c = cnt[e][bk(o)];
-            return dlt > 0 ? 2 * c + 1 : -(2 * c - 1);
-          };
-          int d = term(a, oa, -1);
-          if (oa != sent) cnt[a][bk(oa)]--;
-          d += term(b, ob, -1);
-          if (ob != sent) cnt[b][bk(ob)]--;
-          d += term(a, ob, +1);
-          if (ob != sent) cnt[a][bk(ob)]++;
-          d += term(b, oa, +1);
-          if (oa != sent) cnt[b][bk(oa)]++;
-          if (d <= 0) {
-            roff[i][a] = ob;
-            roff[i][b] = oa;
-          } else {  // undo
-            if (ob != sent) cnt[a][bk(ob)]--;
-            if (oa != sent) cnt[b][bk(oa)]--;
-            if (oa != sent) cnt[a][bk(oa)]++;
-            if (ob != sent) cnt[b][bk(ob)]++;
-          }
-        }
-      }
-  }
-  tab.assign((size_t)4 * TBm * 4, 0);
-  for (int q = 0; q < 4; ++q)
-    for (int t = 0; t < TBm; ++t) {
-      const int i = q * TBm + t;
-      uint32_t o[8];
-      for (int e = 0; e < 8; ++e) o[e] = i < g->m ? roff[i][e] : sent;
-      for (int w = 0; w < 4; ++w) tab[((size_t)q * TBm + t) * 4 + w] = o[2 * w] | (o[2 * w + 1] << 16);
-    }
-  return 0;
-}
-
-// The host tables of a planned decoder (bp->route, bp->slot_var; the m2v lane search may permute
-// the latter), plus its label / LDS-model statistics.
+// The host tables of a planned decoder (bp->route, bp->slot_var), plus its label / LDS-model
+// statistics.
 static int build_tables(qldpc_bp* bp, HostTables& T) {
   const qldpc_graph* g = bp->g;
   const Route& r = bp->route;
@@ -1599,26 +1420,23 @@ static int build_tables(qldpc_bp* bp, HostTables& T) {
   }
   const int tsize = r.precision == 32 ? 4 : 8;
   const RLayout L = route_layout(r, route_vslots(r, g->m), g->m);
-  if (r.m2s == 3 && env_int("QLDPC_M2V_PERM", 0) != 0) m2v_lane_search(g, r, bp->slot_var);
   // fp64 two-word families (measured +3 % with the bank-aware fp64 v2c placement); fp32 gathers of
   // the structured codes are already near conflict-free, and the m2s family runs 2.5 % faster on
   // the identity labels (1.188 M vs 1.159 M shots/s, profiles/r03/m2s_ab/ab_label.txt): off there
   // (QLDPC_LABEL=1 forces it on)
   if (r.engine == 3 && env_int("QLDPC_LABEL", r.precision == 64 && !r.m2s ? 1 : 0) != 0)
     T.lab = label_checks(g, r, bp->slot_var, &bp->gather_conf[0], &bp->gather_conf[1]);
-  const bool f64e3 = r.engine == 3 && r.precision == 64 && r.m2s != 3;
+  const bool f64e3 = r.engine == 3 && r.precision == 64;
   int ndummy = 0;
   build_slot_edges(g, r, bp->slot_var, T.edges, (r.engine == 3 && env_int("QLDPC_BANKOPT", 1) != 0) ? (int)(L.v / 4) : -1,
-                   T.lab, r.m2s == 1 && env_int("QLDPC_M2S_PLACE", 1) != 0,
+                   T.lab, r.m2s && env_int("QLDPC_M2S_PLACE", 1) != 0,
                    r.vslots_dummy ? (1 + g->m * r.nch) * (16 / tsize) : -1, &ndummy,
                    !f64e3 ? 0 : (r.m2s || r.tail) ? 1 : env_int("QLDPC_ANNEAL_2W", 1) != 0 ? 2 : 0, -1,
                    (r.tail && r.vslots_dummy) ? (int)(L.t - L.v) / tsize : -1);
   if (ndummy != r.vslots_dummy) return set_err(QLDPC_EINVAL, "m2s private dummy slot count mismatch");
   if (f64e3 && r.ea_shift == 0) lds_model_var_phase(T.edges, r, L.v, bp->lds_model);
-  if (r.m2s == 3)
-    if (const int rc = m2v_row_table(g, r, bp->slot_var, T.rowtab)) return rc;
-  if (r.engine >= 3) {
-    // row degrees by check label: engine 4 keeps them in F, engine 3 their parity (bp_reg.h, w domain)
+  if (r.engine == 3) {
+    // row degrees by check label: the kernels keep their parity in F (bp_reg.h, w domain)
     T.rdeg.resize(std::max(1, g->m));
     for (int i = 0; i < g->m; ++i) T.rdeg[T.lab.empty() ? i : T.lab[i]] = (uint8_t)(g->row_ptr[i + 1] - g->row_ptr[i]);
   }
@@ -1650,7 +1468,7 @@ static int create_min_sum(qldpc_graph* g, const double* channel_probs, int32_t m
   bp->method = bp_method;
   bp->alpha = ms_scaling_factor;
   bp->probs.assign(channel_probs, channel_probs + g->n);
-  if ((rc = plan_route(g, !QLDPC_M2S_UNIL || uniform_priors(channel_probs, g->n), precision, vars_per_thread,
+  if ((rc = plan_route(g, uniform_priors(channel_probs, g->n), precision, vars_per_thread,
                        min_col_slots, forced_engine, bp->route, bp->slot_var)))
     return fail(rc);
   const Route& r = bp->route;
@@ -1668,8 +1486,7 @@ static int create_min_sum(qldpc_graph* g, const double* channel_probs, int32_t m
       for (int i = 0; i < g->m; ++i) inv[T.lab[i]] = i;
       if ((rc = upload(bp->rperm, inv.data(), inv.size() * 4, "upload check labels"))) return fail(rc);
     }
-    if ((r.m2s == 3 && (rc = upload(bp->rowtab, T.rowtab.data(), T.rowtab.size() * 4, "upload m2v row table"))) ||
-        (r.engine >= 3 && (rc = upload(bp->rdeg, T.rdeg.data(), T.rdeg.size(), "upload row degrees"))) ||
+    if ((r.engine == 3 && (rc = upload(bp->rdeg, T.rdeg.data(), T.rdeg.size(), "upload row degrees"))) ||
         (rc = upload(bp->vchk, T.edges.data(), T.edges.size() * 4, "upload edge table")) ||
         (!bp->slot_var.empty() && (rc = upload(bp->perm, bp->slot_var.data(), bp->slot_var.size() * 4, "upload slot map"))) ||
         (rc = bp->llr.alloc((size_t)r.VPL * r.TB * tsize)))
@@ -1694,7 +1511,7 @@ int qldpc_bp_plan(const qldpc_graph* g, const double* channel_probs, int32_t bp_
   if (bp_method == QLDPC_PRODUCT_SUM) return set_err(QLDPC_ENOTSUP, "the product-sum geometry needs the device");
   Route r;
   std::vector<int32_t> slot_var;
-  if ((rc = plan_route(g, !QLDPC_M2S_UNIL || uniform_priors(channel_probs, g->n), precision, vars_per_thread,
+  if ((rc = plan_route(g, uniform_priors(channel_probs, g->n), precision, vars_per_thread,
                        min_col_slots, 0, r, slot_var)))
     return rc;
   const int32_t v[8] = {r.engine, route_kernel_id(r), r.nch, r.TB, r.VPL, r.lds_bytes, r.engine == 3 ? r.d3k : 0,
@@ -1706,7 +1523,7 @@ int qldpc_bp_plan(const qldpc_graph* g, const double* channel_probs, int32_t bp_
 int qldpc_bp_destroy(qldpc_bp* bp) {
   if (!bp) return 0;
   if (bp->bp1) qldpc_firstmin_destroy(bp->bp1);
-  for (DevBuf* d : {&bp->vchk, &bp->llr, &bp->rdeg, &bp->rowtab, &bp->perm, &bp->rperm, &bp->work, &bp->ps_rp, &bp->ps_ci, &bp->ps_cp,
+  for (DevBuf* d : {&bp->vchk, &bp->llr, &bp->rdeg, &bp->perm, &bp->rperm, &bp->work, &bp->ps_rp, &bp->ps_ci, &bp->ps_cp,
                     &bp->ps_ce, &bp->ps_ws, &bp->h_rp, &bp->h_rcol, &bp->h_rcpos, &bp->h_cp, &bp->h_crpos, &bp->h_ws,
                     &bp->rl_gam, &bp->rl_wq, &bp->sr_cr, &bp->sr_ord, &bp->sr_lp, &bp->side_llr, &bp->side_wq})
     d->release();
@@ -1816,7 +1633,7 @@ int qldpc_bp_create_serial(qldpc_graph* g, const double* channel_probs, int32_t 
 
 int qldpc_bp_set_channel_probs(qldpc_bp* bp, const double* channel_probs) {
   if (!bp || !channel_probs) return set_err(QLDPC_EINVAL, "NULL argument");
-  if (bp->route.m2s && QLDPC_M2S_UNIL && !uniform_priors(channel_probs, bp->g->n))
+  if (bp->route.m2s && !uniform_priors(channel_probs, bp->g->n))
     return set_err(QLDPC_ENOTSUP, "this decoder's kernels hold one uniform prior: create a new decoder for "
                                   "non-uniform channel_probs");
   bp->probs.assign(channel_probs, channel_probs + bp->g->n);
@@ -1962,9 +1779,8 @@ static SSector ssector_of(const qldpc_bp* bp, const unsigned long long* lmask, i
   s.nch = bp->route.nch;
   s.vpl = bp->route.VPL;
   s.alpha = bp->alpha;
-  s.rows = static_cast<const uint32_t*>(bp->rowtab.p);
-  s.vlast = bp->route.m2v_vlast;
-  s.vnl = bp->route.m2v_nl;
+  s.rows = nullptr;
+  s.vlast = s.vnl = 0;
   s.npos = bp->npos > 0 ? bp->npos : bp->g->n;
   s.nw = bp->route.nw;
   s.live_last = bp->route.live_last;
@@ -2124,7 +1940,7 @@ int qldpc_mc_create(qldpc_bp* dec_x, const qldpc_graph* logical_x, qldpc_bp* dec
                       (dec_x && dec_z &&
                        (dec_x->route.m2s != dec_z->route.m2s || dec_x->route.tail != dec_z->route.tail || dec_x->route.fb != dec_z->route.fb ||
                         dec_x->route.m2s_pk != dec_z->route.m2s_pk)) ||
-                      // one-slot families (m2s / c2s / m2v) keep no dummy edge on a real variable:
+                      // the one-slot family (m2s) keeps no dummy edge on a real variable:
                       // the kernel's compile-time D3K must be each sector's own (a degree-3
                       // variable past it would run the 4-edge path and read the shared dummy slot)
                       (dec_x && dec_z && dec_x->route.m2s && dec_x->route.d3k != dec_z->route.d3k) ||

@@ -20,14 +20,10 @@ struct Route {
   int d2k = 0;  // byte-F family: compile-time degree-2 slot count (slots of the measurement variables)
   int ea_shift = 0;  // engine 3: 2 = dword-scaled LDS addresses in the edge words (images > 64 KiB)
   int tail = 0;      // engine 3: 1 = rows of nch chunks + one tail slot per row (bp_reg.h eng_tail)
-  int m2s = 0;       // engine 3: 1 = one-word check state, m2 in the argmin slot (bp_reg.h eng_m2s);
-                     // 3 = the same with variable-major V slots (eng_m2v);
-                     // 2 = c2v written into the slots by the check phase (eng_c2s)
+  int m2s = 0;       // engine 3: 1 = one-word check state, m2 in the argmin slot (bp_reg.h eng_m2s)
   int fb = 0;        // engine 3: 1 = byte F words (fp32 space-time family, 512 threads; bp_reg.h eng_fb)
   int m2s_pk = 0;        // m2s rows of 8 with packed absolute edge addresses (engine id 10203)
   int vslots_dummy = 0;  // m2s rows of 8 (engine id 10103): private V slots of real variables' missing edges
-  int vslots_m2v = 0;    // m2v: V slots of the variable-major layout (0 = row-major formula)
-  int m2v_vlast = 0, m2v_nl = 0;  // m2v: first V slot of the last variable slot, its per-edge stride
   uint32_t nw = 0;         // narrow waves of the fp64 space-time m2s family (SSector::nw)
   uint32_t live_last = 0;  // its waves live in the last variable slot (SSector::live_last)
   int lds_bytes = 0;
@@ -35,7 +31,7 @@ struct Route {
 
 // V slots of the LDS image of a graph with m checks
 inline int route_vslots(const Route& r, int m) {
-  return r.vslots_m2v ? r.vslots_m2v : (1 + m * r.nch) * (r.precision == 32 ? 4 : 2) + r.vslots_dummy;
+  return (1 + m * r.nch) * (r.precision == 32 ? 4 : 2) + r.vslots_dummy;
 }
 
 }  // namespace qldpc_rt

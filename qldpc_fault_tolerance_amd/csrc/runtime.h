@@ -4,12 +4,6 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-// measured-and-not-kept kernel families (c2s, m2v, fp64 x 512 threads, engine 4): out of the
-// product build unless -DQLDPC_EXPERIMENTAL=1
-#ifndef QLDPC_EXPERIMENTAL
-#define QLDPC_EXPERIMENTAL 0
-#endif
-
 #include <cmath>
 #include <string>
 #include <vector>
@@ -80,12 +74,11 @@ struct qldpc_bp {
   // BP (firstmin.hip), built on first use from these priors; dropped when they change
   qldpc_firstmin* bp1 = nullptr;
   bool bp1_off = false;
-  qldpc_rt::DevBuf vchk, llr;  // engine 1: packed u16 check ids; engines 2-4: edge words (check | slot<<16)
-  qldpc_rt::DevBuf rdeg;       // engines 3/4: u8 row degrees (by check label)
-  qldpc_rt::DevBuf rowtab;     // m2v: the check phase's row table [kM2vRows][TB] x 4 u32
+  qldpc_rt::DevBuf vchk, llr;  // engine 1: packed u16 check ids; engines 2-3: edge words (check | slot<<16)
+  qldpc_rt::DevBuf rdeg;       // engine 3: u8 row degrees (by check label)
   int npos = 0;       // 1 + the last slot position holding a variable (SSector::npos)
   qldpc_rt::DevBuf work;       // engine 3 decode_batch: chunk-queue head
-  std::vector<int32_t> slot_var;  // engines 2-4: variable of each (k, t) slot (-1 = padding)
+  std::vector<int32_t> slot_var;  // engines 2-3: variable of each (k, t) slot (-1 = padding)
   qldpc_rt::DevBuf perm;
   qldpc_rt::DevBuf rperm;  // engine 3: original check of each check label (label_checks)
   int gather_conf[2] = {0, 0};  // engine 3: extra gather cycles per pass before / after labelling

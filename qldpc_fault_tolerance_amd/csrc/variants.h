@@ -9,12 +9,6 @@
 #pragma once
 #include "bp_reg.h"
 
-// measured-and-not-kept kernel families (c2s, m2v, fp64 x 512 threads, engine 4): out of the
-// product build unless -DQLDPC_EXPERIMENTAL=1
-#ifndef QLDPC_EXPERIMENTAL
-#define QLDPC_EXPERIMENTAL 0
-#endif
-
 namespace qldpc {
 
 using DecLaunch = hipError_t (*)(dim3, dim3, size_t, hipStream_t, const DecArgs&);
@@ -52,7 +46,6 @@ SVariant get_rvariant_f32_w(int vpl, int d3k);  // kern_r_f32_w.hip: compile-tim
 SVariant get_rvariant_f64_w(int vpl, int d3k, int nch);  // kern_r_f64_w{3,4}.hip: <= 256 threads, own v2c in VGPRs, D3K
 SVariant get_rvariant_f64_w3(int vpl, int d3k);
 SVariant get_rvariant_f64_w_d5(int vpl, int d3k, int nch);  // kern_r_f64_d5.hip: column degree 5
-SVariant get_rvariant_f64_x(int vpl, int d3k);  // kern_r_f64_x.hip: 257-512 threads, 128 VGPRs (opt-in)
 SVariant get_rvariant_f64_w4(int vpl, int d3k);
 SVariant get_rvariant_f64_st(int vpl, int d3k, int d2k = 0);  // kern_r_f64_st*.hip: tail layout, 1024 threads (engine id 1013)
 SVariant get_rvariant_f64_st_hi(int vpl, int d3k);
@@ -61,12 +54,7 @@ SVariant get_rvariant_f64_m2st(int vpl, int d3k, int d2k);  // kern_r_f64_m2st.h
 SVariant get_rvariant_f64_m2s(int vpl, int d3k);  // kern_r_f64_m2s.hip: m2 in the argmin slot, rows of 3 chunks + tail (engine id 11103)
 SVariant get_rvariant_f64_m2s8(int vpl, int d3k);  // kern_r_f64_m2s8.hip: m2s, rows of 4 chunks (8 edges), column degree 5 (engine id 10103)
 SVariant get_rvariant_f64_m2s8pk(int vpl, int d3k);  // the same with packed absolute edge addresses, 4 per CU (engine id 10203)
-SVariant get_rvariant_f64_m2v(int vpl, int d3k);  // kern_r_f64_m2v.hip: m2s with variable-major V slots (engine id 40103)
-SVariant get_rvariant_f64_c2s(int vpl, int d3k);  // kern_r_f64_c2s.hip: c2v written by the check phase into the slots (engine id 31103)
 SVariant get_rvariant_f32_stfb(int vpl, int d3k, int d2k);  // kern_r_f32_stfb.hip: fp32 tail layout, byte F, 512 threads (engine id 21013 + 100000 * D2K)
-SVariant get_r4variant_f32(int vpl);
-SVariant get_r4variant_f64(int vpl);
-SVariant get_r4variant_f64_w(int vpl);  // <= 256 threads
 SVariant get_svariant_f32_d4(int ns);
 SVariant get_svariant_f32_d8(int ns);
 SVariant get_svariant_f64_d4(int ns);
@@ -148,7 +136,7 @@ SVariant make_rvariant() {
                   reinterpret_cast<const void*>(&rdec_kernel<T, DM, VPL, ENG, D3K, LB, NCH>),
                   reinterpret_cast<const void*>(&rmc_kernel<T, DM, VPL, ENG, D3K, LB, NCH>)};
 }
-// D3K = 0 only (fp64 and engine 4)
+// D3K = 0 only (the plain fp64 kernels, kern_r_f64.hip)
 template <typename T, int ENG>
 SVariant pick_rvpl(int vpl) {
   switch (vpl) {

@@ -69,6 +69,36 @@ def test_hbm_fallback_switch_turns_the_fallback_into_enotsup():
     assert e.value.rc == _native.ENOTSUP
 
 
+def _removed_family_graphs():
+    code = codes.get_code("hgp_34_n1600")
+    return {
+        "n1600-hz": lambda: codes.CSR.from_dense(code.hz),
+        "n1600-hx": lambda: codes.CSR.from_dense(code.hx),
+        # 512 threads x 4 variables on the plain fp64 kernels: the geometry the removed 257-512-thread
+        # family took
+        "n1225-hI-512-threads": lambda: rf.graph("hgp_34_n1225_q3", "hI"),
+    }
+
+
+@pytest.mark.parametrize("name", list(_removed_family_graphs()))
+def test_switches_of_the_removed_families_move_no_plan(name):
+    """QLDPC_C2S / QLDPC_M2V / QLDPC_M2V_PERM / QLDPC_F64X selected kernel families that were measured,
+    not kept and removed: the plan is the one with none of them set."""
+    H = _removed_family_graphs()[name]()
+    pr = rf.PROB * np.ones(H.n)
+    plain = plan_bp(H, pr, precision=64)
+    if name.startswith("n1225"):
+        assert 256 < plain["threads"] <= 512 and plain["engine"] == 3, plain
+    with rf.switches({"QLDPC_C2S": "1", "QLDPC_M2V": "1", "QLDPC_M2V_PERM": "1", "QLDPC_F64X": "1"}):
+        assert plan_bp(H, pr, precision=64) == plain
+
+
+def test_engine_4_is_not_supported():
+    with pytest.raises(_native.QldpcError) as e:
+        _plan("hgp_34_n225", "hz", 64, QLDPC_ENGINE="4")
+    assert e.value.rc == _native.ENOTSUP
+
+
 def test_product_sum_has_no_host_plan():
     H = rf.graph("hgp_34_n225", "hz")
     with pytest.raises(_native.QldpcError) as e:
