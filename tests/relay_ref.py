@@ -39,8 +39,9 @@ def priors(channel_probs, precision):
     return [T(v) for v in l64], [int(math.floor(v * 4294967296.0 + 0.5)) for v in l64]
 
 
-def decode_one(csr, l0, wq, gam, pre_iter, num_legs, leg_iter, stop_nconv, alpha, precision, synd):
-    """One syndrome -> (corr [n] uint8, iters, conv, nsol)."""
+def decode_one(csr, l0, wq, gam, pre_iter, num_legs, leg_iter, stop_nconv, alpha, precision, synd, trace=None):
+    """One syndrome -> (corr [n] uint8, iters, conv, nsol).  ``trace``: a list that receives, per
+    solution of the chain in order, (leg, integer weight, decision vector as a tuple)."""
     T = _number_type(precision)
     m, n = csr.m, csr.n
     rp = [int(v) for v in csr.row_ptr]
@@ -125,6 +126,8 @@ def decode_one(csr, l0, wq, gam, pre_iter, num_legs, leg_iter, stop_nconv, alpha
             continue
         nsol += 1
         w = sum(wq[j] for j in range(n) if dec[j])
+        if trace is not None:
+            trace.append((r, w, tuple(dec)))
         if best_w is None or w < best_w:
             best_w, best = w, list(dec)
         if nsol >= stop_nconv:
