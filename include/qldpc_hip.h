@@ -483,6 +483,17 @@ int qldpc_serial_decode_host(int32_t m, int32_t n, const int32_t *row_ptr, const
 int qldpc_bp_set_side_probs(qldpc_bp *bp, const double *p0, const double *p1);
 int qldpc_bp_decode_batch_side(qldpc_bp *bp, const uint8_t *d_synd, const uint8_t *d_side, uint8_t *d_corr,
                                int32_t *d_iters, uint8_t *d_conv, int64_t B, void *stream);
+/* Soft output of a side decode: corr / iters / conv exactly as qldpc_bp_decode_batch_side returns them
+ * (d_side = NULL: as qldpc_bp_decode_batch), and d_post [B][n], the posteriors after the last iteration.
+ * Engine 8: handles created with soft = 1 (post_j widened to double, as qldpc_bp_decode_batch_soft).
+ * Engine 7: handles with num_legs = 0 only; d_post[b][j] = (double) M_j after the last iteration, which
+ * with pre_gamma = 0 is ldpc's log_prob_ratios bit for bit.  The kernel writes the M it already holds in
+ * LDS in its output loop: no LDS byte, no barrier, one qldpc_bp_geometry.  QLDPC_ENOTSUP: any other
+ * engine, an engine-8 handle without soft, an engine-7 chain (num_legs > 0: a chain's best solution has
+ * no single posterior).  QLDPC_EINVAL: d_side without side tables.  qldpc_bp_decode_batch_soft keeps
+ * refusing engine 7. */
+int qldpc_bp_decode_batch_side_soft(qldpc_bp *bp, const uint8_t *d_synd, const uint8_t *d_side, uint8_t *d_corr,
+                                    int32_t *d_iters, uint8_t *d_conv, double *d_post, int64_t B, void *stream);
 int qldpc_relay_decode_host_side(int32_t m, int32_t n, const int32_t *row_ptr, const int32_t *col_idx,
                                  const double *p0, const double *p1, const uint8_t *side, int32_t pre_iter,
                                  double pre_gamma, int32_t num_legs, int32_t leg_iter, double gamma_lo,
@@ -493,6 +504,38 @@ int qldpc_serial_decode_host_side(int32_t m, int32_t n, const int32_t *row_ptr, 
                                   const double *p0, const double *p1, const uint8_t *side, int32_t max_iter,
                                   double ms_scaling_factor, int32_t precision, const uint8_t *synd, uint8_t *corr,
                                   int32_t *iters, uint8_t *conv, int64_t B, int32_t threads);
+
+/*
+ * OSD under side priors: the OSD half of X/Z-correlated BP+OSD decoding.
+ * THE LAW.  An OSD handle (host or GPU) may carry two probability tables p0[n], p1[n], every entry
+ * finite and strictly inside (0, 1).  They give two weight tables w_s[j] = log(1 / p_s[j]), computed on
+ * the host in double with libm exactly as qldpc_osd_create computes its weights.  A side decode takes
+ * side: uint8 [B][n], of which only bit 0 is read.  For syndrome b, a candidate x weighs
+ *   sum_{j: x_j = 1} w_{side[b][j] & 1}[j],   the terms added in ascending column order,
+ * and the first strictly lightest candidate wins.  The sort, the elimination, OSD-0, the candidate
+ * sets and the conv / bp_corr pass-through are those of the plain decode.  A side decode always takes
+ * the soft-weight path, even when each table is uniform.  side = 0 everywhere with p0 = the handle's
+ * channel_probs is the plain decode bit for bit (a uniform handle's popcount order included: a sum of
+ * k equal positive doubles is strictly increasing in k at these n); side = 1 everywhere is the plain
+ * decode of a handle built on p1.
+ *
+ * qldpc_osd_set_side_probs / qldpc_osd_gpu_set_side_probs: QLDPC_EINVAL for an entry outside (0, 1) or
+ * non-finite; may be called again to replace the tables; no plain decode changes.  The GPU form may
+ * regrow the handle's workspace (it waits for the device first); qldpc_osd_gpu_geometry is unchanged.
+ * qldpc_osd_decode_batch_side / qldpc_osd_gpu_decode_side: the plain decodes' arguments with side
+ * (d_side on the device); QLDPC_EINVAL when no side tables are set.  The GPU kernels are instantiations
+ * of their own (a compile-time switch): they stage the syndrome's n selected weights once in the
+ * workgroup's workspace slice, and the candidate walk reads one weight per set bit as the plain
+ * non-uniform path does.
+ */
+int qldpc_osd_set_side_probs(qldpc_osd *osd, const double *p0, const double *p1);
+int qldpc_osd_decode_batch_side(const qldpc_osd *osd, const uint8_t *synd, const double *post, const uint8_t *conv,
+                                const uint8_t *bp_corr, const uint8_t *side, uint8_t *out_osd0, uint8_t *out_osdw,
+                                int64_t B, int32_t threads);
+int qldpc_osd_gpu_set_side_probs(qldpc_osd_gpu *osd, const double *p0, const double *p1);
+int qldpc_osd_gpu_decode_side(qldpc_osd_gpu *osd, const uint8_t *d_synd, const double *d_post,
+                              const uint8_t *d_conv, const uint8_t *d_bp_corr, const uint8_t *d_side,
+                              uint8_t *d_out0, uint8_t *d_outw, int64_t B, void *stream);
 
 /*
  * X/Z-correlated decoding in the staged data-error shot loop.  direction: 0 = off, 1 = "x->z", 2 =
@@ -508,6 +551,25 @@ int qldpc_serial_decode_host_side(int32_t m, int32_t n, const int32_t *row_ptr, 
  * qldpc_mc_set_osd, and a handle with an OSD stage rejects a direction: QLDPC_ENOTSUP.
  */
 int qldpc_mc_set_channel_update(qldpc_mc *mc, int32_t direction);
+
+/*
+ * BP+OSD in the staged shot loop, with and without a direction.  Staged handles only (QLDPC_ENOTSUP
+ * otherwise); each OSD handle must be built on its sector decoder's graph (QLDPC_EINVAL), and the sector
+ * decoder must give soft output through qldpc_bp_decode_batch_side_soft (QLDPC_ENOTSUP otherwise: an
+ * engine-8 handle created with soft = 1, or an engine-7 handle with num_legs = 0).  NULL clears a sector.
+ * With a stage set, qldpc_mc_launch, qldpc_mc_run and qldpc_mc_launch_weight do, per sector: (1) BP with
+ * soft output, as a side decode for the second sector of a direction; (2) the GPU OSD over the batch with
+ * BP's conv flags, converged decodes keeping BP's correction; (3) outw is the sector's correction: it is
+ * what is folded, checked and written to d_corr, and with a direction the first sector's side bytes.
+ * With a direction, the second sector's OSD is qldpc_osd_gpu_decode_side on the same side bytes; its
+ * side tables are required (QLDPC_EINVAL from whichever of this call and qldpc_mc_set_channel_update
+ * comes second).  The iteration and non-converged counters stay BP's: sector_nonconv is the number of
+ * decodes handed to OSD.  The posterior buffer is [batch][n] doubles: with a stage set the staged batch
+ * is bounded so that it stays within QLDPC_OSD_CAPTURE_MB (default 2048; read as a real number by this
+ * call, so a fraction of a megabyte bounds a small code's batch), a multiple of 64, at least 64; shot keying does not depend on the batch, so no result changes with it.  qldpc_mc_set_osd (the
+ * fused engine-3 stage) keeps refusing staged handles.
+ */
+int qldpc_mc_set_staged_osd(qldpc_mc *mc, qldpc_osd_gpu *osd_x, qldpc_osd_gpu *osd_z);
 
 /* BP+OSD in the fused shot loop (bposd_decoder per sector, src/Decoders.py:26-41, inside
  * _single_run, src/Simulators.py:117-168): after qldpc_mc_set_osd, qldpc_mc_launch captures

@@ -39,6 +39,8 @@ EXPORTED = [
     "qldpc_bp_create_serial", "qldpc_serial_layers", "qldpc_serial_decode_host",
     "qldpc_bp_set_side_probs", "qldpc_bp_decode_batch_side", "qldpc_relay_decode_host_side",
     "qldpc_serial_decode_host_side", "qldpc_mc_set_channel_update",
+    "qldpc_bp_decode_batch_side_soft", "qldpc_osd_set_side_probs", "qldpc_osd_decode_batch_side",
+    "qldpc_osd_gpu_set_side_probs", "qldpc_osd_gpu_decode_side", "qldpc_mc_set_staged_osd",
 ]
 COMM_ID_BYTES = 128
 
@@ -267,6 +269,18 @@ def _declare(L):
                                                 _vp, _i64, _i32]
     L.qldpc_mc_set_channel_update.restype = ctypes.c_int
     L.qldpc_mc_set_channel_update.argtypes = [_vp, _i32]
+    L.qldpc_bp_decode_batch_side_soft.restype = ctypes.c_int
+    L.qldpc_bp_decode_batch_side_soft.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]
+    L.qldpc_osd_set_side_probs.restype = ctypes.c_int
+    L.qldpc_osd_set_side_probs.argtypes = [_vp, _vp, _vp]
+    L.qldpc_osd_decode_batch_side.restype = ctypes.c_int
+    L.qldpc_osd_decode_batch_side.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32]
+    L.qldpc_osd_gpu_set_side_probs.restype = ctypes.c_int
+    L.qldpc_osd_gpu_set_side_probs.argtypes = [_vp, _vp, _vp]
+    L.qldpc_mc_set_staged_osd.restype = ctypes.c_int
+    L.qldpc_mc_set_staged_osd.argtypes = [_vp, _vp, _vp]
+    L.qldpc_osd_gpu_decode_side.restype = ctypes.c_int
+    L.qldpc_osd_gpu_decode_side.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]
 
 
 def lib():

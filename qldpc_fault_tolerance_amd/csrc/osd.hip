@@ -40,6 +40,9 @@ struct qldpc_osd {
   std::vector<std::vector<int32_t>> col_rows;
   std::vector<double> w;  // log(1/p_j)
   bool uniform = true;
+  // side tables (qldpc_osd_set_side_probs): w_s[j] = log(1 / p_s[j]); a side decode weighs column j of
+  // syndrome b with w_{side[b][j] & 1}[j].  Empty until set.
+  std::vector<double> ws0, ws1;
 };
 
 namespace {
@@ -136,16 +139,20 @@ struct Work {
   std::vector<uint8_t> cand;
 };
 
-double soft_weight(const qldpc_osd& O, const uint8_t* x) {
+double soft_weight(const double* w, int n, const uint8_t* x) {
   double s = 0.0;
-  for (int j = 0; j < O.n; ++j)
-    if (x[j]) s += O.w[j];
+  for (int j = 0; j < n; ++j)
+    if (x[j]) s += w[j];
   return s;
 }
 
-// Decode one non-converged syndrome; writes OSD-0 and OSD-w corrections.
-void osd_one(const qldpc_osd& O, Work& K, const uint8_t* synd, const double* post, uint8_t* out0, uint8_t* outw) {
+// Decode one non-converged syndrome; writes OSD-0 and OSD-w corrections.  sw: the syndrome's own
+// weights [n] of a side decode (always the soft-weight path), or null for the handle's.
+void osd_one(const qldpc_osd& O, Work& K, const uint8_t* synd, const double* post, uint8_t* out0, uint8_t* outw,
+             const double* sw = nullptr) {
   const int m = O.m, n = O.n, rank = O.rank;
+  const bool uniform = O.uniform && !sw;
+  const double* wt = sw ? sw : O.w.data();
   K.cols.resize(n);
   std::iota(K.cols.begin(), K.cols.end(), 0);
   std::stable_sort(K.cols.begin(), K.cols.end(), [&](int a, int b) { return post[a] < post[b]; });
@@ -200,15 +207,15 @@ void osd_one(const qldpc_osd& O, Work& K, const uint8_t* synd, const double* pos
   // weight of OSD-0; candidates must be strictly lighter
   long long best_cnt = 0;
   double best_w = 0.0;
-  if (O.uniform) {
+  if (uniform) {
     for (int q = 0; q < RW; ++q) best_cnt += __builtin_popcountll(K.xs[q]);
   } else {
-    best_w = soft_weight(O, out0);
+    best_w = soft_weight(wt, n, out0);
   }
   std::copy(out0, out0 + n, outw);
   // candidate: x = xs ^ (xor of xh over t's bits); t bits are Ht positions
   auto consider = [&](const u64* x, const int* tj, int nt) {
-    if (O.uniform) {
+    if (uniform) {
       long long cnt = nt;
       for (int q = 0; q < RW; ++q) cnt += __builtin_popcountll(x[q]);
       if (cnt >= best_cnt) return;
@@ -218,9 +225,9 @@ void osd_one(const qldpc_osd& O, Work& K, const uint8_t* synd, const double* pos
     } else {
       expand(x, K.cand.data());
       for (int a = 0; a < nt; ++a) K.cand[K.ht[tj[a]]] = 1;
-      const double sw = soft_weight(O, K.cand.data());
-      if (sw >= best_w) return;
-      best_w = sw;
+      const double cw = soft_weight(wt, n, K.cand.data());
+      if (cw >= best_w) return;
+      best_w = cw;
       std::copy(K.cand.begin(), K.cand.end(), outw);
     }
   };
@@ -252,6 +259,20 @@ void osd_one(const qldpc_osd& O, Work& K, const uint8_t* synd, const double* pos
       }
   }
 }
+
+// w_s = log(1 / p_s) of a side table, as qldpc_osd_create computes w; false on an entry outside (0, 1)
+bool side_weights(const double* p, int n, std::vector<double>& w) {
+  w.resize(n);
+  for (int j = 0; j < n; ++j) {
+    if (!(p[j] > 0.0 && p[j] < 1.0)) return false;
+    w[j] = std::log(1.0 / p[j]);
+  }
+  return true;
+}
+
+int osd_decode_batch_impl(const qldpc_osd* osd, const uint8_t* synd, const double* post, const uint8_t* conv,
+                          const uint8_t* bp_corr, const uint8_t* side, uint8_t* out_osd0, uint8_t* out_osdw,
+                          int64_t B, int32_t threads);
 
 }  // namespace
 
@@ -306,9 +327,36 @@ int qldpc_osd_rank(const qldpc_osd* osd, int32_t* rank) {
   return 0;
 }
 
+int qldpc_osd_set_side_probs(qldpc_osd* osd, const double* p0, const double* p1) {
+  if (!osd || !p0 || !p1) return set_err(QLDPC_EINVAL, "NULL argument");
+  std::vector<double> w0, w1;
+  if (!side_weights(p0, osd->n, w0) || !side_weights(p1, osd->n, w1))
+    return set_err(QLDPC_EINVAL, "side probabilities must lie in (0, 1)");
+  osd->ws0.swap(w0);
+  osd->ws1.swap(w1);
+  return 0;
+}
+
 int qldpc_osd_decode_batch(const qldpc_osd* osd, const uint8_t* synd, const double* post, const uint8_t* conv,
                            const uint8_t* bp_corr, uint8_t* out_osd0, uint8_t* out_osdw, int64_t B,
                            int32_t threads) {
+  return osd_decode_batch_impl(osd, synd, post, conv, bp_corr, nullptr, out_osd0, out_osdw, B, threads);
+}
+
+int qldpc_osd_decode_batch_side(const qldpc_osd* osd, const uint8_t* synd, const double* post, const uint8_t* conv,
+                                const uint8_t* bp_corr, const uint8_t* side, uint8_t* out_osd0, uint8_t* out_osdw,
+                                int64_t B, int32_t threads) {
+  if (!osd || (B > 0 && !side)) return set_err(QLDPC_EINVAL, "NULL argument");
+  if (osd->ws0.empty()) return set_err(QLDPC_EINVAL, "side decode without side tables (qldpc_osd_set_side_probs)");
+  return osd_decode_batch_impl(osd, synd, post, conv, bp_corr, side, out_osd0, out_osdw, B, threads);
+}
+
+}  // extern "C"
+
+namespace {
+int osd_decode_batch_impl(const qldpc_osd* osd, const uint8_t* synd, const double* post, const uint8_t* conv,
+                          const uint8_t* bp_corr, const uint8_t* side, uint8_t* out_osd0, uint8_t* out_osdw,
+                          int64_t B, int32_t threads) {
   if (!osd || (B > 0 && (!synd || !post || !out_osdw))) return set_err(QLDPC_EINVAL, "NULL argument");
   if (conv && !bp_corr) return set_err(QLDPC_EINVAL, "conv needs bp_corr");
   if (B <= 0) return 0;
@@ -333,9 +381,13 @@ int qldpc_osd_decode_batch(const qldpc_osd* osd, const uint8_t* synd, const doub
   auto run = [&](int t) {
     Work K;
     std::vector<uint8_t> o0(n);
+    std::vector<double> sw(side ? n : 0);
     for (size_t a = t; a < todo.size(); a += T) {
       const int64_t b = todo[a];
-      osd_one(*osd, K, synd + b * m, post + b * n, out_osd0 ? out_osd0 + b * n : o0.data(), out_osdw + b * n);
+      if (side)
+        for (int j = 0; j < n; ++j) sw[j] = (side[b * n + j] & 1u) ? osd->ws1[j] : osd->ws0[j];
+      osd_one(*osd, K, synd + b * m, post + b * n, out_osd0 ? out_osd0 + b * n : o0.data(), out_osdw + b * n,
+              side ? sw.data() : nullptr);
     }
   };
   if (T == 1) {
@@ -347,8 +399,7 @@ int qldpc_osd_decode_batch(const qldpc_osd* osd, const uint8_t* synd, const doub
   }
   return 0;
 }
-
-}  // extern "C"
+}  // namespace
 
 // ===========================================================================
 // GPU OSD: one workgroup per syndrome, persistent over the batch (uniform priors: popcount
@@ -412,6 +463,9 @@ struct OsdGpuArgs {
   int pbuf_off;  // register-row mode: LDS byte offset of the pivot-row broadcast buffer
   int win;  // always 0 (see the early-out behind the register-row pivot loop)
   long long ws_words, iws_ints;
+  // side decodes (the SIDE instantiations alone read these; softw is then w_0, never null)
+  const double* softw1;  // [n] w_1
+  const uint8_t* side;   // [B][n], bit 0 selects the weight table per column
 };
 
 // dst[q*m] ^= src[q*m] for q < W: no aliasing between the two rows, so the loads can run ahead
@@ -468,7 +522,11 @@ __device__ inline u64 ord_key(double x) {
 // q.. in an LDS buffer and the rows that have the pivot bit xor them in registers, so a row
 // update costs no LDS writes (the word-major LDS / HBM image paid one 8-byte store per word and
 // row).  The reduced rows go to the HBM slice afterwards for the candidate bit-vectors.
-template <int LB, int WR = 0>
+//
+// SIDE: the side decode (qldpc_osd_gpu_decode_side), a compile-time switch so that the plain
+// instantiations are the code they were.  Step 6' alone differs: always taken, and its weights are
+// the syndrome's own, w_{side[b][j] & 1}[j], staged once per syndrome in the workgroup's slice.
+template <int LB, int WR = 0, bool SIDE = false>
 __global__ void __launch_bounds__(LB) osd_gpu_kernel(OsdGpuArgs A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, TB = blockDim.x;
@@ -874,7 +932,7 @@ __global__ void __launch_bounds__(LB) osd_gpu_kernel(OsdGpuArgs A) {
       }
       return 0;
     };
-    if (A.softw) {
+    if (SIDE || A.softw) {
       // 6'. non-uniform priors (qldpc_osd_gpu_create with channel_probs that differ): the soft weight
       // sum_{j: x_j = 1} log(1 / p_j), added in ascending COLUMN order as the host stage's
       // soft_weight (and ldpc) adds it, so the candidates go to column space first: Xc[j] = X[j]
@@ -884,6 +942,15 @@ __global__ void __launch_bounds__(LB) osd_gpu_kernel(OsdGpuArgs A) {
       // the first strictly lightest candidate, as the uniform path.
       int32_t* colpiv = gpos + n;            // [n]
       u64* Xc = X + (size_t)(1 + nh) * RW;   // [(1 + nh)][W]
+      const double* wt = A.softw;
+      if constexpr (SIDE) {
+        // the syndrome's weights, all n rewritten per syndrome (nothing of the last one's is read),
+        // visible to the candidate walk through the barriers below
+        double* wsel = reinterpret_cast<double*>(Xc + (size_t)(1 + nh) * W);  // [n]
+        const uint8_t* sd = A.side + b * (long long)n;
+        for (int j = tid; j < n; j += TB) wsel[j] = (sd[j] & 1u) ? A.softw1[j] : A.softw[j];
+        wt = wsel;
+      }
       for (int j = tid; j < n; j += TB) colpiv[j] = -1;
       __syncthreads();
       for (int i = tid; i < r; i += TB) colpiv[sidxr[pivpos[i]]] = i;
@@ -924,7 +991,7 @@ __global__ void __launch_bounds__(LB) osd_gpu_kernel(OsdGpuArgs A) {
               if ((hc >> 6) == q) v |= 1ull << (hc & 63);
             }
           }
-          for (; v; v &= v - 1) sw += A.softw[q * 64 + __ffsll((long long)v) - 1];
+          for (; v; v &= v - 1) sw += wt[q * 64 + __ffsll((long long)v) - 1];
         }
         if (sw < bw) {  // c ascends per thread: the first of equal weights stays
           bw = sw;
@@ -1025,6 +1092,7 @@ struct qldpc_osd_gpu {
   size_t lds = 0;
   long long ws_words = 0, iws_ints = 0;
   qldpc_rt::DevBuf rp, ci, ws, iws, softw;  // softw: [n] log(1 / p_j) when the priors are not uniform
+  qldpc_rt::DevBuf sw0, sw1;  // side tables [n] each (qldpc_osd_gpu_set_side_probs), else empty
 };
 
 namespace {
@@ -1089,17 +1157,21 @@ namespace {
 constexpr int kOsdWR[] = {2, 4, 8, 12, 16, 20, 25};
 inline int osd_rr_threads(int wr) { return wr <= 16 ? 1024 : 768; }
 using OsdKern = void (*)(OsdGpuArgs);
-OsdKern osd_rr_kernel(int wr) {
+template <bool SIDE>
+OsdKern osd_rr_kernel_of(int wr) {
   switch (wr) {
-    case 2: return &osd_gpu_kernel<1024, 2>;
-    case 4: return &osd_gpu_kernel<1024, 4>;
-    case 8: return &osd_gpu_kernel<1024, 8>;
-    case 12: return &osd_gpu_kernel<1024, 12>;
-    case 16: return &osd_gpu_kernel<1024, 16>;
-    case 20: return &osd_gpu_kernel<768, 20>;
-    case 25: return &osd_gpu_kernel<768, 25>;
+    case 2: return &osd_gpu_kernel<1024, 2, SIDE>;
+    case 4: return &osd_gpu_kernel<1024, 4, SIDE>;
+    case 8: return &osd_gpu_kernel<1024, 8, SIDE>;
+    case 12: return &osd_gpu_kernel<1024, 12, SIDE>;
+    case 16: return &osd_gpu_kernel<1024, 16, SIDE>;
+    case 20: return &osd_gpu_kernel<768, 20, SIDE>;
+    case 25: return &osd_gpu_kernel<768, 25, SIDE>;
     default: return nullptr;
   }
+}
+OsdKern osd_rr_kernel(int wr, bool side = false) {
+  return side ? osd_rr_kernel_of<true>(wr) : osd_rr_kernel_of<false>(wr);
 }
 }  // namespace
 
@@ -1129,6 +1201,8 @@ bool osd_host_matches(const qldpc_osd* o, const qldpc_graph* g) {
 bool osd_gpu_matches(const qldpc_osd_gpu* o, const qldpc_graph* g) {
   return o && g && o->host.m == g->m && o->host.n == g->n && o->host.col_rows == g->col_rows;
 }
+
+bool osd_gpu_has_side(const qldpc_osd_gpu* o) { return o && o->sw0.p; }
 }  // namespace qldpc_rt
 
 extern "C" {
@@ -1201,6 +1275,7 @@ int qldpc_rt::osd_gpu_from_host(const qldpc_graph* g, const qldpc_osd* O, qldpc_
   G->iws_ints = 2ll * rank + 4ll * n;
   auto fail = [&](int code) {
     G->rp.release(); G->ci.release(); G->ws.release(); G->iws.release(); G->softw.release();
+    G->sw0.release(); G->sw1.release();
     delete G;
     return code;
   };
@@ -1247,6 +1322,7 @@ int qldpc_osd_gpu_geometry(const qldpc_osd_gpu* osd, int32_t* row_words, int32_t
 int qldpc_osd_gpu_destroy(qldpc_osd_gpu* osd) {
   if (!osd) return 0;
   osd->rp.release(); osd->ci.release(); osd->ws.release(); osd->iws.release(); osd->softw.release();
+  osd->sw0.release(); osd->sw1.release();
   delete osd;
   return 0;
 }
@@ -1268,6 +1344,13 @@ namespace qldpc_rt {
 int osd_gpu_decode_slots(qldpc_osd_gpu* osd, const uint8_t* d_synd, const double* d_post, const uint8_t* d_conv,
                          const long long* d_shot, const uint8_t* d_bp_corr, uint8_t* d_out0, uint8_t* d_outw,
                          int64_t B, void* stream) {
+  return osd_gpu_decode_any(osd, d_synd, d_post, d_conv, d_shot, d_bp_corr, nullptr, d_out0, d_outw, B, stream);
+}
+
+// d_side != null: the side decode (the SIDE kernels, weights from the handle's side tables)
+int osd_gpu_decode_any(qldpc_osd_gpu* osd, const uint8_t* d_synd, const double* d_post, const uint8_t* d_conv,
+                       const long long* d_shot, const uint8_t* d_bp_corr, const uint8_t* d_side, uint8_t* d_out0,
+                       uint8_t* d_outw, int64_t B, void* stream) {
   if (!osd || (B > 0 && (!d_synd || !d_post || !d_outw))) return set_err(QLDPC_EINVAL, "NULL argument");
   if (d_conv && !d_bp_corr) return set_err(QLDPC_EINVAL, "conv needs bp_corr");
   if (B <= 0) return 0;
@@ -1277,6 +1360,13 @@ int osd_gpu_decode_slots(qldpc_osd_gpu* osd, const uint8_t* d_synd, const double
   a.ci = static_cast<const int32_t*>(osd->ci.p);
   a.synd = d_synd; a.post = d_post; a.conv = d_conv; a.shot = d_shot; a.bp_corr = d_bp_corr; a.out0 = d_out0;
   a.softw = osd->host.uniform ? nullptr : static_cast<const double*>(osd->softw.p);
+  a.softw1 = nullptr;
+  a.side = d_side;
+  if (d_side) {
+    if (!osd->sw0.p) return set_err(QLDPC_EINVAL, "side decode without side tables (qldpc_osd_gpu_set_side_probs)");
+    a.softw = static_cast<const double*>(osd->sw0.p);
+    a.softw1 = static_cast<const double*>(osd->sw1.p);
+  }
   a.outw = d_outw;
   a.ws = static_cast<u64*>(osd->ws.p);
   a.iws = static_cast<int32_t*>(osd->iws.p);
@@ -1287,7 +1377,16 @@ int osd_gpu_decode_slots(qldpc_osd_gpu* osd, const uint8_t* d_synd, const double
   a.win = 0;
   a.ws_words = osd->ws_words; a.iws_ints = osd->iws_ints;
   const int grid = (int)std::min<long long>(B, osd->grid);
-  if (osd->wr)
+  if (d_side) {
+    if (osd->wr)
+      hipLaunchKernelGGL(osd_rr_kernel(osd->wr, true), dim3(grid), dim3(osd->rr_tb), osd->lds, (hipStream_t)stream, a);
+    else if (osd->m_lds)
+      hipLaunchKernelGGL((osd_gpu_kernel<kOsdThreadsLds, 0, true>), dim3(grid), dim3(kOsdThreadsLds), osd->lds,
+                         (hipStream_t)stream, a);
+    else
+      hipLaunchKernelGGL((osd_gpu_kernel<kOsdThreads, 0, true>), dim3(grid), dim3(kOsdThreads), osd->lds,
+                         (hipStream_t)stream, a);
+  } else if (osd->wr)
     hipLaunchKernelGGL(osd_rr_kernel(osd->wr), dim3(grid), dim3(osd->rr_tb), osd->lds, (hipStream_t)stream, a);
   else if (osd->m_lds)
     hipLaunchKernelGGL(osd_gpu_kernel<kOsdThreadsLds>, dim3(grid), dim3(kOsdThreadsLds), osd->lds, (hipStream_t)stream, a);
@@ -1302,6 +1401,38 @@ extern "C" {
 int qldpc_osd_gpu_decode(qldpc_osd_gpu* osd, const uint8_t* d_synd, const double* d_post, const uint8_t* d_conv,
                          const uint8_t* d_bp_corr, uint8_t* d_out0, uint8_t* d_outw, int64_t B, void* stream) {
   return qldpc_rt::osd_gpu_decode_slots(osd, d_synd, d_post, d_conv, nullptr, d_bp_corr, d_out0, d_outw, B, stream);
+}
+
+// Side tables of the GPU handle: the same law and checks as qldpc_osd_set_side_probs.  The workspace
+// grows to the soft path's (Xc, which a uniform handle does not have) plus the staged weights [n]
+// per workgroup; the grid, the LDS layout and so qldpc_osd_gpu_geometry stay as they are.
+int qldpc_osd_gpu_set_side_probs(qldpc_osd_gpu* osd, const double* p0, const double* p1) {
+  if (!osd || !p0 || !p1) return set_err(QLDPC_EINVAL, "NULL argument");
+  int rc = qldpc_osd_set_side_probs(&osd->host, p0, p1);
+  if (rc) return rc;
+  const int n = osd->host.n;
+  QLDPC_HIP(hipSetDevice(osd->device));
+  QLDPC_HIP(hipDeviceSynchronize());  // no decode in flight on the workspace that is replaced
+  const long long words = (long long)osd->W * osd->host.m + (long long)(1 + osd->nh) * osd->RW +
+                          (long long)(1 + osd->nh) * osd->W + n;
+  if (words > osd->ws_words) {
+    osd->ws.release();
+    osd->ws_words = words;
+    if ((rc = osd->ws.alloc((size_t)osd->grid * osd->ws_words * 8))) return rc;
+  }
+  if (!osd->sw0.p && ((rc = osd->sw0.alloc((size_t)n * 8)) || (rc = osd->sw1.alloc((size_t)n * 8)))) return rc;
+  QLDPC_HIP(hipMemcpy(osd->sw0.p, osd->host.ws0.data(), (size_t)n * 8, hipMemcpyHostToDevice));
+  QLDPC_HIP(hipMemcpy(osd->sw1.p, osd->host.ws1.data(), (size_t)n * 8, hipMemcpyHostToDevice));
+  return 0;
+}
+
+int qldpc_osd_gpu_decode_side(qldpc_osd_gpu* osd, const uint8_t* d_synd, const double* d_post, const uint8_t* d_conv,
+                              const uint8_t* d_bp_corr, const uint8_t* d_side, uint8_t* d_out0, uint8_t* d_outw,
+                              int64_t B, void* stream) {
+  if (!osd || (B > 0 && !d_side)) return set_err(QLDPC_EINVAL, "NULL argument");
+  if (!osd->sw0.p) return set_err(QLDPC_EINVAL, "side decode without side tables (qldpc_osd_gpu_set_side_probs)");
+  return qldpc_rt::osd_gpu_decode_any(osd, d_synd, d_post, d_conv, nullptr, d_bp_corr, d_side, d_out0, d_outw, B,
+                                      stream);
 }
 
 }  // extern "C"

@@ -1681,6 +1681,29 @@ int qldpc_bp_decode_batch_side(qldpc_bp* bp, const uint8_t* d_synd, const uint8_
   return serial_decode_launch(bp, d_synd, d_corr, d_iters, d_conv, nullptr, B, (hipStream_t)stream, d_side);
 }
 
+// true when qldpc_bp_decode_batch_side_soft serves the decoder: an engine-8 handle created with
+// soft = 1, or an engine-7 handle without a chain (a chain's best solution has no single posterior)
+static bool side_soft_capable(const qldpc_bp* bp) {
+  return (bp->route.engine == 8 && bp->sr_soft) || (bp->route.engine == 7 && bp->rl_legs == 0);
+}
+
+// The soft output of a side decode (d_side = NULL: of the plain decode): corr / iters / conv are
+// qldpc_bp_decode_batch[_side]'s, d_post the posteriors after the last iteration.
+int qldpc_bp_decode_batch_side_soft(qldpc_bp* bp, const uint8_t* d_synd, const uint8_t* d_side, uint8_t* d_corr,
+                                    int32_t* d_iters, uint8_t* d_conv, double* d_post, int64_t B, void* stream) {
+  if (!bp || (B > 0 && (!d_synd || !d_corr || !d_post))) return set_err(QLDPC_EINVAL, "NULL argument");
+  if (!side_soft_capable(bp))
+    return set_err(QLDPC_ENOTSUP,
+                   "soft side output needs a serial decoder created with soft = 1 or a Relay-BP decoder with num_legs = 0");
+  if (d_side && !bp->side_set) return set_err(QLDPC_EINVAL, "no side priors set (qldpc_bp_set_side_probs)");
+  if (B <= 0) return B < 0 ? set_err(QLDPC_EINVAL, "B < 0") : 0;
+  QLDPC_HIP(hipSetDevice(bp->g->device));
+  if (bp->g->n == 0) d_side = nullptr;  // no variable selects anything
+  if (bp->route.engine == 7)
+    return relay_decode_launch(bp, d_synd, d_corr, d_iters, d_conv, B, (hipStream_t)stream, d_side, d_post);
+  return serial_decode_launch(bp, d_synd, d_corr, d_iters, d_conv, d_post, B, (hipStream_t)stream, d_side);
+}
+
 int qldpc_bp_degree3_slots(const qldpc_bp* bp, int32_t* d3k) {
   if (!bp || !d3k) return set_err(QLDPC_EINVAL, "NULL argument");
   *d3k = bp->route.engine == 3 ? bp->route.d3k : 0;
@@ -2035,6 +2058,10 @@ int qldpc_mc_set_channel_update(qldpc_mc* mc, int32_t direction) {
   if (!second->side_set)
     return set_err(QLDPC_EINVAL, "channel update needs side priors on the second sector's decoder "
                                  "(qldpc_bp_set_side_probs)");
+  // with a BP+OSD stage (qldpc_mc_set_staged_osd) the second sector's OSD is a side decode too
+  if (qldpc_osd_gpu* so = mc->sosd[direction == 1 ? 1 : 0]; so && !osd_gpu_has_side(so))
+    return set_err(QLDPC_EINVAL, "channel update needs side tables on the second sector's OSD handle "
+                                 "(qldpc_osd_gpu_set_side_probs)");
   if (!mc->s_side.p) {
     QLDPC_HIP(hipSetDevice(second->g->device));
     if (int rc = mc->s_side.alloc(std::max<size_t>(1, (size_t)second->g->n * (size_t)mc->sbatch))) return rc;
@@ -2059,6 +2086,51 @@ int qldpc_mc_set_osd(qldpc_mc* mc, qldpc_osd_gpu* osd_x, qldpc_osd_gpu* osd_z) {
   mc->osd[0] = osd_x;
   mc->osd[1] = osd_z;
   mc->c_cap = 0;  // the next launch (re)allocates the capture buffers of every enabled sector
+  return 0;
+}
+
+// BP+OSD in the staged shot loop: per sector, BP with soft output (qldpc_bp_decode_batch_side_soft),
+// then the GPU OSD over the batch with BP's conv flags; outw is the sector's correction.
+int qldpc_mc_set_staged_osd(qldpc_mc* mc, qldpc_osd_gpu* osd_x, qldpc_osd_gpu* osd_z) {
+  if (!mc) return set_err(QLDPC_EINVAL, "NULL mc");
+  if (!mc->staged) return set_err(QLDPC_ENOTSUP, "the staged BP+OSD stage needs a staged handle (qldpc_mc_create_staged)");
+  qldpc_osd_gpu* o[2] = {osd_x, osd_z};
+  for (int q = 0; q < 2; ++q) {
+    if (!o[q]) continue;
+    if (!mc->dec[q] || !osd_gpu_matches(o[q], mc->dec[q]->g))
+      return set_err(QLDPC_EINVAL, q == 0 ? "X-sector OSD handle was built on a different graph than dec_x"
+                                          : "Z-sector OSD handle was built on a different graph than dec_z");
+    if (!side_soft_capable(mc->dec[q]))
+      return set_err(QLDPC_ENOTSUP, "the staged BP+OSD stage needs soft output of the sector decoder: a serial "
+                                    "decoder created with soft = 1 or a Relay-BP decoder with num_legs = 0");
+  }
+  if (mc->chan_dir)
+    if (qldpc_osd_gpu* so = o[mc->chan_dir == 1 ? 1 : 0]; so && !osd_gpu_has_side(so))
+      return set_err(QLDPC_EINVAL, "channel update needs side tables on the second sector's OSD handle "
+                                   "(qldpc_osd_gpu_set_side_probs)");
+  if (osd_x || osd_z) {
+    const qldpc_bp* d0 = mc->dec[0] ? mc->dec[0] : mc->dec[1];
+    const long long n = std::max(1, d0->g->n);
+    // the posterior buffer [batch][n] doubles within QLDPC_OSD_CAPTURE_MB: the batch only ever shrinks
+    // (every per-batch buffer of the handle was cut for a batch at least this large), and shot keying
+    // does not depend on it
+    // (read as a real number here: a fraction of a megabyte bounds the batch of a small code)
+    const char* e = std::getenv("QLDPC_OSD_CAPTURE_MB");
+    const double mb = e && std::atof(e) > 0.0 ? std::min(std::atof(e), 1048576.0) : 2048.0;
+    const long long fit = std::max<long long>(64, (long long)(mb * 1048576.0) / (n * 8) / 64 * 64);
+    const long long B = std::min(mc->sbatch, fit);
+    QLDPC_HIP(hipSetDevice(d0->g->device));
+    if (mc->s_post.bytes < (size_t)B * n * 8) {
+      QLDPC_HIP(hipDeviceSynchronize());
+      mc->s_post.release();
+      mc->s_bpcorr.release();
+      if (int rc = mc->s_post.alloc((size_t)B * n * 8)) return rc;
+      if (int rc = mc->s_bpcorr.alloc((size_t)B * n)) return rc;
+    }
+    mc->sbatch = B;
+  }
+  mc->sosd[0] = osd_x;
+  mc->sosd[1] = osd_z;
   return 0;
 }
 

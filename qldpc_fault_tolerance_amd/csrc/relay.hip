@@ -94,6 +94,7 @@ struct RelayArgs {
   long long B;
   double alpha;
   int m, n, E, pre_iter, leg_iter, num_legs, stop_nconv;
+  double* post;          // [B][n] or NULL: M after the last iteration (qldpc_bp_decode_batch_side_soft, num_legs = 0)
 };
 
 // LDS: [b2c, c2b: 2E x T when in LDS][M: n x T][wsum: 8][flag: 2 x 4][dec: n][best: n][syn: m]
@@ -281,6 +282,8 @@ __global__ void __launch_bounds__(kRelayMaxThreads) relay_kernel(RelayArgs A) {
         A.corr[b * n + j] = (nsol > 0 ? best[j] : dec[j]) & 1;
       else
         A.corr[b * n + j] = nsol > 0 ? best[j] : dec[j];
+      // soft output: M is the LDS word the last variable pass left (no leg follows: num_legs = 0)
+      if (A.post) A.post[b * n + j] = (double)M[j];
     }
     if (tid == 0) {
       if (A.iters) A.iters[b] = total;
@@ -611,9 +614,10 @@ static void relay_launch(const RelayArgs& a, dim3 grid, dim3 block, size_t lds, 
 }
 
 int relay_decode_launch(const qldpc_bp* bp, const uint8_t* synd, uint8_t* corr, int32_t* iters, uint8_t* conv,
-                        int64_t B, hipStream_t stream, const uint8_t* side) {
+                        int64_t B, hipStream_t stream, const uint8_t* side, double* post) {
   const qldpc_graph* g = bp->g;
   RelayArgs a;
+  a.post = post;
   a.rp = static_cast<const int32_t*>(bp->ps_rp.p);
   a.ci = static_cast<const int32_t*>(bp->ps_ci.p);
   a.cp = static_cast<const int32_t*>(bp->ps_cp.p);

@@ -136,6 +136,10 @@ struct qldpc_mc {
   // sector's corrections as the side bytes of the second sector's decode
   int chan_dir = 0;
   qldpc_rt::DevBuf s_side;
+  // qldpc_mc_set_staged_osd: GPU OSD per sector behind the staged loop's soft BP; s_post [sbatch][n]
+  // doubles and s_bpcorr [sbatch][n] hold BP's posteriors and corrections for the OSD launch
+  qldpc_osd_gpu* sosd[2] = {nullptr, nullptr};
+  qldpc_rt::DevBuf s_post, s_bpcorr;
 };
 
 
@@ -159,7 +163,7 @@ int relay_upload_gammas(qldpc_bp* bp);
 int relay_upload_side(qldpc_bp* bp, const double* p0, const double* p1);
 // side non-NULL: the side decode (uint8 [B][n], bit 0), on the handle's side tables
 int relay_decode_launch(const qldpc_bp* bp, const uint8_t* synd, uint8_t* corr, int32_t* iters, uint8_t* conv,
-                        int64_t B, hipStream_t stream, const uint8_t* side = nullptr);
+                        int64_t B, hipStream_t stream, const uint8_t* side = nullptr, double* post = nullptr);
 
 // engine 8 (serial.hip)
 int serial_check_params(int64_t n, int32_t max_iter, int32_t precision);
@@ -172,6 +176,8 @@ int serial_decode_launch(const qldpc_bp* bp, const uint8_t* synd, uint8_t* corr,
 
 // GPU OSD handle built on this graph? (osd.hip; qldpc_phenl_set_final_osd checks it)
 bool osd_gpu_matches(const qldpc_osd_gpu* o, const qldpc_graph* g);
+// side tables set on the GPU OSD handle? (qldpc_osd_gpu_set_side_probs)
+bool osd_gpu_has_side(const qldpc_osd_gpu* o);
 // host OSD stage built on this graph? (osd.hip; qldpc_circ_set_final_osd checks it)
 bool osd_host_matches(const qldpc_osd* o, const qldpc_graph* g);
 // GPU OSD handle from a host OSD stage on graph g: same method / order / rank / soft weights (osd.hip)
@@ -190,6 +196,10 @@ int osd_gpu_bposd_stage(qldpc_osd_gpu* osd, const uint8_t* synd, const double* p
 int osd_gpu_decode_slots(qldpc_osd_gpu* osd, const uint8_t* d_synd, const double* d_post, const uint8_t* d_conv,
                          const long long* d_shot, const uint8_t* d_bp_corr, uint8_t* d_out0, uint8_t* d_outw,
                          int64_t B, void* stream);
+// the same with side bytes (d_side != null: qldpc_osd_gpu_decode_side's kernels and tables)
+int osd_gpu_decode_any(qldpc_osd_gpu* osd, const uint8_t* d_synd, const double* d_post, const uint8_t* d_conv,
+                       const long long* d_shot, const uint8_t* d_bp_corr, const uint8_t* d_side, uint8_t* d_out0,
+                       uint8_t* d_outw, int64_t B, void* stream);
 
 // engine 6 (bp_hbm.hip)
 int hbm_prepare(qldpc_bp* bp);

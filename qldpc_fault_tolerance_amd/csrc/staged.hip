@@ -581,7 +581,9 @@ void staged_mc_release(qldpc_mc* mc) {
   for (int q = 0; q < 2; ++q) {
     mc->s_rp[q].release(); mc->s_ci[q].release(); mc->s_cur[q].release(); mc->s_failw[q].release();
   }
-  for (DevBuf* d : {&mc->s_D, &mc->s_det, &mc->s_corr, &mc->s_iters, &mc->s_conv, &mc->s_side}) d->release();
+  for (DevBuf* d : {&mc->s_D, &mc->s_det, &mc->s_corr, &mc->s_iters, &mc->s_conv, &mc->s_side, &mc->s_post,
+                    &mc->s_bpcorr})
+    d->release();
 }
 
 int staged_mc_prepare(qldpc_mc* mc, const qldpc_graph* logical_x, const qldpc_graph* logical_z) {
@@ -694,14 +696,29 @@ int staged_mc_launch(qldpc_mc* mc, double px, double py, double pz, uint64_t see
                          static_cast<const unsigned long long*>(mc->s_D.p), static_cast<uint8_t*>(mc->s_det.p),
                          nullptr, 0, 0, c0, m, W, B);
       QLDPC_HIP(hipGetLastError());
-      int rc = dir && oq == 1
-                   ? qldpc_bp_decode_batch_side(mc->dec[q], static_cast<const uint8_t*>(mc->s_det.p),
-                                                static_cast<const uint8_t*>(mc->s_side.p), corr,
-                                                static_cast<int32_t*>(mc->s_iters.p),
-                                                static_cast<uint8_t*>(mc->s_conv.p), B, st)
-                   : qldpc_bp_decode_batch(mc->dec[q], static_cast<const uint8_t*>(mc->s_det.p), corr,
-                                           static_cast<int32_t*>(mc->s_iters.p),
-                                           static_cast<uint8_t*>(mc->s_conv.p), B, st);
+      const uint8_t* side = dir && oq == 1 ? static_cast<const uint8_t*>(mc->s_side.p) : nullptr;
+      int rc;
+      if (mc->sosd[q]) {
+        // BP+OSD (qldpc_mc_set_staged_osd): soft BP into s_bpcorr / s_post, then the GPU OSD over the
+        // batch with BP's conv flags (converged decodes keep BP's correction); outw is the sector's
+        // correction.  The iteration / non-converged counters below stay BP's.
+        auto* bpc = static_cast<uint8_t*>(mc->s_bpcorr.p);
+        rc = qldpc_bp_decode_batch_side_soft(mc->dec[q], static_cast<const uint8_t*>(mc->s_det.p), side, bpc,
+                                             static_cast<int32_t*>(mc->s_iters.p),
+                                             static_cast<uint8_t*>(mc->s_conv.p), static_cast<double*>(mc->s_post.p),
+                                             B, st);
+        if (rc) return rc;
+        rc = osd_gpu_decode_any(mc->sosd[q], static_cast<const uint8_t*>(mc->s_det.p),
+                                static_cast<const double*>(mc->s_post.p), static_cast<const uint8_t*>(mc->s_conv.p),
+                                nullptr, bpc, side, nullptr, corr, B, st);
+      } else {
+        rc = side ? qldpc_bp_decode_batch_side(mc->dec[q], static_cast<const uint8_t*>(mc->s_det.p), side, corr,
+                                               static_cast<int32_t*>(mc->s_iters.p),
+                                               static_cast<uint8_t*>(mc->s_conv.p), B, st)
+                  : qldpc_bp_decode_batch(mc->dec[q], static_cast<const uint8_t*>(mc->s_det.p), corr,
+                                          static_cast<int32_t*>(mc->s_iters.p),
+                                          static_cast<uint8_t*>(mc->s_conv.p), B, st);
+      }
       if (rc) return rc;
       hipLaunchKernelGGL(ph_iters, dim3((unsigned)((B + kTile - 1) / kTile)), dim3(kTile), 0, st,
                          static_cast<const int32_t*>(mc->s_iters.p), static_cast<const uint8_t*>(mc->s_conv.p), cnt, q,

@@ -244,38 +244,64 @@ class BPOSD_Decoder:
     (``qldpc_osd_decode_batch``).
     ``decode`` returns ``osdw_decoding`` like the reference; ``osd0_decoding``,
     ``bp_decoding``, ``converge``, ``iter`` and ``log_prob_ratios`` are kept.
+
+    ``side_probs=(p0, p1)`` makes the decoder side-capable, as on :class:`BPDecoder`:
+    ``decode(synd, side)`` runs BP and OSD under the per-variable priors ``side`` selects (the laws in
+    include/qldpc_hip.h).  Min-sum only.  BP then runs on engine 7 (``pre_iter = max_iter``, no memory,
+    no legs: plain min-sum bit for bit, with soft output through ``qldpc_bp_decode_batch_side_soft``),
+    or on engine 8 for ``schedule="serial"``; the OSD stages carry the same tables.
     """
 
     def __init__(self, h, channel_probs, max_iter, bp_method, ms_scaling_factor, osd_method, osd_order,
                  precision: int = 64, device: int | None = None, osd_threads: int = 0, use_gpu_osd: bool = True,
-                 schedule: str = "parallel"):
-        from .engine import DeviceBP, DeviceOSD, HostOSD
+                 schedule: str = "parallel", side_probs=None):
+        from .engine import DeviceBP, DeviceOSD, HostOSD, RelayParams, bp_method_code
 
         self.h = h
         self.schedule = schedule
+        self.side_probs = side_probs
+        self.max_iter = max_iter
+        self.bp_method = bp_method
+        self.ms_scaling_factor = ms_scaling_factor
         H = h if isinstance(h, CSR) else CSR.from_dense(h)
         self.num_checks, self.num_qubits = H.m, H.n
         self.channel_probs = np.asarray(channel_probs, dtype=np.float64)
         self.osd_method, self.osd_order = osd_method, osd_order
+        relay = None
+        if side_probs is not None:
+            if bp_method_code(bp_method) != 1:
+                raise ValueError("side_probs need bp_method 'minimum_sum': product_sum has no side decode")
+            if schedule == "parallel":
+                relay = RelayParams(pre_iter=_int_max_iter(max_iter, H.n), pre_gamma=0.0, num_legs=0)
         self.decoder = DeviceBP(H, self.channel_probs, max_iter=_int_max_iter(max_iter, H.n), bp_method=bp_method,
-                                ms_scaling_factor=ms_scaling_factor, precision=precision, device=device, soft=True,
-                                schedule=schedule)
+                                ms_scaling_factor=ms_scaling_factor, precision=precision, device=device,
+                                soft=relay is None, schedule=schedule, relay=relay)
         self.osd = HostOSD(H, self.channel_probs, osd_method=osd_method, osd_order=osd_order)
         # OSD on the GPU (uniform priors: popcount weights; non-uniform: soft weights); the host stage
         # stays for use_gpu_osd=False and graphs past the GPU kernel's envelope
         self.gpu_osd = (DeviceOSD(self.decoder.graph, self.channel_probs, osd_method, osd_order)
                         if use_gpu_osd and DeviceOSD.supported(H.n, self.channel_probs, osd_method, osd_order)
                         else None)
+        if side_probs is not None:
+            for stage in (self.decoder, self.osd, self.gpu_osd):
+                if stage is not None:
+                    _set_side_probs(stage, side_probs)
         self.osd_threads = osd_threads
         self.iter, self.converge = 0, 0
 
-    def decode_batch(self, synd):
+    def decode_batch(self, synd, side=None):
         """[B, m] syndromes -> osdw corrections [B, n] (int); also sets the batch's
         ``osd0_batch``, ``bp_batch``, ``conv_batch``, ``iters_batch``, ``post_batch`` (the
-        posteriors; a device tensor when the OSD ran on the GPU)."""
+        posteriors; a device tensor when the OSD ran on the GPU).  ``side`` [B, n]: a side decode of
+        both stages (needs ``side_probs``)."""
         s = np.atleast_2d(np.asarray(synd))
+        if side is not None and self.side_probs is None:
+            raise TypeError("a side decode needs a BPOSD_Decoder built with side_probs")
         if self.gpu_osd is not None:
-            ow, o0, corr, iters, conv, post = self.gpu_osd.bposd_batch(self.decoder, s, host_post=False)
+            ow, o0, corr, iters, conv, post = self.gpu_osd.bposd_batch(self.decoder, s, host_post=False, side=side)
+        elif side is not None:
+            corr, iters, conv, post = self.decoder.decode_batch_soft(s, side)
+            o0, ow = self.osd.decode_batch(s, post, conv, corr, threads=self.osd_threads, side=side)
         else:
             corr, iters, conv, post = self.decoder.decode_batch_soft(s)
             o0, ow = self.osd.decode_batch(s, post, conv, corr, threads=self.osd_threads)
@@ -283,8 +309,8 @@ class BPOSD_Decoder:
         self.osd0_batch = o0.astype(np.int64)
         return ow.astype(np.int64)
 
-    def decode(self, synd):
-        ow = self.decode_batch(np.asarray(synd).reshape(1, -1))
+    def decode(self, synd, side=None):
+        ow = self.decode_batch(np.asarray(synd).reshape(1, -1), None if side is None else np.asarray(side).reshape(1, -1))
         self.bp_decoding = self.bp_batch[0]
         self.osd0_decoding = self.osd0_batch[0]
         self.osdw_decoding = ow[0]
@@ -383,10 +409,11 @@ class BPOSD_Decoder_Class(DecoderClass):
         num_qubits, probs = BP_Decoder_Class._probs(p)
         d = self.decoder_default_params
         max_iter = num_qubits / d["max_iter_ratio"]
+        # optional "side_probs": (p0, p1) of a side-capable decoder (the second sector of a channel update)
         return BPOSD_Decoder(h=p["h"], channel_probs=probs, max_iter=max_iter, bp_method=d["bp_method"],
                              ms_scaling_factor=d["ms_scaling_factor"], osd_method=d["osd_method"],
                              osd_order=d["osd_order"], precision=self.precision, device=self.device,
-                             schedule=self.schedule)
+                             schedule=self.schedule, side_probs=p.get("side_probs"))
 
 
 # ------------------------------------------------------------------ space-time

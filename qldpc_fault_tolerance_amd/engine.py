@@ -353,20 +353,29 @@ class DeviceBP(_Handle):
         torch.cuda.synchronize(dev)
         return corr.cpu().numpy().astype(np.int64), iters.cpu().numpy(), conv.cpu().numpy().astype(bool)
 
-    def _decode_soft_device(self, sd, corr, iters, conv, stream):
-        """Soft decode of device syndromes ``sd`` (async); returns the posteriors [B, n] float64."""
+    def _decode_soft_device(self, sd, corr, iters, conv, stream, side=None):
+        """Soft decode of device syndromes ``sd`` (async); returns the posteriors [B, n] float64.
+        ``side``: device side bytes [B, n] of a side decode.  A Relay-BP handle (engine 7) and every
+        side decode go through ``qldpc_bp_decode_batch_side_soft``."""
         torch = _torch()
         post = torch.empty(corr.shape, dtype=torch.float64, device=sd.device)
+        if side is not None or self.relay is not None:
+            _native.check(_native.lib().qldpc_bp_decode_batch_side_soft(
+                self.handle, _ptr(sd), _ptr(side), _ptr(corr), _ptr(iters), _ptr(conv), _ptr(post), sd.shape[0],
+                stream), "qldpc_bp_decode_batch_side_soft")
+            return post
         _native.check(_native.lib().qldpc_bp_decode_batch_soft(
             self.handle, _ptr(sd), _ptr(corr), _ptr(iters), _ptr(conv), _ptr(post), sd.shape[0], stream),
             "qldpc_bp_decode_batch_soft")
         return post
 
-    def decode_batch_soft(self, synd):
+    def decode_batch_soft(self, synd, side=None):
         """Like :meth:`decode_batch` plus the final posteriors ``post`` [B, n] float64
-        (ldpc's ``log_prob_ratios``); needs ``soft=True``."""
+        (ldpc's ``log_prob_ratios``); needs ``soft=True``, or a Relay-BP handle without legs
+        (``num_legs = 0``).  ``side`` [B, n]: a side decode (engines 7 and 8)."""
         torch, dev, sd, corr, iters, conv = _decode_buffers(self.graph, synd)
-        post = self._decode_soft_device(sd, corr, iters, conv, _stream_handle(torch, dev))
+        sb = None if side is None else torch.from_numpy(_side_bytes(side, sd.shape[0], self.graph.n)).to(dev)
+        post = self._decode_soft_device(sd, corr, iters, conv, _stream_handle(torch, dev), side=sb)
         torch.cuda.synchronize(dev)
         return (corr.cpu().numpy().astype(np.int64), iters.cpu().numpy(), conv.cpu().numpy().astype(bool),
                 post.cpu().numpy())
@@ -408,8 +417,17 @@ class HostOSD(_Handle):
                      self.osd_method, self.osd_order)
         self.rank, = self._ints("qldpc_osd_rank", "qldpc_osd_rank", 1)
 
-    def decode_batch(self, synd, post, conv=None, bp_corr=None, threads: int = 0):
-        """(osd0 [B, n], osdw [B, n]) uint8; converged rows (``conv``) copy ``bp_corr``."""
+    def set_side_probs(self, p0, p1):
+        """Side tables (``qldpc_osd_set_side_probs``): a side decode weighs column j of syndrome b with
+        log(1 / p_s[j]), s = ``side[b, j] & 1``.  A scalar broadcasts to ``n``."""
+        a, b = _channel_probs(p0, self.n, check_length=False), _channel_probs(p1, self.n, check_length=False)
+        _native.check(_native.lib().qldpc_osd_set_side_probs(self.handle, _np_ptr(a), _np_ptr(b)),
+                      "qldpc_osd_set_side_probs")
+        self.side_probs = (a, b)
+
+    def decode_batch(self, synd, post, conv=None, bp_corr=None, threads: int = 0, side=None):
+        """(osd0 [B, n], osdw [B, n]) uint8; converged rows (``conv``) copy ``bp_corr``.  ``side``
+        [B, n]: a side decode on the handle's side tables (:meth:`set_side_probs`)."""
         s = _syndromes(synd, self.m)
         B = s.shape[0]
         pst = np.ascontiguousarray(np.asarray(post, dtype=np.float64).reshape(B, self.n))
@@ -419,6 +437,12 @@ class HostOSD(_Handle):
         o0 = np.zeros((B, self.n), np.uint8)
         ow = np.zeros((B, self.n), np.uint8)
         vp = lambda a: None if a is None else _np_ptr(a)  # noqa: E731
+        if side is not None:
+            sb = _side_bytes(side, B, self.n)
+            _native.check(_native.lib().qldpc_osd_decode_batch_side(
+                self.handle, vp(s), vp(pst), vp(cv), vp(bc), vp(sb), vp(o0), vp(ow), B, int(threads)),
+                "qldpc_osd_decode_batch_side")
+            return o0, ow
         _native.check(_native.lib().qldpc_osd_decode_batch(self.handle, vp(s), vp(pst), vp(cv), vp(bc), vp(o0),
                                                            vp(ow), B, int(threads)), "qldpc_osd_decode_batch")
         return o0, ow
@@ -458,22 +482,41 @@ class DeviceOSD(_Handle):
         return dict(zip(("row_words", "window_words", "threads", "workgroups"),
                         self._ints("qldpc_osd_gpu_geometry", "qldpc_osd_gpu_geometry", 4)))
 
-    def decode_device(self, synd_dev, post_dev, conv_dev, corr_dev, out0_dev, outw_dev, stream=None):
+    def set_side_probs(self, p0, p1):
+        """Side tables on the GPU handle (``qldpc_osd_gpu_set_side_probs``), as :meth:`HostOSD.set_side_probs`."""
+        n = self.graph.n
+        a, b = _channel_probs(p0, n, check_length=False), _channel_probs(p1, n, check_length=False)
+        _native.check(_native.lib().qldpc_osd_gpu_set_side_probs(self.handle, _np_ptr(a), _np_ptr(b)),
+                      "qldpc_osd_gpu_set_side_probs")
+        self.side_probs = (a, b)
+
+    def decode_device(self, synd_dev, post_dev, conv_dev, corr_dev, out0_dev, outw_dev, stream=None, side_dev=None):
+        """``side_dev``: device uint8 side bytes [B, n] of a side decode (``qldpc_osd_gpu_decode_side``)."""
         B = int(synd_dev.shape[0])
+        if side_dev is not None:
+            torch = _torch()
+            assert side_dev.dtype == torch.uint8 and side_dev.is_contiguous()
+            assert tuple(side_dev.shape) == (B, self.graph.n)
+            _native.check(_native.lib().qldpc_osd_gpu_decode_side(
+                self.handle, _ptr(synd_dev), _ptr(post_dev), _ptr(conv_dev), _ptr(corr_dev), _ptr(side_dev),
+                _ptr(out0_dev), _ptr(outw_dev), B, _stream(stream, synd_dev.device)), "qldpc_osd_gpu_decode_side")
+            return
         _native.check(_native.lib().qldpc_osd_gpu_decode(
             self.handle, _ptr(synd_dev), _ptr(post_dev), _ptr(conv_dev), _ptr(corr_dev), _ptr(out0_dev),
             _ptr(outw_dev), B, _stream(stream, synd_dev.device)), "qldpc_osd_gpu_decode")
 
-    def bposd_batch(self, bp: "DeviceBP", synd, host_post: bool = True):
+    def bposd_batch(self, bp: "DeviceBP", synd, host_post: bool = True, side=None):
         """Soft BP (``bp``, soft=True) then GPU OSD, all on the device: ``synd`` [B, m] ->
         (osdw, osd0, bp_corr, iters, conv, post) as host arrays (``post`` stays a device
-        tensor when ``host_post`` is False: 8 bytes per variable not worth copying back)."""
+        tensor when ``host_post`` is False: 8 bytes per variable not worth copying back).
+        ``side`` [B, n]: both stages are side decodes on the same bytes."""
         torch, dev, sd, corr, iters, conv = _decode_buffers(self.graph, synd, check_width=False)
         o0 = torch.empty_like(corr)
         ow = torch.empty_like(corr)
         st = _stream_handle(torch, dev)
-        post = bp._decode_soft_device(sd, corr, iters, conv, st)
-        self.decode_device(sd, post, conv, corr, o0, ow, st)
+        sb = None if side is None else torch.from_numpy(_side_bytes(side, sd.shape[0], self.graph.n)).to(dev)
+        post = bp._decode_soft_device(sd, corr, iters, conv, st, side=sb)
+        self.decode_device(sd, post, conv, corr, o0, ow, st, side_dev=sb)
         torch.cuda.synchronize(dev)
         return (ow.cpu().numpy(), o0.cpu().numpy(), corr.cpu().numpy().astype(np.int64), iters.cpu().numpy(),
                 conv.cpu().numpy().astype(bool), post.cpu().numpy() if host_post else post)
@@ -609,6 +652,15 @@ class DeviceMC(_Handle):
         GPU OSD stage and their failures are re-checked on the device."""
         self._osd = (osd_x, osd_z)  # keep the handles alive
         _native.check(_native.lib().qldpc_mc_set_osd(self.handle, _handle(osd_x), _handle(osd_z)), "qldpc_mc_set_osd")
+
+    def set_staged_osd(self, osd_x: "DeviceOSD | None", osd_z: "DeviceOSD | None"):
+        """BP+OSD in the staged loop (``qldpc_mc_set_staged_osd``): each sector's soft BP (engine 7
+        without legs, or engine 8 with ``soft=True``) is followed by the GPU OSD over the batch, and
+        OSD's correction is the sector's.  With a channel update the second sector's OSD is a side
+        decode (:meth:`DeviceOSD.set_side_probs`).  Staged handles only."""
+        self._staged_osd = (osd_x, osd_z)  # keep the handles alive
+        _native.check(_native.lib().qldpc_mc_set_staged_osd(self.handle, _handle(osd_x), _handle(osd_z)),
+                      "qldpc_mc_set_staged_osd")
 
     def set_channel_update(self, direction):
         """X/Z-correlated decoding (``qldpc_mc_set_channel_update``): None, ``"x->z"`` or ``"z->x"``.  The

@@ -290,8 +290,11 @@ class CodeSimulator_DataError(_ShotStream):
     second with, per shot and qubit, the prior conditioned on the first decoder's decision
     (:func:`~.decoders.channel_update_probs` of ``pauli_error_probs``).  The fused paths build the
     second sector's side-capable handle from the user decoder's graph and parameters and run the
-    staged pipeline (``qldpc_mc_set_channel_update``); both sectors are then always decoded.  BP only:
-    BP+OSD sectors raise ``TypeError``.
+    staged pipeline (``qldpc_mc_set_channel_update``); both sectors are then always decoded.  BP+OSD runs
+    when both sectors are ``BPOSD_Decoder`` instances and the second one was built with ``side_probs``
+    (BP and OSD of the second sector then both decode under the conditional priors; the fused paths put
+    the GPU OSD behind each sector's soft BP, ``qldpc_mc_set_staged_osd``); BP+OSD sectors without
+    ``side_probs``, and a BP sector mixed with a BP+OSD one, raise ``TypeError``.
     """
 
     def __init__(self, code=None, decoder_x=None, decoder_z=None, pauli_error_probs=(0.01, 0.01, 0.01),
@@ -331,9 +334,11 @@ class CodeSimulator_DataError(_ShotStream):
         else:
             x_first = self.channel_update == "x->z"
             second = self.decoder_z if x_first else self.decoder_x
-            if _is_bposd(self.decoder_x) or _is_bposd(self.decoder_z) or getattr(second, "side_probs", None) is None:
+            if not self._cu_bposd() and (_is_bposd(self.decoder_x) or _is_bposd(self.decoder_z)
+                                         or getattr(second, "side_probs", None) is None):
                 raise TypeError(f"channel_update={self.channel_update!r} needs a BP decoder built with side_probs "
-                                "for the second sector (BP+OSD is not supported)")
+                                "for the second sector (BP+OSD: both sectors BPOSD_Decoder, the second with "
+                                "side_probs)")
             if x_first:
                 decoded_x = self.decoder_x.decode(synd_x)
                 decoded_z = second.decode(synd_z, side=decoded_x)
@@ -363,6 +368,56 @@ class CodeSimulator_DataError(_ShotStream):
             self._mc = DeviceMC(self.code, bx, bz)
         return self._mc
 
+    def _cu_bposd(self) -> bool:
+        """A ``channel_update`` run on BP+OSD: both sectors are BPOSD_Decoder instances and the second
+        one carries ``side_probs``."""
+        if self.channel_update is None or not (_is_bposd(self.decoder_x) and _is_bposd(self.decoder_z)):
+            return False
+        second = self.decoder_z if self.channel_update == "x->z" else self.decoder_x
+        return getattr(second, "side_probs", None) is not None
+
+    def _channel_update_bposd_mc(self):
+        """The staged handle of a BP+OSD ``channel_update`` run: each sector's BP rebuilt soft-capable on
+        the decoder's own graph and parameters (engine 7 without memory or legs for the flooding
+        schedule, engine 8 with soft output for the serial one), the GPU OSD behind it
+        (``qldpc_mc_set_staged_osd``), and the conditional priors of ``pauli_error_probs`` as the side
+        tables of the second sector's BP and OSD."""
+        from .decoders import channel_update_probs
+        from .engine import DeviceBP, DeviceMC, DeviceOSD, RelayParams
+
+        decs = (self.decoder_x, self.decoder_z)
+        if any(d.decoder.bp_method != 1 for d in decs):
+            raise ValueError("channel_update needs minimum_sum decoders: product_sum has no side decode")
+        if any(getattr(d, "gpu_osd", None) is None for d in decs):
+            raise TypeError("channel_update with BP+OSD needs the GPU OSD stage on both sectors")
+        x_first = self.channel_update == "x->z"
+        _, p0, p1 = channel_update_probs(*self.channel_probs, self.channel_update)
+
+        def soft_bp(dec):
+            b = dec.decoder
+            if b.relay is not None or (b.schedule == "serial" and b.soft):
+                return b  # already engine 7 / engine 8 with soft output
+            relay = RelayParams(pre_iter=b.max_iter, pre_gamma=0.0, num_legs=0) if b.schedule == "parallel" else None
+            return DeviceBP(None, b.channel_probs, max_iter=b.max_iter, bp_method="minimum_sum",
+                            ms_scaling_factor=b.ms_scaling_factor, precision=b.precision, graph=b.graph,
+                            relay=relay, schedule=b.schedule, soft=relay is None)
+
+        first_dec, second_dec = (decs[0], decs[1]) if x_first else (decs[1], decs[0])
+        first = soft_bp(first_dec)
+        sb = second_dec.decoder
+        relay = RelayParams(pre_iter=sb.max_iter, pre_gamma=0.0, num_legs=0) if sb.schedule == "parallel" else None
+        second = DeviceBP(None, sb.channel_probs, max_iter=sb.max_iter, bp_method="minimum_sum",
+                          ms_scaling_factor=sb.ms_scaling_factor, precision=sb.precision, graph=sb.graph,
+                          relay=relay, schedule=sb.schedule, soft=relay is None)
+        second.set_side_probs(p0, p1)
+        osd2 = DeviceOSD(sb.graph, second_dec.channel_probs, second_dec.osd_method, second_dec.osd_order)
+        osd2.set_side_probs(p0, p1)
+        osd1 = first_dec.gpu_osd
+        mc = DeviceMC(self.code, first if x_first else second, second if x_first else first, staged=True)
+        mc.set_staged_osd(osd1 if x_first else osd2, osd2 if x_first else osd1)
+        mc.set_channel_update(self.channel_update)
+        return mc
+
     def _channel_update_mc(self):
         """The staged handle of a ``channel_update`` run: the first sector's engine BP as the user built
         it, the second sector's side-capable handle (engine 7 for a flooding or relay decoder, engine 8
@@ -372,8 +427,12 @@ class CodeSimulator_DataError(_ShotStream):
             from .decoders import channel_update_probs
             from .engine import DeviceBP, DeviceMC, RelayParams
 
+            if self._cu_bposd():
+                self._mc_cu = self._channel_update_bposd_mc()
+                return self._mc_cu
             if _is_bposd(self.decoder_x) or _is_bposd(self.decoder_z):
-                raise TypeError("channel_update does not run with BP+OSD sectors")
+                raise TypeError("channel_update does not run with BP+OSD sectors unless both are BPOSD_Decoder "
+                                "instances and the second one carries side_probs")
             bx, bz = _engine_bp(self.decoder_x), _engine_bp(self.decoder_z)
             if bx is None or bz is None:
                 raise TypeError("channel_update decodes both sectors: it needs engine BPDecoder instances for both")
@@ -477,6 +536,12 @@ class CodeSimulator_DataError(_ShotStream):
         converges.  Otherwise the host-assisted path below.  ``keep_shots`` stores ``last_shots``
         = (errors [S, n] bit0 x / bit1 z, sector failures [S, 2]).
         """
+        if self.channel_update is not None:  # BP+OSD under a channel update: the staged loop
+            if not self._cu_bposd():
+                raise TypeError("bposd_counts with channel_update needs BPOSD_Decoder instances for both sectors, "
+                                "the second one built with side_probs")
+            res = self.fused_counts(num_run)
+            return res.failures, res.shots, int(sum(res.sector_nonconv))
         if not self._bposd_ready():
             raise TypeError("bposd_counts needs BPOSD_Decoder instances for the sectors eval_logical_type uses")
         need_x = self.eval_logical_type != "Z"
@@ -607,8 +672,11 @@ class CodeSimulator_DataError(_ShotStream):
 
     def _batch_failures(self, n: int) -> int:
         if self.channel_update is not None:
+            if self._cu_bposd():
+                return self.fused_counts(n).failures
             if _is_bposd(self.decoder_x) or _is_bposd(self.decoder_z):
-                raise TypeError("channel_update does not run with BP+OSD sectors")
+                raise TypeError("channel_update does not run with BP+OSD sectors unless both are BPOSD_Decoder "
+                                "instances and the second one carries side_probs")
             if _engine_bp(self.decoder_x) is not None and _engine_bp(self.decoder_z) is not None:
                 return self.fused_counts(n).failures
             return int(np.sum([self._single_run() for _ in range(n)]))
@@ -1273,8 +1341,17 @@ class _CodeFamilyBase:
     def _data_simulator(self, eval_code, eval_p, eval_logical_type, channel_update=None):
         """The ``'data'`` point: decoder2 on hz / hx with ``p_data = eval_p`` and the
         :class:`CodeSimulator_DataError` of the depolarizing channel at ``3/2 eval_p``."""
-        decoder_x = self.decoder2_class.GetDecoder({"h": eval_code.hz, "p_data": eval_p})
-        decoder_z = self.decoder2_class.GetDecoder({"h": eval_code.hx, "p_data": eval_p})
+        px = {"h": eval_code.hz, "p_data": eval_p}
+        pz = {"h": eval_code.hx, "p_data": eval_p}
+        if channel_update is not None:
+            from .decoders import BPOSD_Decoder_Class, channel_update_probs
+
+            if isinstance(self.decoder2_class, BPOSD_Decoder_Class):
+                # BP+OSD: the second sector's decoder is built side-capable, on the channel's conditional priors
+                _, p0, p1 = channel_update_probs(*_depolarizing_probs(eval_p), channel_update)
+                (pz if channel_update == "x->z" else px)["side_probs"] = (p0, p1)
+        decoder_x = self.decoder2_class.GetDecoder(px)
+        decoder_z = self.decoder2_class.GetDecoder(pz)
         return CodeSimulator_DataError(code=eval_code, decoder_x=decoder_x, decoder_z=decoder_z,
                                        pauli_error_probs=_depolarizing_probs(eval_p),
                                        eval_logical_type=eval_logical_type, channel_update=channel_update)

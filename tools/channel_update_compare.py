@@ -15,6 +15,13 @@ runs ``--warmup`` untimed and ``--steps`` timed steps of ``shots`` shots, each s
 synchronise; shots/s is shots over the median step, with the slowest and fastest step beside it.  One
 JSON line per configuration goes to stdout.
 
+Four BP+OSD lines follow on the same errors (OSD-E(10) behind the same flooding min-sum; ``--no-bposd``
+leaves them out): independent sectors on the fused engine-3 BP+OSD loop (``qldpc_mc_set_osd``);
+independent sectors on engine 7 through the staged loop with the GPU OSD behind each sector's soft BP
+(``qldpc_mc_set_staged_osd``; the same law: its failure count must equal the fused line's, asserted);
+``x->z`` and ``z->x`` BP+OSD (the second sector's BP and OSD under the conditional priors).  Their
+``nonconverged_decodes`` are the decodes handed to OSD per sector.
+
 Two more lines give the cost of the side selection alone, per engine: one handle decodes the X-sector
 syndromes of 65,536 sampled shots plainly and as a side decode with ``p0 = p1`` = its own prior under
 random side bytes, so both run the same iterations bit for bit (asserted) and differ only in the
@@ -31,14 +38,16 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def measure(sim, shots, steps, warmup):
+def measure(sim, shots, steps, warmup, run=None):
+    """``run(shots)``: one step's MCResult (default: ``sim.fused_counts``)."""
+    run = run or sim.fused_counts
     for _ in range(warmup):
-        sim.fused_counts(shots)
+        run(shots)
     sim.rewind_shots()  # every configuration's timed steps cover the same shots
     times, fails, nonconv, iters, decodes = [], 0, [0, 0], [0, 0], [0, 0]
     for _ in range(steps):
         t0 = time.perf_counter()
-        r = sim.fused_counts(shots)  # ends in a device synchronise
+        r = run(shots)  # ends in a device synchronise
         times.append(time.perf_counter() - t0)
         fails += r.failures
         for q in range(2):
@@ -87,6 +96,49 @@ def side_decode_cost(code, probs, pauli, mi, precision, seed, steps, warmup, ser
             "side_step_seconds": times[1]}
 
 
+def bposd_lines(a, code, pauli, probs, mi, out, BPOSD_Decoder, CodeSimulator_DataError, channel_update_probs,
+                DeviceBP, DeviceMC, DeviceOSD, RelayParams):
+    """The four BP+OSD configurations, on the Philox errors of the BP lines."""
+    def bposd(h, side_probs=None):
+        return BPOSD_Decoder(h, probs, mi, "minimum_sum", 0.625, "osd_e", a.osd_order, precision=a.precision,
+                             side_probs=side_probs)
+
+    def emit(name, r):
+        out["configurations"][name] = r
+        print(json.dumps({"configuration": name, "code": a.code, "eval_p": a.p, **r}), flush=True)
+
+    # independent, fused engine-3 loop (bposd_counts' device path; its counters stay in last_result)
+    sim = CodeSimulator_DataError(code, bposd(code.hz), bposd(code.hx), pauli, "Total", seed=a.seed)
+
+    def fused(shots):
+        sim.bposd_counts(shots)
+        return sim.last_result
+
+    emit("independent BP+OSD engine 3 (fused)", measure(sim, a.shots, a.steps, a.warmup, fused))
+    # independent, staged loop: engine 7 without memory or legs, the GPU OSD behind each sector
+    relay = RelayParams(pre_iter=mi, pre_gamma=0.0, num_legs=0)
+    dx = DeviceBP(code.csr("hz"), probs, ms_scaling_factor=0.625, precision=a.precision, relay=relay)
+    dz = DeviceBP(code.csr("hx"), probs, ms_scaling_factor=0.625, precision=a.precision, relay=relay)
+    mc = DeviceMC(code, dx, dz, staged=True)
+    mc.set_staged_osd(DeviceOSD(dx.graph, probs, "osd_e", a.osd_order), DeviceOSD(dz.graph, probs, "osd_e", a.osd_order))
+    sim = CodeSimulator_DataError(code, bposd(code.hz), bposd(code.hx), pauli, "Total", seed=a.seed)
+
+    def staged(shots):
+        return sim._fused_run(lambda: mc, shots, lambda loop, b, c, cnt: loop.launch(*pauli, sim.seed, b, c, "Total", cnt))
+
+    emit("independent BP+OSD engine 7 (staged)", measure(sim, a.shots, a.steps, a.warmup, staged))
+    f3, f7 = (out["configurations"][k]["failures"] for k in ("independent BP+OSD engine 3 (fused)",
+                                                              "independent BP+OSD engine 7 (staged)"))
+    assert f3 == f7, f"same errors, same law: the fused BP+OSD loop counted {f3} failures, the staged one {f7}"
+    for direction in ("x->z", "z->x"):
+        _, p0, p1 = channel_update_probs(*pauli, direction)
+        x_first = direction == "x->z"
+        sim = CodeSimulator_DataError(code, bposd(code.hz, None if x_first else (p0, p1)),
+                                      bposd(code.hx, (p0, p1) if x_first else None), pauli, "Total", seed=a.seed,
+                                      channel_update=direction)
+        emit(f"{direction} BP+OSD engine 7", measure(sim, a.shots, a.steps, a.warmup))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("code")
@@ -97,13 +149,16 @@ def main():
     ap.add_argument("--precision", type=int, default=64, choices=(32, 64))
     ap.add_argument("--max-iter-ratio", type=float, default=10, help="max_iter = N / ratio")
     ap.add_argument("--seed", type=int, default=20251021)
+    ap.add_argument("--osd-order", type=int, default=10, help="order of the BP+OSD lines' OSD-E")
+    ap.add_argument("--no-bposd", action="store_true", help="leave the BP+OSD lines out")
     ap.add_argument("--json", default=None, help="also write the results to this file")
     a = ap.parse_args()
 
     import numpy as np
 
     from qldpc_fault_tolerance_amd import codes
-    from qldpc_fault_tolerance_amd.decoders import BPDecoder, RelayBPDecoder
+    from qldpc_fault_tolerance_amd.decoders import BPDecoder, BPOSD_Decoder, RelayBPDecoder, channel_update_probs
+    from qldpc_fault_tolerance_amd.engine import DeviceBP, DeviceMC, DeviceOSD, RelayParams
     from qldpc_fault_tolerance_amd.simulators import CodeSimulator_DataError
 
     code = codes.get_code(a.code)
@@ -134,6 +189,9 @@ def main():
     e3, e7 = (out["configurations"][k]["failures"] for k in ("independent engine 3 (fused)",
                                                               "independent engine 7 (staged)"))
     assert e3 == e7, f"same errors, same law: engine 3 counted {e3} failures, engine 7 {e7}"
+    if not a.no_bposd:
+        bposd_lines(a, code, pauli, probs, mi, out, BPOSD_Decoder, CodeSimulator_DataError, channel_update_probs,
+                    DeviceBP, DeviceMC, DeviceOSD, RelayParams)
     out["side_decode_cost"] = {}
     for name, is_serial in (("engine 7", False), ("engine 8", True)):
         r = side_decode_cost(code, probs, pauli, mi, a.precision, a.seed, a.steps, a.warmup, is_serial)
