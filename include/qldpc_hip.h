@@ -198,6 +198,57 @@ int qldpc_osd_gpu_geometry(const qldpc_osd_gpu *osd, int32_t *row_words, int32_t
                            int32_t *workgroups);
 
 /*
+ * BP+LSD: localised statistics decoding of order 0 (Hillmann et al. 2024; ldpc v2's BpLsdDecoder) as the
+ * second stage in place of OSD, through the same two handles (csrc/lsd.hip).
+ * THE LAW.  Inputs for one syndrome: H (m x n), the syndrome s, the posteriors L[n] (double: BP's
+ * log_prob_ratios, what the OSD stage receives) and bits_per_step = k >= 1.  Every choice below is a set
+ * or a total order, so no execution order can change a result.
+ *   column order : j comes before j' when L_j < L_j' as doubles, or when neither is less and j < j' (the
+ *                  OSD stage's stable ascending sort: -0 and +0 tie, +-inf are ordered, NaN is unspecified).
+ *   state        : active columns A (empty at first), active rows R (at first {i : s_i = 1}); every row
+ *                  adjacent to a column of A is in R.
+ *   clusters     : the connected components of the bipartite graph on R and A with the edges of H; a seed
+ *                  row without an active column is a cluster of its own.  A cluster C is valid when s on
+ *                  its rows lies in the column space of H[rows(C), cols(C)].
+ *   round        : every invalid cluster nominates the first min(k, |boundary|) columns of its boundary
+ *                  (the columns outside A adjacent to one of its rows) in column order; all nominated
+ *                  columns join A at once (a column nominated twice joins once) and their rows join R;
+ *                  clusters and validity are formed anew (a merge can make a valid cluster invalid again,
+ *                  and the reverse).  Rounds repeat until no invalid cluster has a boundary column; an
+ *                  invalid cluster without boundary is unsolvable (it holds its whole component of the
+ *                  Tanner graph and is still inconsistent).
+ *   output       : x_j = 0 outside A and on the columns of unsolvable clusters; on each valid cluster x is
+ *                  its OSD-0 solution: walk its columns in column order, keep each column independent of
+ *                  the kept ones, x = the unique solution supported on the kept columns.
+ *   statistics   : int32 [4] = valid (1: no unsolvable cluster), rounds (those that added a column), |A|,
+ *                  clusters at the end.  An all-zero syndrome gives x = 0 and (1, 0, 0, 0), as a
+ *                  converged entry does (which copies bp_corr).
+ * The stage uses no channel weights: order 0 weighs no candidates.
+ * qldpc_osd_create_lsd: a host stage.  qldpc_osd_decode_batch on it writes the law's x to out_osd0 (if
+ * given) and out_osdw; qldpc_osd_set_side_probs succeeds and a side decode equals the plain decode;
+ * qldpc_osd_rank answers.  QLDPC_EINVAL: bits_per_step < 1, NULL, a bad shape or column index.
+ * qldpc_lsd_decode_batch_stats: the same decode plus stats int32 [B][4] (or NULL); LSD handles only.
+ * qldpc_osd_gpu_create_lsd: the GPU stage, m, n <= 8192 (QLDPC_ENOTSUP past it), one 256-thread
+ * workgroup per non-converged syndrome.  Every qldpc_osd_gpu_decode* call, qldpc_mc_set_osd,
+ * qldpc_mc_set_staged_osd, qldpc_phenl_set_final_osd and qldpc_circ_set_final_osd take such a handle
+ * (the latter also a host LSD stage); qldpc_osd_gpu_geometry answers row_words = 0 and the launch.
+ * qldpc_lsd_gpu_decode adds d_stats int32 [B][4] (or NULL) and writes one output.  The active image
+ * lives in LDS up to a row capacity cut at create time (qldpc_lsd_gpu_info: lds_rows, 0 = none, and the
+ * LDS bytes per workgroup); a syndrome that outgrows it, or every syndrome under QLDPC_LSD_WS=1, is
+ * decoded on the workgroup's HBM slice, with the same answer.
+ */
+int qldpc_osd_create_lsd(int32_t m, int32_t n, const int32_t *row_ptr, const int32_t *col_idx,
+                         int32_t bits_per_step, qldpc_osd **out);
+int qldpc_lsd_decode_batch_stats(const qldpc_osd *osd, const uint8_t *synd, const double *post, const uint8_t *conv,
+                                 const uint8_t *bp_corr, uint8_t *out, int32_t *stats, int64_t B, int32_t threads);
+int qldpc_osd_gpu_create_lsd(const qldpc_graph *g, int32_t bits_per_step, qldpc_osd_gpu **out);
+int qldpc_lsd_gpu_decode(qldpc_osd_gpu *osd, const uint8_t *d_synd, const double *d_post, const uint8_t *d_conv,
+                         const uint8_t *d_bp_corr, uint8_t *d_out, int32_t *d_stats, int64_t B, void *stream);
+int qldpc_lsd_gpu_info(const qldpc_osd_gpu *osd, int32_t *lds_rows, int32_t *lds_bytes);
+/* decodes since the last call that outgrew the LDS image and ran again on the HBM slice; waits for the device */
+int qldpc_lsd_gpu_retries(qldpc_osd_gpu *osd, uint64_t *count);
+
+/*
  * Fused Monte Carlo shot loop = CodeSimulator_DataError._single_run
  * (src/Simulators.py:117-168) for many shots in one launch: per shot sample
  * the Pauli error (3-way split of u, :99-113), syndrome H e, BP decode,

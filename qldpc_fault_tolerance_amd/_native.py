@@ -41,6 +41,8 @@ EXPORTED = [
     "qldpc_serial_decode_host_side", "qldpc_mc_set_channel_update",
     "qldpc_bp_decode_batch_side_soft", "qldpc_osd_set_side_probs", "qldpc_osd_decode_batch_side",
     "qldpc_osd_gpu_set_side_probs", "qldpc_osd_gpu_decode_side", "qldpc_mc_set_staged_osd",
+    "qldpc_osd_create_lsd", "qldpc_lsd_decode_batch_stats", "qldpc_osd_gpu_create_lsd", "qldpc_lsd_gpu_decode",
+    "qldpc_lsd_gpu_info", "qldpc_lsd_gpu_retries",
 ]
 COMM_ID_BYTES = 128
 
@@ -281,6 +283,18 @@ def _declare(L):
     L.qldpc_mc_set_staged_osd.argtypes = [_vp, _vp, _vp]
     L.qldpc_osd_gpu_decode_side.restype = ctypes.c_int
     L.qldpc_osd_gpu_decode_side.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]
+    L.qldpc_osd_create_lsd.restype = ctypes.c_int
+    L.qldpc_osd_create_lsd.argtypes = [_i32, _i32, _vp, _vp, _i32, _pp]
+    L.qldpc_lsd_decode_batch_stats.restype = ctypes.c_int
+    L.qldpc_lsd_decode_batch_stats.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32]
+    L.qldpc_osd_gpu_create_lsd.restype = ctypes.c_int
+    L.qldpc_osd_gpu_create_lsd.argtypes = [_vp, _i32, _pp]
+    L.qldpc_lsd_gpu_decode.restype = ctypes.c_int
+    L.qldpc_lsd_gpu_decode.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]
+    L.qldpc_lsd_gpu_info.restype = ctypes.c_int
+    L.qldpc_lsd_gpu_info.argtypes = [_vp] + [ctypes.POINTER(_i32)] * 2
+    L.qldpc_lsd_gpu_retries.restype = ctypes.c_int
+    L.qldpc_lsd_gpu_retries.argtypes = [_vp, ctypes.POINTER(_u64)]
 
 
 def lib():

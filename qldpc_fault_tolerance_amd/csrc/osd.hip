@@ -31,19 +31,10 @@
 #include <utility>
 #include <vector>
 
+#include "osd_types.h"
 #include "runtime.h"
 
 using qldpc_rt::set_err;
-
-struct qldpc_osd {
-  int m = 0, n = 0, method = 1, order = 0, rank = 0;
-  std::vector<std::vector<int32_t>> col_rows;
-  std::vector<double> w;  // log(1/p_j)
-  bool uniform = true;
-  // side tables (qldpc_osd_set_side_probs): w_s[j] = log(1 / p_s[j]); a side decode weighs column j of
-  // syndrome b with w_{side[b][j] & 1}[j].  Empty until set.
-  std::vector<double> ws0, ws1;
-};
 
 namespace {
 
@@ -360,6 +351,9 @@ int osd_decode_batch_impl(const qldpc_osd* osd, const uint8_t* synd, const doubl
   if (!osd || (B > 0 && (!synd || !post || !out_osdw))) return set_err(QLDPC_EINVAL, "NULL argument");
   if (conv && !bp_corr) return set_err(QLDPC_EINVAL, "conv needs bp_corr");
   if (B <= 0) return 0;
+  // an LSD stage (qldpc_osd_create_lsd) weighs no candidates: its side decode is its plain decode
+  if (osd->lsd_k)
+    return qldpc_rt::lsd_decode_batch_host(osd, synd, post, conv, bp_corr, out_osd0, out_osdw, nullptr, B, threads);
   const int m = osd->m, n = osd->n;
   std::vector<int64_t> todo;
   for (int64_t b = 0; b < B; ++b) {
@@ -1084,17 +1078,6 @@ __global__ void __launch_bounds__(LB) osd_gpu_kernel(OsdGpuArgs A) {
 
 }  // namespace
 
-struct qldpc_osd_gpu {
-  qldpc_osd host;  // shape, method, order, rank
-  int device = 0, grid = 0, W = 0, RW = 0, NP = 0, nh = 0, m_lds = 0, bits_off = 0;
-  int wr = 0, pbuf_off = 0;  // register-row mode: compile-time words per row (0 = off), LDS pivot buffer
-  int rr_tb = 0;             // register-row mode: threads per workgroup = m rounded up to waves
-  size_t lds = 0;
-  long long ws_words = 0, iws_ints = 0;
-  qldpc_rt::DevBuf rp, ci, ws, iws, softw;  // softw: [n] log(1 / p_j) when the priors are not uniform
-  qldpc_rt::DevBuf sw0, sw1;  // side tables [n] each (qldpc_osd_gpu_set_side_probs), else empty
-};
-
 namespace {
 
 // BP+OSD failure re-check of the fused shot loop's candidates (qldpc_mc_set_osd): per
@@ -1227,6 +1210,7 @@ int qldpc_osd_gpu_create(const qldpc_graph* g, const double* channel_probs, int3
 int qldpc_rt::osd_gpu_from_host(const qldpc_graph* g, const qldpc_osd* O, qldpc_osd_gpu** out) {
   if (!g || !O || !out) return set_err(QLDPC_EINVAL, "NULL argument");
   if (!osd_host_matches(O, g)) return set_err(QLDPC_EINVAL, "host OSD stage was built on a different graph");
+  if (O->lsd_k) return lsd_gpu_from_host(g, O, out);
   const int osd_method = O->method, osd_order = O->order;
   int rc = 0;
   if (g->n > kOsdMaxN || (osd_method == 1 && osd_order > 20))  // 20: the host stage's cap (qldpc_osd_create)
@@ -1314,6 +1298,11 @@ int qldpc_osd_gpu_geometry(const qldpc_osd_gpu* osd, int32_t* row_words, int32_t
   if (!osd || !row_words || !window_words || !threads || !workgroups) return set_err(QLDPC_EINVAL, "NULL argument");
   *row_words = osd->wr;
   *window_words = 0;  // kept for the ABI: no layout holds a column window
+  if (osd->host.lsd_k) {  // the cluster kernel (lsd.hip): no register rows
+    *threads = qldpc_rt::lsd_gpu_threads();
+    *workgroups = osd->grid;
+    return 0;
+  }
   *threads = osd->wr ? osd->rr_tb : osd->m_lds ? kOsdThreadsLds : kOsdThreads;
   *workgroups = osd->grid;
   return 0;
@@ -1322,7 +1311,7 @@ int qldpc_osd_gpu_geometry(const qldpc_osd_gpu* osd, int32_t* row_words, int32_t
 int qldpc_osd_gpu_destroy(qldpc_osd_gpu* osd) {
   if (!osd) return 0;
   osd->rp.release(); osd->ci.release(); osd->ws.release(); osd->iws.release(); osd->softw.release();
-  osd->sw0.release(); osd->sw1.release();
+  osd->sw0.release(); osd->sw1.release(); osd->cp.release(); osd->ce.release(); osd->lsd_retries.release();
   delete osd;
   return 0;
 }
@@ -1354,6 +1343,11 @@ int osd_gpu_decode_any(qldpc_osd_gpu* osd, const uint8_t* d_synd, const double* 
   if (!osd || (B > 0 && (!d_synd || !d_post || !d_outw))) return set_err(QLDPC_EINVAL, "NULL argument");
   if (d_conv && !d_bp_corr) return set_err(QLDPC_EINVAL, "conv needs bp_corr");
   if (B <= 0) return 0;
+  if (osd->host.lsd_k) {  // LSD handle: the cluster kernel; a side decode is its plain decode (no weights)
+    if (d_side && !osd->sw0.p)
+      return set_err(QLDPC_EINVAL, "side decode without side tables (qldpc_osd_gpu_set_side_probs)");
+    return lsd_gpu_launch(osd, d_synd, d_post, d_conv, d_shot, d_bp_corr, d_out0, d_outw, nullptr, B, stream);
+  }
   QLDPC_HIP(hipSetDevice(osd->device));
   OsdGpuArgs a;
   a.rp = static_cast<const int32_t*>(osd->rp.p);
@@ -1415,7 +1409,7 @@ int qldpc_osd_gpu_set_side_probs(qldpc_osd_gpu* osd, const double* p0, const dou
   QLDPC_HIP(hipDeviceSynchronize());  // no decode in flight on the workspace that is replaced
   const long long words = (long long)osd->W * osd->host.m + (long long)(1 + osd->nh) * osd->RW +
                           (long long)(1 + osd->nh) * osd->W + n;
-  if (words > osd->ws_words) {
+  if (!osd->host.lsd_k && words > osd->ws_words) {  // (an LSD handle's workspace holds no weights)
     osd->ws.release();
     osd->ws_words = words;
     if ((rc = osd->ws.alloc((size_t)osd->grid * osd->ws_words * 8))) return rc;

@@ -255,7 +255,7 @@ class BPOSD_Decoder:
     def __init__(self, h, channel_probs, max_iter, bp_method, ms_scaling_factor, osd_method, osd_order,
                  precision: int = 64, device: int | None = None, osd_threads: int = 0, use_gpu_osd: bool = True,
                  schedule: str = "parallel", side_probs=None):
-        from .engine import DeviceBP, DeviceOSD, HostOSD, RelayParams, bp_method_code
+        from .engine import DeviceBP, RelayParams, bp_method_code
 
         self.h = h
         self.schedule = schedule
@@ -276,18 +276,31 @@ class BPOSD_Decoder:
         self.decoder = DeviceBP(H, self.channel_probs, max_iter=_int_max_iter(max_iter, H.n), bp_method=bp_method,
                                 ms_scaling_factor=ms_scaling_factor, precision=precision, device=device,
                                 soft=relay is None, schedule=schedule, relay=relay)
-        self.osd = HostOSD(H, self.channel_probs, osd_method=osd_method, osd_order=osd_order)
-        # OSD on the GPU (uniform priors: popcount weights; non-uniform: soft weights); the host stage
-        # stays for use_gpu_osd=False and graphs past the GPU kernel's envelope
-        self.gpu_osd = (DeviceOSD(self.decoder.graph, self.channel_probs, osd_method, osd_order)
-                        if use_gpu_osd and DeviceOSD.supported(H.n, self.channel_probs, osd_method, osd_order)
-                        else None)
+        self.osd, self.gpu_osd = self._second_stage(H, use_gpu_osd)
         if side_probs is not None:
             for stage in (self.decoder, self.osd, self.gpu_osd):
                 if stage is not None:
                     _set_side_probs(stage, side_probs)
         self.osd_threads = osd_threads
         self.iter, self.converge = 0, 0
+
+    def new_gpu_stage(self, graph):
+        """A fresh GPU second stage of this decoder's kind on ``graph`` (the shot loops that give the stage
+        tables of their own build theirs through here)."""
+        from .engine import DeviceOSD
+
+        return DeviceOSD(graph, self.channel_probs, self.osd_method, self.osd_order)
+
+    def _second_stage(self, H, use_gpu_osd):
+        """(host stage, GPU stage or None) behind BP."""
+        from .engine import DeviceOSD, HostOSD
+
+        # OSD on the GPU (uniform priors: popcount weights; non-uniform: soft weights); the host stage
+        # stays for use_gpu_osd=False and graphs past the GPU kernel's envelope
+        gpu = (self.new_gpu_stage(self.decoder.graph)
+               if use_gpu_osd and DeviceOSD.supported(H.n, self.channel_probs, self.osd_method, self.osd_order)
+               else None)
+        return HostOSD(H, self.channel_probs, osd_method=self.osd_method, osd_order=self.osd_order), gpu
 
     def decode_batch(self, synd, side=None):
         """[B, m] syndromes -> osdw corrections [B, n] (int); also sets the batch's
@@ -318,6 +331,50 @@ class BPOSD_Decoder:
         self.log_prob_ratios = pb[0] if isinstance(pb, np.ndarray) else pb[0].cpu().numpy()
         self.iter, self.converge = int(self.iters_batch[0]), int(self.conv_batch[0])
         return self.osdw_decoding
+
+
+class BPLSD_Decoder(BPOSD_Decoder):
+    """BP, then localised statistics decoding of order 0 (ldpc v2's ``BpLsdDecoder``; the law in
+    include/qldpc_hip.h, csrc/lsd.hip) where BP does not converge: clusters grown around the unsatisfied
+    checks in BP's reliability order, ``bits_per_step`` columns per cluster and round, elimination inside
+    the clusters alone.  A :class:`BPOSD_Decoder` with the same attributes, so every shot loop that takes
+    one takes this; the stage weighs no candidates, hence ``osd0_decoding == osdw_decoding``."""
+
+    def __init__(self, h, channel_probs, max_iter, bp_method, ms_scaling_factor, bits_per_step: int = 1,
+                 precision: int = 64, device: int | None = None, use_gpu_osd: bool = True,
+                 schedule: str = "parallel", side_probs=None):
+        self.bits_per_step = int(bits_per_step)
+        super().__init__(h, channel_probs, max_iter, bp_method, ms_scaling_factor, "osd_0", 0, precision=precision,
+                         device=device, use_gpu_osd=use_gpu_osd, schedule=schedule, side_probs=side_probs)
+
+    def new_gpu_stage(self, graph):
+        from .engine import DeviceLSD
+
+        return DeviceLSD(graph, self.bits_per_step)
+
+    def _second_stage(self, H, use_gpu_osd):
+        from .engine import DeviceLSD, HostLSD
+
+        gpu = (self.new_gpu_stage(self.decoder.graph)
+               if use_gpu_osd and DeviceLSD.supported(H.m, H.n) else None)
+        return HostLSD(H, self.bits_per_step), gpu
+
+    def lsd_stats_batch(self, synd, side=None):
+        """:meth:`decode_batch` plus the stage's statistics: (x [B, n] int, stats [B, 4] int32 = valid,
+        rounds, active columns, clusters); converged rows report (1, 0, 0, 0).  One BP decode and one
+        decode of the stage; the batch attributes are set as :meth:`decode_batch` sets them."""
+        s = np.atleast_2d(np.asarray(synd))
+        if side is not None and self.side_probs is None:
+            raise TypeError("a side decode needs a BPLSD_Decoder built with side_probs")
+        if self.gpu_osd is not None:
+            x, st, corr, iters, conv, post = self.gpu_osd.bplsd_batch_stats(self.decoder, s, side=side)
+        else:
+            corr, iters, conv, post = (self.decoder.decode_batch_soft(s) if side is None
+                                       else self.decoder.decode_batch_soft(s, side))
+            x, st = self.osd.decode_batch_stats(s, post, conv, corr)  # (a side decode is the plain decode)
+        self.bp_batch, self.iters_batch, self.conv_batch, self.post_batch = corr, iters, conv, post
+        self.osd0_batch = x.astype(np.int64)
+        return self.osd0_batch.copy(), st
 
 
 class DecoderClass(ABC):
@@ -413,6 +470,29 @@ class BPOSD_Decoder_Class(DecoderClass):
         return BPOSD_Decoder(h=p["h"], channel_probs=probs, max_iter=max_iter, bp_method=d["bp_method"],
                              ms_scaling_factor=d["ms_scaling_factor"], osd_method=d["osd_method"],
                              osd_order=d["osd_order"], precision=self.precision, device=self.device,
+                             schedule=self.schedule, side_probs=p.get("side_probs"))
+
+
+class BPLSD_Decoder_Class(DecoderClass):
+    """:class:`BPLSD_Decoder` factory keyed like :class:`BPOSD_Decoder_Class`."""
+
+    def __init__(self, max_iter_ratio: int, bp_method: str, ms_scaling_factor: float, bits_per_step: int = 1,
+                 precision: int = 64, device: int | None = None, schedule: str = "parallel"):
+        self.decoder_default_params = {"max_iter_ratio": max_iter_ratio, "bp_method": bp_method,
+                                       "ms_scaling_factor": ms_scaling_factor, "bits_per_step": bits_per_step}
+        self.precision = precision
+        self.device = device
+        self.schedule = schedule
+
+    def GetDecoder(self, code_and_noise_channel_params):
+        p = code_and_noise_channel_params
+        assert "h" in p.keys(), "missing the check matrix h"
+        assert "p_data" in p.keys(), "missing the data error prob: p_data"
+        num_qubits, probs = BP_Decoder_Class._probs(p)
+        d = self.decoder_default_params
+        return BPLSD_Decoder(h=p["h"], channel_probs=probs, max_iter=num_qubits / d["max_iter_ratio"],
+                             bp_method=d["bp_method"], ms_scaling_factor=d["ms_scaling_factor"],
+                             bits_per_step=d["bits_per_step"], precision=self.precision, device=self.device,
                              schedule=self.schedule, side_probs=p.get("side_probs"))
 
 

@@ -522,6 +522,112 @@ class DeviceOSD(_Handle):
                 conv.cpu().numpy().astype(bool), post.cpu().numpy() if host_post else post)
 
 
+class HostLSD(HostOSD):
+    """BP+LSD's second stage on the host (``qldpc_osd_create_lsd``, csrc/lsd.hip): clusters grown
+    around the unsatisfied checks in BP's reliability order, ``bits_per_step`` columns per cluster
+    and round, elimination inside the clusters alone (the law: include/qldpc_hip.h).  A
+    :class:`HostOSD` in every call; it uses no channel weights, so ``osd0 == osdw`` and a side decode
+    equals the plain one."""
+
+    def __init__(self, H, bits_per_step: int = 1):
+        c = H if isinstance(H, CSR) else CSR.from_dense(H)
+        self.m, self.n = c.m, c.n
+        self.osd_method, self.osd_order = 0, 0
+        self.bits_per_step = int(bits_per_step)
+        rp = np.ascontiguousarray(c.row_ptr, dtype=np.int32)
+        ci = np.ascontiguousarray(c.col_idx, dtype=np.int32)
+        self._create("qldpc_osd_create_lsd", self.m, self.n, _np_ptr(rp), _np_ptr(ci), self.bits_per_step)
+        self.rank, = self._ints("qldpc_osd_rank", "qldpc_osd_rank", 1)
+
+    def decode_batch_stats(self, synd, post, conv=None, bp_corr=None, threads: int = 0):
+        """(x [B, n] uint8, stats [B, 4] int32 = valid, rounds, active columns, clusters)."""
+        s = _syndromes(synd, self.m)
+        B = s.shape[0]
+        pst = np.ascontiguousarray(np.asarray(post, dtype=np.float64).reshape(B, self.n))
+        cv = None if conv is None else np.ascontiguousarray(np.asarray(conv).reshape(B), dtype=np.uint8)
+        bc = None if bp_corr is None else np.ascontiguousarray(np.asarray(bp_corr).reshape(B, self.n),
+                                                                 dtype=np.uint8)
+        x = np.zeros((B, self.n), np.uint8)
+        st = np.zeros((B, 4), np.int32)
+        vp = lambda a: None if a is None else _np_ptr(a)  # noqa: E731
+        _native.check(_native.lib().qldpc_lsd_decode_batch_stats(
+            self.handle, vp(s), vp(pst), vp(cv), vp(bc), vp(x), vp(st), B, int(threads)),
+            "qldpc_lsd_decode_batch_stats")
+        return x, st
+
+
+class DeviceLSD(DeviceOSD):
+    """BP+LSD's second stage on the GPU (``qldpc_osd_gpu_create_lsd``): one workgroup per
+    non-converged syndrome, the whole cluster growth and solution inside the kernel.  A
+    :class:`DeviceOSD` in every call (``DeviceMC.set_osd`` / ``set_staged_osd``, the
+    phenomenological and circuit loops, ``bposd_batch``)."""
+
+    MAX_M = 8192
+
+    @staticmethod
+    def supported(m, n) -> bool:  # noqa: D102 (the GPU stage's envelope)
+        return m <= DeviceLSD.MAX_M and n <= DeviceOSD.MAX_N
+
+    def __init__(self, graph: DeviceGraph, bits_per_step: int = 1):
+        self.graph = graph
+        self.osd_method, self.osd_order = 0, 0
+        self.bits_per_step = int(bits_per_step)
+        self._create("qldpc_osd_gpu_create_lsd", graph.handle, self.bits_per_step)
+
+    def geometry(self) -> dict:
+        """:meth:`DeviceOSD.geometry` (``row_words`` = 0) plus ``lds_rows``, the row capacity of the
+        LDS image (0: the image lives in the HBM slice alone), and ``lds_bytes`` per workgroup."""
+        g = super().geometry()
+        g["lds_rows"], g["lds_bytes"] = self._ints("qldpc_lsd_gpu_info", "qldpc_lsd_gpu_info", 2)
+        return g
+
+    def retries(self) -> int:
+        """Decodes since the last call that outgrew the LDS image and were decoded again on the HBM slice
+        (``qldpc_lsd_gpu_retries``; waits for the device)."""
+        v = ctypes.c_uint64()
+        _native.check(_native.lib().qldpc_lsd_gpu_retries(self.handle, ctypes.byref(v)), "qldpc_lsd_gpu_retries")
+        return int(v.value)
+
+    def bplsd_batch_stats(self, bp: "DeviceBP", synd, side=None):
+        """:meth:`DeviceOSD.bposd_batch` through ``qldpc_lsd_gpu_decode``: soft BP, then this stage with
+        its statistics -> (x, stats [B, 4], bp_corr, iters, conv, post as a device tensor)."""
+        torch, dev, sd, corr, iters, conv = _decode_buffers(self.graph, synd, check_width=False)
+        x = torch.empty_like(corr)
+        stats = torch.zeros((sd.shape[0], 4), dtype=torch.int32, device=dev)
+        st = _stream_handle(torch, dev)
+        sb = None if side is None else torch.from_numpy(_side_bytes(side, sd.shape[0], self.graph.n)).to(dev)
+        post = bp._decode_soft_device(sd, corr, iters, conv, st, side=sb)
+        self.decode_device_stats(sd, post, conv, corr, x, stats, st)
+        torch.cuda.synchronize(dev)
+        return (x.cpu().numpy(), stats.cpu().numpy(), corr.cpu().numpy().astype(np.int64), iters.cpu().numpy(),
+                conv.cpu().numpy().astype(bool), post)
+
+    def decode_device_stats(self, synd_dev, post_dev, conv_dev, corr_dev, out_dev, stats_dev, stream=None):
+        _native.check(_native.lib().qldpc_lsd_gpu_decode(
+            self.handle, _ptr(synd_dev), _ptr(post_dev), _ptr(conv_dev), _ptr(corr_dev), _ptr(out_dev),
+            _ptr(stats_dev), int(synd_dev.shape[0]), _stream(stream, synd_dev.device)), "qldpc_lsd_gpu_decode")
+
+    def decode_batch_stats(self, synd, post, conv=None, bp_corr=None):
+        """Host arrays in, (x [B, n] uint8, stats [B, 4] int32) out: :meth:`HostLSD.decode_batch_stats`
+        on the GPU."""
+        torch = _torch()
+        s = _syndromes(synd, self.graph.m)
+        B, n = s.shape[0], self.graph.n
+        dev = torch.device("cuda", self.graph.device)
+
+        def up(a, shape, dtype):
+            return None if a is None else torch.from_numpy(
+                np.ascontiguousarray(np.asarray(a).reshape(shape), dtype=dtype)).to(dev)
+
+        sd, pd = torch.from_numpy(s).to(dev), up(post, (B, n), np.float64)
+        cd, bd = up(conv, (B,), np.uint8), up(bp_corr, (B, n), np.uint8)
+        x = torch.zeros((B, n), dtype=torch.uint8, device=dev)
+        st = torch.zeros((B, 4), dtype=torch.int32, device=dev)
+        self.decode_device_stats(sd, pd, cd, bd, x, st)
+        torch.cuda.synchronize(dev)
+        return x.cpu().numpy(), st.cpu().numpy()
+
+
 class DeviceFirstMin(_Handle):
     """``FirstMinBPDecoder`` (``src/Decoders.py:49-74``) on the GPU (``qldpc_firstmin_*``): one-iteration
     min-sum BP repeated on the running syndrome while its weight does not grow, at most

@@ -383,7 +383,7 @@ class CodeSimulator_DataError(_ShotStream):
         (``qldpc_mc_set_staged_osd``), and the conditional priors of ``pauli_error_probs`` as the side
         tables of the second sector's BP and OSD."""
         from .decoders import channel_update_probs
-        from .engine import DeviceBP, DeviceMC, DeviceOSD, RelayParams
+        from .engine import DeviceBP, DeviceMC, RelayParams
 
         decs = (self.decoder_x, self.decoder_z)
         if any(d.decoder.bp_method != 1 for d in decs):
@@ -410,7 +410,7 @@ class CodeSimulator_DataError(_ShotStream):
                           ms_scaling_factor=sb.ms_scaling_factor, precision=sb.precision, graph=sb.graph,
                           relay=relay, schedule=sb.schedule, soft=relay is None)
         second.set_side_probs(p0, p1)
-        osd2 = DeviceOSD(sb.graph, second_dec.channel_probs, second_dec.osd_method, second_dec.osd_order)
+        osd2 = second_dec.new_gpu_stage(sb.graph)  # a fresh second stage of the decoder's kind (OSD or LSD)
         osd2.set_side_probs(p0, p1)
         osd1 = first_dec.gpu_osd
         mc = DeviceMC(self.code, first if x_first else second, second if x_first else first, staged=True)
