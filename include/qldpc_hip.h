@@ -249,6 +249,51 @@ int qldpc_lsd_gpu_info(const qldpc_osd_gpu *osd, int32_t *lds_rows, int32_t *lds
 int qldpc_lsd_gpu_retries(qldpc_osd_gpu *osd, uint64_t *count);
 
 /*
+ * BP+LSD of higher order (ldpc v2's lsd_order / lsd_method): the clusters grow until each has a few dependent
+ * ("free") columns, and a handful of candidates per cluster is weighed by channel weight.
+ * THE LAW.  Inputs: everything the order-0 law above takes, lsd_method in {0 = "lsd_0", 1 = "lsd_e",
+ * 2 = "lsd_cs"}, lsd_order = w >= 0 and priors p_j in (0, 1).  Order 0, or method 0, is the order-0 law bit
+ * for bit.  Every choice is again a set or a total order.
+ *   weights    : wq_j = floor(log(1 / p_j) 2^32 + 0.5) as a 64-bit integer, computed once on the host with
+ *                std::log (as Relay-BP's wq).  A candidate weighs the sum of wq_j over x_j = 1: an integer
+ *                sum, so any summation order is allowed; uniform priors give popcount order.
+ *   free count : free(C) = |cols(C)| - rank(H[rows(C), cols(C)]).
+ *   round      : a cluster nominates the first min(k, |boundary|) boundary columns in column order when it is
+ *                invalid, or when it is valid and free(C) < w.  Everything else in a round is unchanged (all
+ *                nominated columns join at once, clusters and validity are formed anew, a merge may
+ *                invalidate a cluster).  Rounds end when no nominating cluster has a boundary column.
+ *   split      : on each valid final cluster, walk its columns in column order as OSD-0 does: the kept columns
+ *                P (the pivots) and the free columns F, in column order; each free column f equals a unique
+ *                xor dep(f) of earlier kept columns.
+ *   candidates : candidate 0 is the OSD-0 solution x0.  Later candidates are sets t of free columns with
+ *                x(t) = x0 + sum over f in t of (e_f + dep(f)) (mod 2).  T = the first min(w, |F|) columns
+ *                of F.  lsd_e: all non-empty subsets of T in natural binary order, bit i for T[i].  lsd_cs:
+ *                {f} for every f in F in column order, then {T[a], T[b]} for a < b in lexicographic order.
+ *                The first strictly lighter candidate wins, cluster by cluster.  Unsolvable clusters and
+ *                everything outside A stay 0.
+ *   outputs    : out_osd0 = the union of the candidates 0 on the grown clusters; out_osdw = the union of the
+ *                winners.  Statistics as above (growth rounds count).
+ * lsd_e takes w <= 12, lsd_cs w <= 64.  QLDPC_EINVAL: an order past those, a negative order, an unknown method,
+ * and with an order above 0 in force a prior outside (0, 1) or no priors.
+ * qldpc_osd_create_lsd_order / qldpc_osd_gpu_create_lsd_order: the handles of qldpc_osd_create_lsd /
+ * qldpc_osd_gpu_create_lsd (which mean order 0), served by the same calls.  channel_probs may be NULL at
+ * order 0.  With an order above 0 in force there are no per-shot side tables: qldpc_osd_set_side_probs and
+ * qldpc_osd_gpu_set_side_probs return QLDPC_ENOTSUP.  The GPU stage keeps dep(f) of every free column
+ * beside the image (as many as rows in LDS; a decode with more is taken again on the HBM slice and counted
+ * by qldpc_lsd_gpu_retries) and spreads each cluster's candidates over the workgroup.
+ * A GPU handle of order > 0 keeps 4 m more bytes of tables in LDS than one of order 0: where that exceeds the
+ * 160 KiB of a workgroup (n = 8192 with m above about 7,500) the create call returns QLDPC_ENOTSUP although
+ * the order-0 handle exists.
+ * qldpc_lsd_weights: the handle's wq [n] (QLDPC_EINVAL on a stage created without priors in (0, 1)).
+ */
+int qldpc_osd_create_lsd_order(int32_t m, int32_t n, const int32_t *row_ptr, const int32_t *col_idx,
+                               const double *channel_probs, int32_t bits_per_step, int32_t lsd_method,
+                               int32_t lsd_order, qldpc_osd **out);
+int qldpc_osd_gpu_create_lsd_order(const qldpc_graph *g, const double *channel_probs, int32_t bits_per_step,
+                                   int32_t lsd_method, int32_t lsd_order, qldpc_osd_gpu **out);
+int qldpc_lsd_weights(const qldpc_osd *osd, int64_t *wq);
+
+/*
  * Fused Monte Carlo shot loop = CodeSimulator_DataError._single_run
  * (src/Simulators.py:117-168) for many shots in one launch: per shot sample
  * the Pauli error (3-way split of u, :99-113), syndrome H e, BP decode,

@@ -43,6 +43,7 @@ EXPORTED = [
     "qldpc_osd_gpu_set_side_probs", "qldpc_osd_gpu_decode_side", "qldpc_mc_set_staged_osd",
     "qldpc_osd_create_lsd", "qldpc_lsd_decode_batch_stats", "qldpc_osd_gpu_create_lsd", "qldpc_lsd_gpu_decode",
     "qldpc_lsd_gpu_info", "qldpc_lsd_gpu_retries",
+    "qldpc_osd_create_lsd_order", "qldpc_osd_gpu_create_lsd_order", "qldpc_lsd_weights",
 ]
 COMM_ID_BYTES = 128
 
@@ -295,6 +296,12 @@ def _declare(L):
     L.qldpc_lsd_gpu_info.argtypes = [_vp] + [ctypes.POINTER(_i32)] * 2
     L.qldpc_lsd_gpu_retries.restype = ctypes.c_int
     L.qldpc_lsd_gpu_retries.argtypes = [_vp, ctypes.POINTER(_u64)]
+    L.qldpc_osd_create_lsd_order.restype = ctypes.c_int
+    L.qldpc_osd_create_lsd_order.argtypes = [_i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _pp]
+    L.qldpc_osd_gpu_create_lsd_order.restype = ctypes.c_int
+    L.qldpc_osd_gpu_create_lsd_order.argtypes = [_vp, _vp, _i32, _i32, _i32, _pp]
+    L.qldpc_lsd_weights.restype = ctypes.c_int
+    L.qldpc_lsd_weights.argtypes = [_vp, _vp]
 
 
 def lib():

@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <numeric>
 #include <thread>
@@ -82,6 +83,11 @@ struct LsdWork {
   std::vector<uint8_t> inA, inR, bad;
   std::vector<std::vector<int32_t>> cand;
   std::vector<u64> v, c;
+  // order > 0: free counts by root; the free columns in column order with dep(f) over the kept slots;
+  // the cluster being searched
+  std::vector<int32_t> fre, depcol, fl, pick, best;
+  std::vector<u64> dep;
+  std::vector<uint8_t> done;
   int find(int i) {
     while (parent[i] != i) i = parent[i] = parent[parent[i]];
     return i;
@@ -93,8 +99,12 @@ void lsd_load_col(const qldpc_osd& O, int j, u64* v, int W) {
   for (int r : O.col_rows[j]) v[r >> 6] ^= 1ull << (r & 63);
 }
 
-void lsd_one(const qldpc_osd& O, LsdWork& K, const uint8_t* synd, const double* post, uint8_t* x, int32_t* stats) {
-  const int m = O.m, n = O.n, k = O.lsd_k;
+void lsd_search(const qldpc_osd& O, LsdWork& K, int CW, uint8_t* x);
+
+// x0 (or null): the union of the candidates 0; x: the union of the winners
+void lsd_one(const qldpc_osd& O, LsdWork& K, const uint8_t* synd, const double* post, uint8_t* x0, uint8_t* x,
+             int32_t* stats) {
+  const int m = O.m, n = O.n, k = O.lsd_k, w = O.lsd_w;
   const int W = (m + 63) / 64;
   std::fill(x, x + n, (uint8_t)0);
   K.order.resize(n);
@@ -121,11 +131,22 @@ void lsd_one(const qldpc_osd& O, LsdWork& K, const uint8_t* synd, const double* 
   int rounds = 0;
   if (!K.R.empty())
     for (;;) {
-      // the invalid clusters, by root
+      // the nominating clusters, by root: the invalid ones, and the valid ones with fewer than w free
+      // columns (columns less basis vectors: the rank of a cluster does not depend on the insertion order)
       bool any = false;
       for (int i : K.R) K.bad[K.find(i)] = 0;
       for (int i : K.R)
         if (LsdBasis::bit(K.B.sred.data(), i)) K.bad[K.find(i)] = 1, any = true;
+      if (w > 0) {
+        K.fre.resize(m);
+        for (int i : K.R) K.fre[K.find(i)] = 0;
+        for (int j : K.A) ++K.fre[K.find(O.col_rows[j][0])];
+        for (int p : K.B.piv) --K.fre[K.find(p)];
+        for (int i : K.R) {
+          const int r = K.find(i);
+          if (!K.bad[r] && K.fre[r] < w) K.bad[r] = 2, any = true;
+        }
+      }
       if (!any) break;
       // their boundaries, and the first k of each in column order
       for (int i : K.R) K.cand[K.find(i)].clear();
@@ -174,22 +195,91 @@ void lsd_one(const qldpc_osd& O, LsdWork& K, const uint8_t* synd, const double* 
     if (synd[i] & 1u) F.sred[i >> 6] |= 1ull << (i & 63);
   K.c.resize(std::max(CW, 1));
   K.kept.clear();
+  K.depcol.clear();
+  K.dep.clear();
   for (int j : K.A) {
     lsd_load_col(O, j, K.v.data(), W);
     std::fill(K.c.begin(), K.c.end(), 0ull);
     const int t = (int)K.kept.size();
     if (t < CW * 64) K.c[t >> 6] |= 1ull << (t & 63);
-    if (F.insert(K.v.data(), K.c.data())) K.kept.push_back(j);
+    if (F.insert(K.v.data(), K.c.data())) {
+      K.kept.push_back(j);
+    } else if (w > 0) {  // a free column: what is left of its combination is dep(f)
+      if (t < CW * 64) K.c[t >> 6] &= ~(1ull << (t & 63));
+      K.depcol.push_back(j);
+      K.dep.insert(K.dep.end(), K.c.begin(), K.c.begin() + CW);
+    }
   }
   for (int t = 0; t < (int)K.kept.size(); ++t) {
     const int j = K.kept[t];
     if (LsdBasis::bit(F.scomb.data(), t) && !K.bad[K.find(O.col_rows[j][0])]) x[j] = 1;
   }
+  if (x0) std::copy(x, x + n, x0);
+  if (w > 0 && !K.depcol.empty()) lsd_search(O, K, CW, x);
   if (stats) {
     stats[0] = valid;
     stats[1] = rounds;
     stats[2] = (int32_t)K.A.size();
     stats[3] = ncl;
+  }
+}
+
+// The candidate search of order w > 0 on every valid final cluster, one after another: the cluster's free
+// columns F in column order (the re-insertion met them in that order), T = the first min(w, |F|), the
+// candidates of the method in the law's order.  A candidate is weighed by its difference to candidate 0,
+// sum wq over t plus, over the kept slots of xor dep(f), -wq where x0 is set and +wq where it is not: an
+// integer, so the comparison is that of the full weights.  x holds x0 on entry and the winners on return.
+void lsd_search(const qldpc_osd& O, LsdWork& K, int CW, uint8_t* x) {
+  const int w = O.lsd_w, nf = (int)K.depcol.size();
+  const long long* wq = O.lsd_wq.data();
+  const u64* x0 = K.B.scomb.data();
+  auto root = [&](int e) { return K.find(O.col_rows[K.depcol[e]][0]); };
+  auto delta = [&](const std::vector<int32_t>& t) {
+    long long d = 0;
+    for (int e : t) d += wq[K.depcol[e]];
+    for (int q = 0; q < CW; ++q) {
+      u64 D = 0;
+      for (int e : t) D ^= K.dep[(size_t)e * CW + q];
+      for (; D; D &= D - 1) {
+        const int b = __builtin_ctzll(D);
+        const long long wt = wq[K.kept[q * 64 + b]];
+        d += ((x0[q] >> b) & 1ull) ? -wt : wt;
+      }
+    }
+    return d;
+  };
+  K.done.assign(O.m, 0);
+  for (int e0 = 0; e0 < nf; ++e0) {
+    const int r = root(e0);
+    if (K.bad[r] || K.done[r]) continue;
+    K.done[r] = 1;
+    K.fl.clear();
+    for (int e = e0; e < nf; ++e)
+      if (root(e) == r) K.fl.push_back(e);
+    const int nF = (int)K.fl.size(), T = std::min(w, nF);
+    long long bw = 0;
+    K.best.clear();
+    auto weigh = [&]() {
+      const long long d = delta(K.pick);
+      if (d < bw) bw = d, K.best = K.pick;
+    };
+    if (O.lsd_method == 1) {
+      for (uint32_t c = 1; c < (1u << T); ++c) {
+        K.pick.clear();
+        for (int i = 0; i < T; ++i)
+          if ((c >> i) & 1u) K.pick.push_back(K.fl[i]);
+        weigh();
+      }
+    } else {
+      for (int a = 0; a < nF; ++a) K.pick.assign(1, K.fl[a]), weigh();
+      for (int a = 0; a < T; ++a)
+        for (int b = a + 1; b < T; ++b) K.pick.assign({K.fl[a], K.fl[b]}), weigh();
+    }
+    for (int e : K.best) {
+      x[K.depcol[e]] = 1;
+      for (int q = 0; q < CW; ++q)
+        for (u64 D = K.dep[(size_t)e * CW + q]; D; D &= D - 1) x[K.kept[q * 64 + __builtin_ctzll(D)]] ^= 1;
+    }
   }
 }
 
@@ -236,8 +326,8 @@ int qldpc_rt::lsd_decode_batch_host(const qldpc_osd* osd, const uint8_t* synd, c
     LsdWork K;
     for (size_t a = t; a < todo.size(); a += T) {
       const int64_t b = todo[a];
-      lsd_one(*osd, K, synd + b * m, post + b * n, out_osdw + b * n, stats ? stats + 4 * b : nullptr);
-      if (out_osd0) std::copy(out_osdw + b * n, out_osdw + (b + 1) * n, out_osd0 + b * n);
+      lsd_one(*osd, K, synd + b * m, post + b * n, out_osd0 ? out_osd0 + b * n : nullptr, out_osdw + b * n,
+              stats ? stats + 4 * b : nullptr);
     }
   };
   if (T == 1) {
@@ -252,13 +342,31 @@ int qldpc_rt::lsd_decode_batch_host(const qldpc_osd* osd, const uint8_t* synd, c
 
 extern "C" {
 
-int qldpc_osd_create_lsd(int32_t m, int32_t n, const int32_t* row_ptr, const int32_t* col_idx,
-                         int32_t bits_per_step, qldpc_osd** out) {
+int qldpc_osd_create_lsd_order(int32_t m, int32_t n, const int32_t* row_ptr, const int32_t* col_idx,
+                               const double* channel_probs, int32_t bits_per_step, int32_t lsd_method,
+                               int32_t lsd_order, qldpc_osd** out) {
   if (!row_ptr || !out) return set_err(QLDPC_EINVAL, "NULL argument");
   if (m < 0 || n <= 0) return set_err(QLDPC_EINVAL, "bad matrix shape");
   if (!col_idx && row_ptr[m] > 0) return set_err(QLDPC_EINVAL, "NULL argument");
   if (bits_per_step < 1) return set_err(QLDPC_EINVAL, "bits_per_step must be >= 1");
+  if (lsd_method < 0 || lsd_method > 2)
+    return set_err(QLDPC_EINVAL, "lsd_method must be 0 (lsd_0), 1 (lsd_e) or 2 (lsd_cs)");
+  if (lsd_order < 0 || (lsd_method == 1 && lsd_order > 12) || (lsd_method == 2 && lsd_order > 64))
+    return set_err(QLDPC_EINVAL, "lsd_order must be >= 0, <= 12 for lsd_e and <= 64 for lsd_cs");
+  const int w = lsd_method ? lsd_order : 0;
+  bool priors = channel_probs != nullptr;
+  for (int j = 0; priors && j < n; ++j) priors = channel_probs[j] > 0.0 && channel_probs[j] < 1.0;
+  if (w > 0 && !priors) return set_err(QLDPC_EINVAL, "LSD of order > 0 needs channel_probs in (0, 1)");
   auto* O = new qldpc_osd();
+  O->lsd_method = w ? lsd_method : 0;
+  O->lsd_w = w;
+  if (priors) {
+    O->lsd_wq.resize(n);
+    for (int j = 0; j < n; ++j) {
+      const double q = std::floor(std::log(1.0 / channel_probs[j]) * 4294967296.0 + 0.5);
+      O->lsd_wq[j] = q < 5.6e14 ? (long long)q : (1LL << 49);  // (1 / p overflows for a denormal p)
+    }
+  }
   O->m = m;
   O->n = n;
   O->method = 0;
@@ -276,9 +384,21 @@ int qldpc_osd_create_lsd(int32_t m, int32_t n, const int32_t* row_ptr, const int
       }
       O->col_rows[j].push_back(i);
     }
-  O->w.assign(n, 0.0);  // LSD of order 0 weighs no candidates
+  O->w.assign(n, 0.0);  // the OSD weights stay unused: LSD weighs its candidates by lsd_wq
   O->rank = lsd_rank(*O);
   *out = O;
+  return 0;
+}
+
+int qldpc_osd_create_lsd(int32_t m, int32_t n, const int32_t* row_ptr, const int32_t* col_idx,
+                         int32_t bits_per_step, qldpc_osd** out) {
+  return qldpc_osd_create_lsd_order(m, n, row_ptr, col_idx, nullptr, bits_per_step, 0, 0, out);
+}
+
+int qldpc_lsd_weights(const qldpc_osd* osd, int64_t* wq) {
+  if (!osd || !osd->lsd_k || !wq) return set_err(QLDPC_EINVAL, "not an LSD stage, or NULL argument");
+  if (osd->lsd_wq.empty()) return set_err(QLDPC_EINVAL, "the stage was created without channel_probs in (0, 1)");
+  std::copy(osd->lsd_wq.begin(), osd->lsd_wq.end(), wq);
   return 0;
 }
 
@@ -319,13 +439,14 @@ constexpr uint32_t kInf = 0xFFFFFFFFu;
 constexpr size_t kLdsMax = (size_t)160 * 1024;
 
 struct LsdLay {
-  int rank16, rlabel, nom, prev, rslot, acols, inA, pend, posb, inR, inv, scan, vbuf, sred, ctl, img;
+  int rank16, rlabel, nom, prev, rslot, acols, inA, pend, posb, inR, inv, scan, vbuf, sred, ctl, fre, img;
   size_t sort_end;
 };
 
 inline size_t al16(size_t x) { return (x + 15) & ~(size_t)15; }
 
-LsdLay lsd_layout(int m, int n, int NP) {
+// ord: a handle of order > 0, which also counts free columns per label (fre)
+LsdLay lsd_layout(int m, int n, int NP, bool ord) {
   LsdLay L;
   const int RWh = (m + 63) / 64 > 0 ? (m + 63) / 64 : 1;
   size_t o = 0;
@@ -346,21 +467,27 @@ LsdLay lsd_layout(int m, int n, int NP) {
   L.vbuf = (int)o; o = al16(o + (size_t)RWh * 16);
   L.sred = (int)o; o = al16(o + (size_t)RWh * 16);
   L.ctl = (int)o; o = al16(o + 64);
+  L.fre = (int)o; o = al16(o + (ord ? (size_t)m * 4 : 0));
   L.img = (int)o;
   return L;
 }
 
-// bytes of an image of row capacity cap (a multiple of 64)
-inline size_t lsd_img_bytes(int cap) { return (((size_t)cap * 6 + 15) & ~(size_t)15) + (size_t)cap * (cap / 64) * 16; }
+// bytes of an image of row capacity cap (a multiple of 64) that keeps dcap dep vectors (order > 0: cap / 64
+// words and a 16-bit column each, behind the basis vectors; 0 at order 0)
+inline size_t lsd_img_bytes(int cap, int dcap) {
+  return (((size_t)cap * 6 + 15) & ~(size_t)15) + (size_t)cap * (cap / 64) * 16 + (size_t)dcap * (cap / 64) * 8 +
+         al16((size_t)dcap * 2);
+}
 
-inline size_t lsd_lds_total(const LsdLay& L, int cap) {
-  return std::max(L.sort_end, (size_t)L.img + (cap ? lsd_img_bytes(cap) : 0));
+// the LDS image keeps as many dep vectors as rows; more free columns than that take the HBM slice (n of them)
+inline size_t lsd_lds_total(const LsdLay& L, int cap, bool ord) {
+  return std::max(L.sort_end, (size_t)L.img + (cap ? lsd_img_bytes(cap, ord ? cap : 0) : 0));
 }
 
 // largest row capacity (multiple of 64, <= m rounded up) whose workgroup fits the budget
-int lsd_cap_fit(const LsdLay& L, int m, size_t budget) {
+int lsd_cap_fit(const LsdLay& L, int m, size_t budget, bool ord) {
   for (int cap = (m + 63) / 64 * 64; cap >= 64; cap -= 64)
-    if (lsd_lds_total(L, cap) <= budget) return cap;
+    if (lsd_lds_total(L, cap, ord) <= budget) return cap;
   return 0;
 }
 
@@ -378,6 +505,9 @@ struct LsdArgs {
   long long ws_bytes, B;
   int m, n, NP, k, cap_l, cap_h;
   LsdLay L;
+  // order > 0: wq [n] (read-only, global), the method (1 lsd_e, 2 lsd_cs), the order, dep vectors per image
+  const long long* wq;
+  int method, w, dcap_l, dcap_h;
 };
 
 __device__ inline u64 lsd_ord_key(double x) {
@@ -386,7 +516,7 @@ __device__ inline u64 lsd_ord_key(double x) {
   return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
 }
 
-enum { C_NR = 0, C_NNEW, C_CH, C_NOM, C_UNS, C_NCL };
+enum { C_NR = 0, C_NNEW, C_CH, C_NOM, C_UNS, C_NCL, C_NF };
 
 struct LsdCtx {
   const LsdArgs* A;
@@ -398,19 +528,30 @@ struct LsdCtx {
   u64* vec;
   int cap, S;  // S: words of a vector's row part = of its combination part
   int nvec, RW, CW;
+  // order > 0: free columns per label; the free columns of the solution pass in column order, dep(f) over
+  // the kept slots (S words each)
+  uint32_t* fre;
+  u64* dep;
+  uint16_t* depcol;
+  int dcap, nf;
 };
 
 __device__ inline bool bit32(const uint32_t* b, int i) { return (b[i >> 5] >> (i & 31)) & 1u; }
 
-// Insert column c; tag >= 0: the solution pass (combination bit tag, kept column recorded).  Uniform.
-__device__ void lsd_insert(LsdCtx& X, int c, bool comb) {
+// Insert column c; comb: the solution pass (combination bit, kept column recorded; ORD: a dependent column
+// leaves its combination of kept columns as a dep vector).  Uniform.
+template <bool ORD>
+__device__ __forceinline__ void lsd_insert(LsdCtx& X, int c, bool comb) {
   const int tid = threadIdx.x, TB = kLsdThreads;
   const int S = X.S, RW = X.RW, nvec = X.nvec, VS = 2 * S;
   const int32_t* cp = X.A->cp;
   const int32_t* ce = X.A->ce;
   __syncthreads();  // the previous insertion's readers of vbuf / sred are done
-  if (nvec >= X.cap) return;  // full rank on every row the image can hold: the column is dependent
-  if (comb && (nvec >> 6) + 1 > X.CW) {  // a new combination word: zero it in the older vectors
+  // full rank on every row the image can hold: the column is dependent (ORD: its dep is still wanted; it
+  // takes no combination bit of its own)
+  const bool full = nvec >= X.cap;
+  if (full && !(ORD && comb)) return;
+  if (comb && !full && (nvec >> 6) + 1 > X.CW) {  // a new combination word: zero it in the older vectors
     for (int i = tid; i < nvec; i += TB) X.vec[(size_t)i * VS + S + X.CW] = 0;
     if (tid == 0) X.sred[S + X.CW] = 0;
     X.CW += 1;
@@ -424,7 +565,7 @@ __device__ void lsd_insert(LsdCtx& X, int c, bool comb) {
     const int s = X.rslot[ce[e]];
     atomicOr(&v32[s >> 5], 1u << (s & 31));
   }
-  if (comb && tid == 0) X.vbuf[S + (nvec >> 6)] = 1ull << (nvec & 63);
+  if (comb && !full && tid == 0) X.vbuf[S + (nvec >> 6)] = 1ull << (nvec & 63);
   __syncthreads();
   // reduce by the vectors whose pivot bit the column has (tested before any xor lands)
   uint32_t hit = 0;
@@ -450,7 +591,21 @@ __device__ void lsd_insert(LsdCtx& X, int c, bool comb) {
       break;
     }
   }
-  if (p < 0) return;  // dependent on the basis (uniform)
+  if (p < 0) {  // dependent on the basis (uniform)
+    if (ORD && comb) {
+      const int f = X.nf;
+      X.nf = f + 1;  // counted past dcap too: the decode is then taken again on the HBM slice
+      if (f < X.dcap) {
+        for (int q = tid; q < S; q += TB) {
+          u64 d = q < CW ? X.vbuf[S + q] : 0ull;
+          if (!full && q == (nvec >> 6)) d &= ~(1ull << (nvec & 63));
+          X.dep[(size_t)f * S + q] = d;
+        }
+        if (tid == 0) X.depcol[f] = (uint16_t)c;
+      }
+    }
+    return;
+  }
   const bool sp = (X.sred[p >> 6] >> (p & 63)) & 1ull;
   __syncthreads();
   for (int i = tid; i < nvec; i += TB) {
@@ -484,10 +639,117 @@ __device__ inline void lsd_seed_syndrome(LsdCtx& X, int ns, int RW) {
   }
 }
 
-// One syndrome on the image at `img` of row capacity cap.  false: the active rows outgrew cap (nothing
-// was written).  Uniform over the workgroup.
-__device__ bool lsd_decode(LsdCtx& X, unsigned char* img, int cap, const uint8_t* synd, uint8_t* ow, uint8_t* o0,
-                           int32_t* stats) {
+// The dep entries of candidate c (1-based, the law's order) of a cluster with nF free columns, T of them in
+// the search set: lsd_e (method 1) sets bit i of `mask` for T[i]; lsd_cs gives one or two positions e0 < e1
+// of the cluster's list (e1 < 0: a single).
+__device__ inline void lsd_candidate(int method, int c, int nF, int T, uint32_t& mask, int& e0, int& e1) {
+  mask = 0;
+  e0 = e1 = -1;
+  if (method == 1) {
+    mask = (uint32_t)c;
+  } else if (c <= nF) {
+    e0 = c - 1;
+  } else {
+    int r = c - nF - 1, a = 0;
+    while (r >= T - 1 - a) r -= T - 1 - a, ++a;
+    e0 = a;
+    e1 = a + 1 + r;
+  }
+}
+
+// xor of word q of the candidate's dep vectors; fl: the cluster's entries in column order
+__device__ inline u64 lsd_cand_word(const LsdCtx& X, const uint16_t* fl, uint32_t mask, int e0, int e1, int q) {
+  u64 D = 0;
+  for (uint32_t mm = mask; mm; mm &= mm - 1) D ^= X.dep[(size_t)fl[__builtin_ctz(mm)] * X.S + q];
+  if (e0 >= 0) D ^= X.dep[(size_t)fl[e0] * X.S + q];
+  if (e1 >= 0) D ^= X.dep[(size_t)fl[e1] * X.S + q];
+  return D;
+}
+
+// The candidate search (order > 0) after the solution pass: the valid clusters that have a free column, one
+// after another in the order of their first free column.  Thread 0 lists the cluster's free columns (they
+// lie in column order in dep); the candidates are spread over the threads, each weighed by its difference to
+// candidate 0 (sum wq over its free columns, and over the kept slots of its xor of dep vectors -wq where
+// candidate 0 is set, +wq where it is not), and reduced to (least difference, least index): candidate 0 has
+// (0, 0), so only a strictly lighter candidate replaces it and the first of equals wins.  The winner's xor
+// goes into the comb part of vbuf, its free columns into pend.  nom[L] = 0 marks a cluster as searched
+// (every word of nom is kInf after the rounds).  Uniform; ends with a barrier.
+__device__ __forceinline__ void lsd_search(LsdCtx& X) {
+  const LsdArgs& A = *X.A;
+  const int tid = threadIdx.x, TB = kLsdThreads;
+  const int nf = X.nf, S = X.S, CW = X.CW;
+  uint16_t* fl = X.acols;  // (the solution pass was the last reader of acols)
+  long long* red = reinterpret_cast<long long*>(X.scan);
+  for (int i0 = 0; i0 < nf; ++i0) {
+    const uint32_t L = X.rlabel[A.ce[A.cp[X.depcol[i0]]]];
+    const bool skip = bit32(X.inv, (int)L) || X.nom[L] != kInf;
+    __syncthreads();  // every thread has read nom[L] and is done with the cluster before
+    if (skip) continue;
+    if (tid == 0) {
+      int cnt = 0;
+      for (int i = i0; i < nf; ++i)
+        if (X.rlabel[A.ce[A.cp[X.depcol[i]]]] == L) fl[cnt++] = (uint16_t)i;
+      X.ctl[C_NF] = (uint32_t)cnt;
+      X.nom[L] = 0;
+    }
+    __syncthreads();
+    const int nF = (int)X.ctl[C_NF], T = min(A.w, nF);
+    const int ncand = A.method == 1 ? (1 << T) - 1 : nF + T * (T - 1) / 2;
+    long long bw = 0;
+    int bc = 0;
+    for (int c = 1 + tid; c <= ncand; c += TB) {
+      uint32_t mask;
+      int e0, e1;
+      lsd_candidate(A.method, c, nF, T, mask, e0, e1);
+      long long d = 0;
+      for (uint32_t mm = mask; mm; mm &= mm - 1) d += A.wq[X.depcol[fl[__builtin_ctz(mm)]]];
+      if (e0 >= 0) d += A.wq[X.depcol[fl[e0]]];
+      if (e1 >= 0) d += A.wq[X.depcol[fl[e1]]];
+      for (int q = 0; q < CW; ++q) {
+        const u64 x0 = X.sred[S + q];
+        for (u64 D = lsd_cand_word(X, fl, mask, e0, e1, q); D; D &= D - 1) {
+          const int b = __builtin_ctzll(D);
+          const long long wt = A.wq[X.keptcol[q * 64 + b]];
+          d += ((x0 >> b) & 1ull) ? -wt : wt;
+        }
+      }
+      if (d < bw) bw = d, bc = c;  // c ascends: the first of a thread's equals stays
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+      const long long ow_ = __shfl_xor(bw, off);
+      const int oc = __shfl_xor(bc, off);
+      if (ow_ < bw || (ow_ == bw && oc < bc)) bw = ow_, bc = oc;
+    }
+    if ((tid & 63) == 0) red[2 * (tid >> 6)] = bw, red[2 * (tid >> 6) + 1] = bc;
+    __syncthreads();
+    for (int v = 0; v < TB / 64; ++v) {
+      const long long ow_ = red[2 * v];
+      const int oc = (int)red[2 * v + 1];
+      if (ow_ < bw || (ow_ == bw && oc < bc)) bw = ow_, bc = oc;
+    }
+    if (bc) {
+      uint32_t mask;
+      int e0, e1;
+      lsd_candidate(A.method, bc, nF, T, mask, e0, e1);
+      for (int q = tid; q < CW; q += TB) X.vbuf[S + q] ^= lsd_cand_word(X, fl, mask, e0, e1, q);
+      if (tid == 0) {
+        for (uint32_t mm = mask; mm; mm &= mm - 1) {
+          const int f = X.depcol[fl[__builtin_ctz(mm)]];
+          X.pend[f >> 5] |= 1u << (f & 31);
+        }
+        if (e0 >= 0) X.pend[X.depcol[fl[e0]] >> 5] |= 1u << (X.depcol[fl[e0]] & 31);
+        if (e1 >= 0) X.pend[X.depcol[fl[e1]] >> 5] |= 1u << (X.depcol[fl[e1]] & 31);
+      }
+    }
+  }
+  __syncthreads();
+}
+
+// One syndrome on the image at `img` of row capacity cap and dcap dep vectors.  false: the active rows
+// outgrew cap, or the free columns dcap (nothing was written).  Uniform over the workgroup.
+template <bool ORD>
+__device__ __forceinline__ bool lsd_decode(LsdCtx& X, unsigned char* img, int cap, int dcap, const uint8_t* synd, uint8_t* ow,
+                           uint8_t* o0, int32_t* stats) {
   const LsdArgs& A = *X.A;
   const int tid = threadIdx.x, TB = kLsdThreads;
   const int m = A.m, n = A.n, k = A.k;
@@ -497,6 +759,12 @@ __device__ bool lsd_decode(LsdCtx& X, unsigned char* img, int cap, const uint8_t
   X.keptcol = X.slotrow + cap;
   X.piv = X.keptcol + cap;
   X.vec = reinterpret_cast<u64*>(img + (((size_t)cap * 6 + 15) & ~(size_t)15));
+  if (ORD) {
+    X.dep = X.vec + (size_t)cap * 2 * X.S;
+    X.depcol = reinterpret_cast<uint16_t*>(X.dep + (size_t)dcap * X.S);
+    X.dcap = dcap;
+    X.nf = 0;
+  }
   const int nbw = (n + 31) / 32, mbw = (m + 31) / 32;
   __syncthreads();
   for (int i = tid; i < m; i += TB) {
@@ -557,13 +825,27 @@ __device__ bool lsd_decode(LsdCtx& X, unsigned char* img, int cap, const uint8_t
     // invalid clusters; every cluster may pick from rank 0 again
     for (int q = tid; q < mbw; q += TB) X.inv[q] = 0;
     for (int q = tid; q < nbw; q += TB) X.pend[q] = 0;
-    for (int s = tid; s < nR; s += TB) X.prev[X.slotrow[s]] = 0;
+    for (int s = tid; s < nR; s += TB) {
+      X.prev[X.slotrow[s]] = 0;
+      if (ORD) X.fre[X.slotrow[s]] = 0;
+    }
     __syncthreads();
     for (int s = tid; s < nR; s += TB)
       if ((X.sred[s >> 6] >> (s & 63)) & 1ull) {
         const uint32_t L = X.rlabel[X.slotrow[s]];
         atomicOr(&X.inv[L >> 5], 1u << (L & 31));
       }
+    if (ORD) {
+      // free(C) by label: active columns less basis vectors; a valid cluster with fewer than w nominates too
+      // (inv holds the nominating labels until the round ends; it is formed anew after the last one)
+      for (int a = tid; a < nA; a += TB) atomicAdd(&X.fre[X.rlabel[A.ce[A.cp[X.acols[a]]]]], 1u);
+      for (int i = tid; i < X.nvec; i += TB) atomicSub(&X.fre[X.rlabel[X.slotrow[X.piv[i]]]], 1u);
+      __syncthreads();
+      for (int s = tid; s < nR; s += TB) {
+        const uint32_t L = X.rlabel[X.slotrow[s]];
+        if ((int)X.fre[L] < A.w) atomicOr(&X.inv[L >> 5], 1u << (L & 31));
+      }
+    }
     __syncthreads();
     for (int pass = 0; pass < k; ++pass) {
       for (int s = tid; s < nR; s += TB) {
@@ -625,7 +907,7 @@ __device__ bool lsd_decode(LsdCtx& X, unsigned char* img, int cap, const uint8_t
       X.RW = RWn;
     }
     if (tid == 0) X.ctl[C_NNEW] = 0;
-    for (int a = nA; a < nA + nnew; ++a) lsd_insert(X, X.acols[a], false);
+    for (int a = nA; a < nA + nnew; ++a) lsd_insert<ORD>(X, X.acols[a], false);
     nA += nnew;
     __syncthreads();
   }
@@ -663,8 +945,9 @@ __device__ bool lsd_decode(LsdCtx& X, unsigned char* img, int cap, const uint8_t
   X.nvec = 0;
   X.CW = 0;
   lsd_seed_syndrome(X, ns, X.RW);
-  for (int a = 0; a < nA; ++a) lsd_insert(X, X.acols[a], true);
+  for (int a = 0; a < nA; ++a) lsd_insert<ORD>(X, X.acols[a], true);
   __syncthreads();
+  if (ORD && X.nf > X.dcap) return false;
   // clusters still inconsistent are unsolvable: x = 0 on them
   for (int q = tid; q < mbw; q += TB) X.inv[q] = 0;
   __syncthreads();
@@ -677,19 +960,42 @@ __device__ bool lsd_decode(LsdCtx& X, unsigned char* img, int cap, const uint8_t
       X.ctl[C_UNS] = 1;
     }
   }
-  for (int j = tid; j < n; j += TB) {
-    ow[j] = 0;
-    if (o0) o0[j] = 0;
-  }
-  __syncthreads();
-  for (int t = tid; t < X.nvec; t += TB)
-    if ((X.sred[X.S + (t >> 6)] >> (t & 63)) & 1ull) {
+  if (ORD) {
+    // the winners: the kept slots start as candidate 0 (the comb part of vbuf is free now), the winning free
+    // columns are collected in pend; the clusters are then searched one after another
+    for (int q = tid; q < X.CW; q += TB) X.vbuf[X.S + q] = X.sred[X.S + q];
+    for (int q = tid; q < nbw; q += TB) X.pend[q] = 0;
+    __syncthreads();
+    if (X.nf > 0) lsd_search(X);
+    for (int j = tid; j < n; j += TB) {
+      ow[j] = bit32(X.pend, j) ? 1 : 0;
+      if (o0) o0[j] = 0;
+    }
+    __syncthreads();
+    for (int t = tid; t < X.nvec; t += TB) {
+      const bool b0 = (X.sred[X.S + (t >> 6)] >> (t & 63)) & 1ull, bw = (X.vbuf[X.S + (t >> 6)] >> (t & 63)) & 1ull;
+      if (!b0 && !bw) continue;
       const int c = X.keptcol[t];
       if (!bit32(X.inv, (int)X.rlabel[A.ce[A.cp[c]]])) {
-        ow[c] = 1;
-        if (o0) o0[c] = 1;
+        if (bw) ow[c] = 1;
+        if (o0 && b0) o0[c] = 1;
       }
     }
+  } else {
+    for (int j = tid; j < n; j += TB) {
+      ow[j] = 0;
+      if (o0) o0[j] = 0;
+    }
+    __syncthreads();
+    for (int t = tid; t < X.nvec; t += TB)
+      if ((X.sred[X.S + (t >> 6)] >> (t & 63)) & 1ull) {
+        const int c = X.keptcol[t];
+        if (!bit32(X.inv, (int)X.rlabel[A.ce[A.cp[c]]])) {
+          ow[c] = 1;
+          if (o0) o0[c] = 1;
+        }
+      }
+  }
   if (stats && tid == 0) {
     stats[0] = X.ctl[C_UNS] ? 0 : 1;
     stats[1] = rounds;
@@ -699,6 +1005,7 @@ __device__ bool lsd_decode(LsdCtx& X, unsigned char* img, int cap, const uint8_t
   return true;
 }
 
+template <bool ORD>
 __global__ void __launch_bounds__(kLsdThreads) lsd_gpu_kernel(LsdArgs A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, TB = kLsdThreads;
@@ -720,6 +1027,7 @@ __global__ void __launch_bounds__(kLsdThreads) lsd_gpu_kernel(LsdArgs A) {
   X.vbuf = reinterpret_cast<u64*>(smem + A.L.vbuf);
   X.sred = reinterpret_cast<u64*>(smem + A.L.sred);
   X.ctl = reinterpret_cast<uint32_t*>(smem + A.L.ctl);
+  if (ORD) X.fre = reinterpret_cast<uint32_t*>(smem + A.L.fre);
   u64* skey = reinterpret_cast<u64*>(smem + A.L.rlabel);  // the sort tables, under the state tables
   int32_t* sidx = reinterpret_cast<int32_t*>(skey + NP);
   unsigned char* gimg = A.ws + (size_t)blockIdx.x * A.ws_bytes;
@@ -764,10 +1072,10 @@ __global__ void __launch_bounds__(kLsdThreads) lsd_gpu_kernel(LsdArgs A) {
     for (int q = tid; q < n; q += TB) X.rank16[sidx[q]] = (uint16_t)q;
     // (lsd_decode opens with a barrier before it writes the tables over the sort)
     bool done = false;
-    if (A.cap_l) done = lsd_decode(X, smem + A.L.img, A.cap_l, synd, ow, o0, stats);
+    if (A.cap_l) done = lsd_decode<ORD>(X, smem + A.L.img, A.cap_l, A.dcap_l, synd, ow, o0, stats);
     if (!done) {
       if (A.cap_l && tid == 0) atomicAdd(A.retries, 1ull);
-      lsd_decode(X, gimg, A.cap_h, synd, ow, o0, stats);
+      lsd_decode<ORD>(X, gimg, A.cap_h, A.dcap_h, synd, ow, o0, stats);
     }
   }
 }
@@ -785,19 +1093,20 @@ int qldpc_rt::lsd_gpu_from_host(const qldpc_graph* g, const qldpc_osd* O, qldpc_
   const int m = g->m, n = g->n;
   G->NP = 1;
   while (G->NP < n) G->NP <<= 1;
-  const LsdLay L = lsd_layout(m, n, G->NP);
+  const bool ord = O->lsd_w > 0;
+  const LsdLay L = lsd_layout(m, n, G->NP, ord);
   // the LDS image: within 64 KiB per workgroup (two or more workgroups per CU) when that holds every row
   // or at least 128 of them, else up to 128 rows in a workgroup of any size; QLDPC_LSD_WS=1: HBM alone
   const char* ws_env = std::getenv("QLDPC_LSD_WS");
   int cap = 0;
   if (!(ws_env && std::atoi(ws_env) == 1) && m > 0) {
-    cap = lsd_cap_fit(L, m, (size_t)64 * 1024);
-    if (cap < 128 && cap < (m + 63) / 64 * 64) cap = std::min(lsd_cap_fit(L, m, kLdsMax), 128);
+    cap = lsd_cap_fit(L, m, (size_t)64 * 1024, ord);
+    if (cap < 128 && cap < (m + 63) / 64 * 64) cap = std::min(lsd_cap_fit(L, m, kLdsMax, ord), 128);
   }
   G->lsd_cap = cap;
-  G->lds = lsd_lds_total(L, cap);
+  G->lds = lsd_lds_total(L, cap, ord);
   const int cap_h = std::max(64, (m + 63) / 64 * 64);
-  G->ws_words = (long long)(lsd_img_bytes(cap_h) / 8);
+  G->ws_words = (long long)((lsd_img_bytes(cap_h, ord ? n : 0) + 7) / 8);
   auto fail = [&](int code) {
     qldpc_osd_gpu_destroy(G);
     return code;
@@ -808,8 +1117,9 @@ int qldpc_rt::lsd_gpu_from_host(const qldpc_graph* g, const qldpc_osd* O, qldpc_
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, g->device) != hipSuccess || cus <= 0)
     return fail(set_err(QLDPC_EHIP, "device CU count"));
   int nb = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(&lsd_gpu_kernel), kLsdThreads,
-                                                   G->lds) != hipSuccess || nb <= 0)
+  const void* kern = ord ? reinterpret_cast<const void*>(&lsd_gpu_kernel<true>)
+                         : reinterpret_cast<const void*>(&lsd_gpu_kernel<false>);
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, kLsdThreads, G->lds) != hipSuccess || nb <= 0)
     nb = 1;
   // the HBM slices (every workgroup has one: the LDS image's overflow route) within 256 MiB
   const long long slice = G->ws_words * 8;
@@ -823,8 +1133,11 @@ int qldpc_rt::lsd_gpu_from_host(const qldpc_graph* g, const qldpc_osd* O, qldpc_
   int rc = 0;
   if ((rc = G->rp.alloc((size_t)(m + 1) * 4)) || (rc = G->ci.alloc(std::max<size_t>(E, 1) * 4)) ||
       (rc = G->cp.alloc((size_t)(n + 1) * 4)) || (rc = G->ce.alloc(std::max<size_t>(E, 1) * 4)) ||
-      (rc = G->ws.alloc((size_t)G->grid * slice)) || (rc = G->lsd_retries.alloc(8)))
+      (rc = G->ws.alloc((size_t)G->grid * slice)) || (rc = G->lsd_retries.alloc(8)) ||
+      (ord && (rc = G->lsd_wq.alloc((size_t)n * 8))))
     return fail(rc);
+  if (ord && hipMemcpy(G->lsd_wq.p, O->lsd_wq.data(), (size_t)n * 8, hipMemcpyHostToDevice) != hipSuccess)
+    return fail(set_err(QLDPC_EHIP, "upload LSD weights"));
   if (hipMemset(G->lsd_retries.p, 0, 8) != hipSuccess) return fail(set_err(QLDPC_EHIP, "clear LSD retry counter"));
   if (hipMemcpy(G->rp.p, g->row_ptr.data(), (size_t)(m + 1) * 4, hipMemcpyHostToDevice) != hipSuccess ||
       (E && hipMemcpy(G->ci.p, g->col_idx.data(), E * 4, hipMemcpyHostToDevice) != hipSuccess) ||
@@ -857,23 +1170,37 @@ int qldpc_rt::lsd_gpu_launch(qldpc_osd_gpu* osd, const uint8_t* d_synd, const do
   a.m = osd->host.m; a.n = osd->host.n; a.NP = osd->NP; a.k = osd->host.lsd_k;
   a.cap_l = osd->lsd_cap;
   a.cap_h = std::max(64, (a.m + 63) / 64 * 64);
-  a.L = lsd_layout(a.m, a.n, a.NP);
+  const bool ord = osd->host.lsd_w > 0;
+  a.L = lsd_layout(a.m, a.n, a.NP, ord);
+  a.wq = static_cast<const long long*>(osd->lsd_wq.p);
+  a.method = osd->host.lsd_method; a.w = osd->host.lsd_w;
+  a.dcap_l = ord ? a.cap_l : 0;
+  a.dcap_h = ord ? a.n : 0;
   const int grid = (int)std::min<long long>(B, osd->grid);
-  hipLaunchKernelGGL(lsd_gpu_kernel, dim3(grid), dim3(kLsdThreads), osd->lds, (hipStream_t)stream, a);
+  if (ord)
+    hipLaunchKernelGGL(lsd_gpu_kernel<true>, dim3(grid), dim3(kLsdThreads), osd->lds, (hipStream_t)stream, a);
+  else
+    hipLaunchKernelGGL(lsd_gpu_kernel<false>, dim3(grid), dim3(kLsdThreads), osd->lds, (hipStream_t)stream, a);
   QLDPC_HIP(hipGetLastError());
   return 0;
 }
 
 extern "C" {
 
-int qldpc_osd_gpu_create_lsd(const qldpc_graph* g, int32_t bits_per_step, qldpc_osd_gpu** out) {
+int qldpc_osd_gpu_create_lsd_order(const qldpc_graph* g, const double* channel_probs, int32_t bits_per_step,
+                                   int32_t lsd_method, int32_t lsd_order, qldpc_osd_gpu** out) {
   if (!g || !out) return set_err(QLDPC_EINVAL, "NULL argument");
   qldpc_osd* O = nullptr;
-  int rc = qldpc_osd_create_lsd(g->m, g->n, g->row_ptr.data(), g->col_idx.data(), bits_per_step, &O);
+  int rc = qldpc_osd_create_lsd_order(g->m, g->n, g->row_ptr.data(), g->col_idx.data(), channel_probs, bits_per_step,
+                                      lsd_method, lsd_order, &O);
   if (rc) return rc;
   rc = qldpc_rt::lsd_gpu_from_host(g, O, out);
   qldpc_osd_destroy(O);
   return rc;
+}
+
+int qldpc_osd_gpu_create_lsd(const qldpc_graph* g, int32_t bits_per_step, qldpc_osd_gpu** out) {
+  return qldpc_osd_gpu_create_lsd_order(g, nullptr, bits_per_step, 0, 0, out);
 }
 
 int qldpc_lsd_gpu_decode(qldpc_osd_gpu* osd, const uint8_t* d_synd, const double* d_post, const uint8_t* d_conv,

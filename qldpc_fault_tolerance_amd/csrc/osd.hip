@@ -320,6 +320,8 @@ int qldpc_osd_rank(const qldpc_osd* osd, int32_t* rank) {
 
 int qldpc_osd_set_side_probs(qldpc_osd* osd, const double* p0, const double* p1) {
   if (!osd || !p0 || !p1) return set_err(QLDPC_EINVAL, "NULL argument");
+  if (osd->lsd_k && osd->lsd_w > 0)
+    return set_err(QLDPC_ENOTSUP, "LSD of order > 0 has no side decode (its candidates are weighed by the handle's priors)");
   std::vector<double> w0, w1;
   if (!side_weights(p0, osd->n, w0) || !side_weights(p1, osd->n, w1))
     return set_err(QLDPC_EINVAL, "side probabilities must lie in (0, 1)");
@@ -1311,7 +1313,7 @@ int qldpc_osd_gpu_geometry(const qldpc_osd_gpu* osd, int32_t* row_words, int32_t
 int qldpc_osd_gpu_destroy(qldpc_osd_gpu* osd) {
   if (!osd) return 0;
   osd->rp.release(); osd->ci.release(); osd->ws.release(); osd->iws.release(); osd->softw.release();
-  osd->sw0.release(); osd->sw1.release(); osd->cp.release(); osd->ce.release(); osd->lsd_retries.release();
+  osd->sw0.release(); osd->sw1.release(); osd->cp.release(); osd->ce.release(); osd->lsd_retries.release(); osd->lsd_wq.release();
   delete osd;
   return 0;
 }

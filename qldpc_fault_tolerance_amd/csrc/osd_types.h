@@ -18,6 +18,11 @@ struct qldpc_osd {
   // rows of H as well; 0 = OSD
   int lsd_k = 0;
   std::vector<int32_t> row_ptr, col_idx;
+  // qldpc_osd_create_lsd_order: the candidate search on the grown clusters.  lsd_w = the order in force
+  // (0 under method 0: today's order-0 stage), lsd_wq [n] = floor(log(1 / p_j) 2^32 + 0.5), empty without
+  // priors in (0, 1)
+  int lsd_method = 0, lsd_w = 0;
+  std::vector<long long> lsd_wq;
 };
 
 struct qldpc_osd_gpu {
@@ -33,6 +38,7 @@ struct qldpc_osd_gpu {
   // capacity of the active image (0: the image lives in the HBM slice ws alone)
   qldpc_rt::DevBuf cp, ce, lsd_retries;
   int lsd_cap = 0;
+  qldpc_rt::DevBuf lsd_wq;  // [n] candidate weights of a handle of order > 0, else empty
 };
 
 namespace qldpc_rt {

@@ -338,26 +338,46 @@ class BPLSD_Decoder(BPOSD_Decoder):
     include/qldpc_hip.h, csrc/lsd.hip) where BP does not converge: clusters grown around the unsatisfied
     checks in BP's reliability order, ``bits_per_step`` columns per cluster and round, elimination inside
     the clusters alone.  A :class:`BPOSD_Decoder` with the same attributes, so every shot loop that takes
-    one takes this; the stage weighs no candidates, hence ``osd0_decoding == osdw_decoding``."""
+    one takes this.  At order 0 the stage weighs no candidates, hence ``osd0_decoding == osdw_decoding``;
+    ``lsd_method`` "lsd_e" / "lsd_cs" with ``lsd_order`` > 0 grow each cluster to ``lsd_order`` free columns
+    and return the lightest candidate under ``channel_probs`` (``osd0_decoding`` stays the OSD-0 solution on
+    the grown clusters).  Such a stage has no per-shot side tables: with ``side_probs`` it raises."""
 
     def __init__(self, h, channel_probs, max_iter, bp_method, ms_scaling_factor, bits_per_step: int = 1,
                  precision: int = 64, device: int | None = None, use_gpu_osd: bool = True,
-                 schedule: str = "parallel", side_probs=None):
+                 schedule: str = "parallel", side_probs=None, *, lsd_method="lsd_0", lsd_order: int = 0):
+        from .engine import lsd_method_code
+
         self.bits_per_step = int(bits_per_step)
+        self.lsd_method, self.lsd_order = lsd_method, int(lsd_order)
+        if side_probs is not None and lsd_method_code(lsd_method) != 0 and self.lsd_order > 0:
+            raise ValueError("side_probs with lsd_order > 0: LSD of higher order has no per-shot side tables")
         super().__init__(h, channel_probs, max_iter, bp_method, ms_scaling_factor, "osd_0", 0, precision=precision,
                          device=device, use_gpu_osd=use_gpu_osd, schedule=schedule, side_probs=side_probs)
 
     def new_gpu_stage(self, graph):
         from .engine import DeviceLSD
 
-        return DeviceLSD(graph, self.bits_per_step)
+        return DeviceLSD(graph, self.bits_per_step, self._stage_probs(graph.n), self.lsd_method, self.lsd_order)
+
+    def _stage_probs(self, n):
+        return np.ascontiguousarray(np.broadcast_to(self.channel_probs, (n,)))
 
     def _second_stage(self, H, use_gpu_osd):
         from .engine import DeviceLSD, HostLSD
 
-        gpu = (self.new_gpu_stage(self.decoder.graph)
-               if use_gpu_osd and DeviceLSD.supported(H.m, H.n) else None)
-        return HostLSD(H, self.bits_per_step), gpu
+        from ._native import ENOTSUP, QldpcError
+
+        gpu = None
+        if use_gpu_osd and DeviceLSD.supported(H.m, H.n):
+            try:
+                gpu = self.new_gpu_stage(self.decoder.graph)
+            except QldpcError as e:
+                # an order > 0 handle keeps more tables in LDS than DeviceLSD.supported's order-0 envelope
+                # counts: past it the native host stage decodes, as it does past the envelope itself
+                if e.rc != ENOTSUP:
+                    raise
+        return HostLSD(H, self.bits_per_step, self._stage_probs(H.n), self.lsd_method, self.lsd_order), gpu
 
     def lsd_stats_batch(self, synd, side=None):
         """:meth:`decode_batch` plus the stage's statistics: (x [B, n] int, stats [B, 4] int32 = valid,
@@ -477,9 +497,11 @@ class BPLSD_Decoder_Class(DecoderClass):
     """:class:`BPLSD_Decoder` factory keyed like :class:`BPOSD_Decoder_Class`."""
 
     def __init__(self, max_iter_ratio: int, bp_method: str, ms_scaling_factor: float, bits_per_step: int = 1,
-                 precision: int = 64, device: int | None = None, schedule: str = "parallel"):
+                 precision: int = 64, device: int | None = None, schedule: str = "parallel", *,
+                 lsd_method="lsd_0", lsd_order: int = 0):
         self.decoder_default_params = {"max_iter_ratio": max_iter_ratio, "bp_method": bp_method,
-                                       "ms_scaling_factor": ms_scaling_factor, "bits_per_step": bits_per_step}
+                                       "ms_scaling_factor": ms_scaling_factor, "bits_per_step": bits_per_step,
+                                       "lsd_method": lsd_method, "lsd_order": lsd_order}
         self.precision = precision
         self.device = device
         self.schedule = schedule
@@ -492,7 +514,8 @@ class BPLSD_Decoder_Class(DecoderClass):
         d = self.decoder_default_params
         return BPLSD_Decoder(h=p["h"], channel_probs=probs, max_iter=num_qubits / d["max_iter_ratio"],
                              bp_method=d["bp_method"], ms_scaling_factor=d["ms_scaling_factor"],
-                             bits_per_step=d["bits_per_step"], precision=self.precision, device=self.device,
+                             bits_per_step=d["bits_per_step"], lsd_method=d["lsd_method"], lsd_order=d["lsd_order"],
+                             precision=self.precision, device=self.device,
                              schedule=self.schedule, side_probs=p.get("side_probs"))
 
 

@@ -131,6 +131,18 @@ def osd_method_code(osd_method) -> int:
     return OSD_METHODS[key]
 
 
+LSD_METHODS = {"lsd_0": 0, "lsd_e": 1, "lsd_cs": 2}
+
+
+def lsd_method_code(lsd_method) -> int:
+    if isinstance(lsd_method, (int, np.integer)):
+        return int(lsd_method)
+    key = str(lsd_method).lower()
+    if key not in LSD_METHODS:
+        raise ValueError(f"unknown lsd_method {lsd_method!r}")
+    return LSD_METHODS[key]
+
+
 class _Handle:
     """Owner of one C-ABI handle: ``_create`` fills ``handle``, ``__del__`` frees it with the
     library function the class names in ``_destroy``."""
@@ -526,18 +538,31 @@ class HostLSD(HostOSD):
     """BP+LSD's second stage on the host (``qldpc_osd_create_lsd``, csrc/lsd.hip): clusters grown
     around the unsatisfied checks in BP's reliability order, ``bits_per_step`` columns per cluster
     and round, elimination inside the clusters alone (the law: include/qldpc_hip.h).  A
-    :class:`HostOSD` in every call; it uses no channel weights, so ``osd0 == osdw`` and a side decode
-    equals the plain one."""
+    :class:`HostOSD` in every call.  At order 0 (``lsd_method="lsd_0"`` or ``lsd_order=0``) it uses no
+    channel weights, so ``osd0 == osdw`` and a side decode equals the plain one.  ``lsd_method`` "lsd_e" /
+    "lsd_cs" with ``lsd_order`` > 0 (``qldpc_osd_create_lsd_order``) grow every cluster to ``lsd_order``
+    free columns and weigh candidates by ``channel_probs``: ``osdw`` is then the lightest, ``osd0`` the
+    OSD-0 solution on the same clusters, and side tables are refused (``QLDPC_ENOTSUP``)."""
 
-    def __init__(self, H, bits_per_step: int = 1):
+    def __init__(self, H, bits_per_step: int = 1, channel_probs=None, lsd_method="lsd_0", lsd_order: int = 0):
         c = H if isinstance(H, CSR) else CSR.from_dense(H)
         self.m, self.n = c.m, c.n
         self.osd_method, self.osd_order = 0, 0
         self.bits_per_step = int(bits_per_step)
+        self.lsd_method, self.lsd_order = lsd_method_code(lsd_method), int(lsd_order)
+        self._probs = None if channel_probs is None else _channel_probs(channel_probs, self.n)  # (the C side reads n)
         rp = np.ascontiguousarray(c.row_ptr, dtype=np.int32)
         ci = np.ascontiguousarray(c.col_idx, dtype=np.int32)
-        self._create("qldpc_osd_create_lsd", self.m, self.n, _np_ptr(rp), _np_ptr(ci), self.bits_per_step)
+        self._create("qldpc_osd_create_lsd_order", self.m, self.n, _np_ptr(rp), _np_ptr(ci),
+                     None if self._probs is None else _np_ptr(self._probs), self.bits_per_step, self.lsd_method,
+                     self.lsd_order)
         self.rank, = self._ints("qldpc_osd_rank", "qldpc_osd_rank", 1)
+
+    def weights(self) -> np.ndarray:
+        """The integer candidate weights wq [n] of the handle (``qldpc_lsd_weights``)."""
+        wq = np.zeros(self.n, np.int64)
+        _native.check(_native.lib().qldpc_lsd_weights(self.handle, _np_ptr(wq)), "qldpc_lsd_weights")
+        return wq
 
     def decode_batch_stats(self, synd, post, conv=None, bp_corr=None, threads: int = 0):
         """(x [B, n] uint8, stats [B, 4] int32 = valid, rounds, active columns, clusters)."""
@@ -560,7 +585,9 @@ class DeviceLSD(DeviceOSD):
     """BP+LSD's second stage on the GPU (``qldpc_osd_gpu_create_lsd``): one workgroup per
     non-converged syndrome, the whole cluster growth and solution inside the kernel.  A
     :class:`DeviceOSD` in every call (``DeviceMC.set_osd`` / ``set_staged_osd``, the
-    phenomenological and circuit loops, ``bposd_batch``)."""
+    phenomenological and circuit loops, ``bposd_batch``).  ``supported`` is the envelope of order 0; a handle
+    of order > 0 keeps 4 m more bytes of tables in LDS, so near m = n = 8192 its creation can still answer
+    ``QLDPC_ENOTSUP`` (:class:`~.decoders.BPLSD_Decoder` then keeps the host stage)."""
 
     MAX_M = 8192
 
@@ -568,11 +595,16 @@ class DeviceLSD(DeviceOSD):
     def supported(m, n) -> bool:  # noqa: D102 (the GPU stage's envelope)
         return m <= DeviceLSD.MAX_M and n <= DeviceOSD.MAX_N
 
-    def __init__(self, graph: DeviceGraph, bits_per_step: int = 1):
+    def __init__(self, graph: DeviceGraph, bits_per_step: int = 1, channel_probs=None, lsd_method="lsd_0",
+                 lsd_order: int = 0):
         self.graph = graph
         self.osd_method, self.osd_order = 0, 0
         self.bits_per_step = int(bits_per_step)
-        self._create("qldpc_osd_gpu_create_lsd", graph.handle, self.bits_per_step)
+        self.lsd_method, self.lsd_order = lsd_method_code(lsd_method), int(lsd_order)
+        self._probs = None if channel_probs is None else _channel_probs(channel_probs, graph.n)
+        self._create("qldpc_osd_gpu_create_lsd_order", graph.handle,
+                     None if self._probs is None else _np_ptr(self._probs), self.bits_per_step, self.lsd_method,
+                     self.lsd_order)
 
     def geometry(self) -> dict:
         """:meth:`DeviceOSD.geometry` (``row_words`` = 0) plus ``lds_rows``, the row capacity of the

@@ -1,5 +1,6 @@
 #!/usr/bin/env python
-"""Plain BP, BP+OSD-0, BP+OSD-E(10) and BP+LSD (bits_per_step 1, 2, 3) side by side on one bundled code:
+"""Plain BP, BP+OSD-0, BP+OSD-E(10), BP+OSD-CS(10), BP+LSD of order 0 (bits_per_step 1, 2, 3) and of higher
+order (bits_per_step 1 with lsd_e 2, lsd_e 4, lsd_cs 4, lsd_cs 8) side by side on one bundled code:
 failures, decodes handed to the second stage and shots/s of the data-error shot loop, plus a probe of
 the second stage alone (its kernel time on one batch, and for LSD the mean rounds and active columns
 and the decodes that outgrew the LDS image and ran again on the HBM slice).
@@ -105,13 +106,17 @@ def main():
     r, ms, al, pr = a.max_iter_ratio, "minimum_sum", 0.625, a.precision
     rows = [(f"plain BP({mi})", BP_Decoder_Class(r, ms, al, pr), fused),
             (f"BP({mi})+OSD-0", BPOSD_Decoder_Class(r, ms, al, "osd_0", 0, pr), second),
-            (f"BP({mi})+OSD-E(10)", BPOSD_Decoder_Class(r, ms, al, "osd_e", 10, pr), second)]
+            (f"BP({mi})+OSD-E(10)", BPOSD_Decoder_Class(r, ms, al, "osd_e", 10, pr), second),
+            (f"BP({mi})+OSD-CS(10)", BPOSD_Decoder_Class(r, ms, al, "osd_cs", 10, pr), second)]
     rows += [(f"BP({mi})+LSD k={k}", BPLSD_Decoder_Class(r, ms, al, k, pr), second) for k in (1, 2, 3)]
+    rows += [(f"BP({mi})+LSD k=1 {meth} {w}",
+              BPLSD_Decoder_Class(r, ms, al, 1, pr, lsd_method=meth, lsd_order=w), second)
+             for meth, w in (("lsd_e", 2), ("lsd_e", 4), ("lsd_cs", 4), ("lsd_cs", 8))]
     out = {"code": a.code, "eval_p": a.p, "precision": a.precision, "shots_per_step": a.shots, "steps": a.steps,
            "warmup": a.warmup, "decoders": {}}
     print(f"{a.code} eval_p={a.p} fp{a.precision}: {a.steps} steps of {a.shots} shots (+{a.warmup} warm-up); "
           f"stage probe on {a.probe} shots (X sector)")
-    print(f"{'decoder':<22}{'failures':>9}{'handed':>9}{'shots/s':>11}  {'(slowest .. fastest)':<22}"
+    print(f"{'decoder':<26}{'failures':>9}{'handed':>9}{'shots/s':>11}  {'(slowest .. fastest)':<22}"
           f"{'stage ms':>9}{'us/decode':>10}{'rounds':>8}{'|A|':>8}{'retried':>9}")
     for name, cls, run in rows:
         res = measure(from_class(name, cls), run, a.shots, a.steps, a.warmup)
@@ -120,8 +125,8 @@ def main():
         out["decoders"][name] = res
         s = res.get("stage", {})
         fmt = lambda v, f: format(v, f) if v is not None else "n/a"  # noqa: E731
-        print(f"{name:<22}{res['failures']:>9}{res['nonconverged_decodes']:>9}{res['shots_per_s']:>11.0f}  "
-              f"({res['shots_per_s_min']:.0f} .. {res['shots_per_s_max']:.0f})".ljust(75) +
+        print(f"{name:<26}{res['failures']:>9}{res['nonconverged_decodes']:>9}{res['shots_per_s']:>11.0f}  "
+              f"({res['shots_per_s_min']:.0f} .. {res['shots_per_s_max']:.0f})".ljust(79) +
               f"{fmt(s.get('stage_ms'), '9.3f'):>9}{fmt(s.get('stage_us_per_handed_decode'), '10.2f'):>10}"
               f"{fmt(s.get('mean_rounds'), '8.1f'):>8}{fmt(s.get('mean_active_columns'), '8.1f'):>8}"
               f"{fmt(s.get('retried_on_hbm'), 'd'):>9}")
